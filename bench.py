@@ -2,7 +2,7 @@
 """Headline benchmark: Mode S (Census -> Hamming -> 8-path SGM -> WTA) in
 Mdisparities/s (W*H*D per second) at 1920x1080, D=128 (BASELINE.json config 2).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
         --master-addr 127.0.0.1 --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -10,9 +10,16 @@ A step = one full disparity computation of one synthetic 1080p pair per rank
 (inputs already resident in HBM), followed for N > 1 by the path's one
 exchange: an RCCL gather of the u16 disparity maps to rank 0 over xGMI.
 Pairs are independent units (weak scaling: every rank matches its own pair).
-Rank 0 prints one JSON line (the driver's contract), including the live
-hipEvent roofline of the dominant kernel and the CPU baseline (the oracle,
-single thread, the same 1080p D=128 frame) timed on this host.
+Rank 0 prints one JSON line (the driver's contract).
+
+A plain run sets up, warms up, times the K steps, writes the last step's
+outputs if --dump-outputs is given, and prints the line: the headline value,
+ms_per_step and the hipEvent roofline of the two aggregation kernels, which
+the timed region itself measures.  --full adds everything that takes runs of
+its own: the per-kernel breakdown, the sanity and exchange checks, the CPU
+baseline (the oracle on this host, the same frame), Mode R beside its CPU
+port, the frame-overlap and steady-state figures and the live rocprofv3 PMC
+passes (traffic, VALU and engine rooflines).
 """
 from __future__ import annotations
 
@@ -72,9 +79,19 @@ def parse():
                          "(profiles/r03_v8/bench_warmup_probe.log.txt)")
     ap.add_argument("--workload", default="1080p_d128", choices=sorted(WORKLOADS))
     ap.add_argument("--pairs-per-rank", type=int, default=1)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run everything beside the headline figure: "
+                         "per-kernel breakdown, sanity and exchange checks, CPU baselines, Mode R, "
+                         "frame-overlap and steady-state figures, live PMC passes")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, rank 0 writes what the last timed step computed "
+                         "as DIR/<name>.npy (float32 / float64; a fixed seeded sample of each "
+                         "array when they exceed 60 MB together)")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the legs that run on the CPU (oracle baselines, "
+                         "Mode R beside its CPU port) and the figures reported with them")
     ap.add_argument("--pmc", default="live", choices=["live", "committed"],
-                    help="roofline.traffic source: 'live' runs two rocprofv3 PMC passes "
+                    help="with --full, roofline.traffic source: 'live' runs two rocprofv3 PMC passes "
                          "(FETCH_SIZE, WRITE_SIZE) of this workload as child processes on "
                          "rank 0 at N=1 and falls back to the committed profiles/pmc_*.json "
                          "if they fail; 'committed' reads the committed file only")
@@ -120,7 +137,42 @@ def parse():
         a.steps = 20 if batch else 100
     if a.warmup is None:
         a.warmup = 5 if batch else 50
+    if not a.full:     # a plain run: none of the CPU legs, no PMC child processes
+        a.no_cpu_baseline, a.pmc = True, "committed"
     return a
+
+
+DUMP_LIMIT_BYTES = 60 * 1000 * 1000     # array bytes; with the .npy headers well below 64 MB
+DUMP_SEED = 0x5EED
+
+
+def dump_outputs(outdir, arrays, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: write {name: numpy array} as outdir/<name>.npy, float64
+    arrays as they are, everything else as float32 (u8 / u16 values are exact
+    in it).  When the files would exceed `limit` bytes together, each array is
+    cut to the same fraction of its elements: a sample of its flat indices
+    drawn from a generator seeded with DUMP_SEED, so it is the same sample for
+    the same shapes in every run and every build."""
+    os.makedirs(outdir, exist_ok=True)
+    size = lambda v: v.size * (8 if v.dtype == np.float64 else 4)
+    total = sum(size(v) for v in arrays.values())
+    frac = min(1.0, limit / total) if total else 1.0
+    rng = np.random.default_rng(DUMP_SEED)
+    written = {}
+    for name in sorted(arrays):
+        v = np.ascontiguousarray(arrays[name])
+        if frac < 1.0:
+            idx = np.sort(rng.integers(0, v.size, size=int(v.size * frac)))
+            v = v.reshape(-1)[idx]
+        v = v.astype(np.float64 if v.dtype == np.float64 else np.float32)
+        np.save(os.path.join(outdir, name + ".npy"), v)
+        written[name] = v
+    return written
+
+
+def host_u16(t):
+    """A device tensor of u16 disparities (held as int16) as a numpy u16 array."""
+    return t.cpu().numpy().view(np.uint16)
 
 
 def host_cpu():
@@ -496,8 +548,9 @@ def _pmc_pass(counter, args, outdir, child=None, env=None):
     prof = shutil.which("rocprofv3") or "/opt/rocm/bin/rocprofv3"
     counters = counter.split()
     d = os.path.join(outdir, counters[0].lower())
-    child = child if child is not None else ["--steps", "3", "--warmup", "1", "--no-cpu-baseline",
-                                             "--pmc", "committed", "--streams", "1"] + args
+    child = child if child is not None else ["--steps", "3", "--warmup", "1", "--full",
+                                             "--no-cpu-baseline", "--pmc", "committed",
+                                             "--streams", "1"] + args
     cmd = ["timeout", "-s", "KILL", "150", prof, "--pmc"] + counters + ["--kernel-trace",
            "-d", d, "-o", "run", "--output-format", "csv", "--",
            sys.executable, os.path.abspath(__file__)] + child
@@ -1028,13 +1081,21 @@ def run_array(a, wl, world, rank, local, dev):
             fuse(ctx, allm)
 
     elapsed = timed(a, step, world, dev, ctxs)
-    kernels = breakdown(a, step, world, ctxs, kernel_table(ctxs))
+    if a.dump_outputs and rank == 0:
+        # what rank 0 holds after the last timed step: every pair's map (its
+        # own at N = 1, the gathered ones otherwise) and the fused depth
+        dump_outputs(a.dump_outputs, {"disparity": host_u16(maps["all"]),
+                                      "depth": depth.cpu().numpy(),
+                                      "nvalid": nvalid.cpu().numpy()})
+    kernels = kernel_table(ctxs)         # sgm_paths + wta_hv, from the timed region
+    if a.full:
+        kernels = breakdown(a, step, world, ctxs, kernels)
     value = n_units * W * H * D * a.steps / elapsed / 1e6
     # committed PMC bytes per pair: the 1080p D=128 frame's for the 1080p rigs
     traffic_wl = "1080p_d128" if (W, H, D) == (1920, 1080, 128) else a.workload
     fpl = batch_frames_per_launch(len(jobs), len(ctxs)) if a.batch else 1
     exchange = None
-    if multi:
+    if multi and a.full:
         def recompute(u):
             i, j = pairs[u]
             sx, sy, _ = synth.pair_step(grid[i], grid[j])
@@ -1049,7 +1110,8 @@ def run_array(a, wl, world, rank, local, dev):
         step()                           # the compute-only steps fused the stand-in
         torch.cuda.synchronize()
     out = None
-    if rank == 0:
+    exact = None
+    if rank == 0 and a.full:
         # sanity: camera 0 sees the texture unwarped, so its fused depth must be
         # the stripe-plane depth pitch*f/(delta*ps) away from stripe edges
         z0 = depth[0].cpu().numpy()
@@ -1062,6 +1124,7 @@ def run_array(a, wl, world, rank, local, dev):
         inner[D:H - D, D:W - D] = True
         inner &= ~edge[None, :]
         exact = float(np.mean(np.abs(z0[inner] - truth[inner]) <= 1e-9 * truth[inner]))
+    if rank == 0:
         out = {
             "metric": f"Mdisparities/sec (W·H·D/s), camera array ({rig_label}), "
                       f"{W}x{H} D={D}, gather + fuse",
@@ -1086,7 +1149,7 @@ def run_array(a, wl, world, rank, local, dev):
                        "streams_per_rank": len(ctxs), "batched": bool(a.batch)},
             "kernels_ms": {k: round(v["avg_ms"], 4) for k, v in kernels.items()},
             "fused_maps_per_s": round(len(groups) * a.steps / elapsed, 2),
-            "ref_interior_depth_exact_frac": round(exact, 4),
+            "ref_interior_depth_exact_frac": round(exact, 4) if exact is not None else None,
             "roofline": roofline_of(kernels, W, H, D, traffic_wl, overlapped=len(ctxs) > 1,
                                     frames_per_launch=fpl),
             "aggregation_roofline": aggregation_roofline_of(kernels, W, H, D,
@@ -1235,44 +1298,58 @@ def run_engine(a, wl):
     run(step, a.warmup, 0)
     elapsed = run(step, a.steps, 3)                     # SVA_TIMING_AGG in the timed region
     timed_k = kernel_table(ctxs)
-    run(step, min(a.steps, 5), 1)                       # every kernel, after the timed region
-    kernels = kernel_table(ctxs)
-    for k in AGG_KERNELS:
-        if k in timed_k:
-            kernels[k] = timed_k[k]
-    for c in ctxs:
-        c.set_timing(0)
-    compute_ms = run(step_local, max(1, min(a.steps, 10)), 0) / max(1, min(a.steps, 10)) * 1e3
-    # every gathered map vs a single-context recompute on device 0
-    check = sva.Context(0)
-    cs = torch.cuda.Stream(devs[0])
-    check.set_stream(cs.cuda_stream)
-    mism = []
-    got = maps.cpu()
-    checked = min(n_units, max(32, N))      # bounded: 32 units, every owner device
-    for u in range(checked):
-        L, R, p = units[u]
-        ref = torch.zeros((H, W), dtype=torch.int16, device=devs[0])
-        Ld, Rd = torch.from_numpy(L).to(devs[0]), torch.from_numpy(R).to(devs[0])
-        torch.cuda.synchronize(devs[0])
-        check.disparity_sgm_d(Ld.data_ptr(), Rd.data_ptr(), W, H, W, p, ref.data_ptr())
-        check.synchronize()
-        if not torch.equal(ref.cpu(), got[u]):
-            mism.append(u)
-    check.close()
+    if a.dump_outputs:
+        arrays = {"disparity": host_u16(maps)}
+        if sub is not None:
+            arrays["subpixel"] = sub.cpu().numpy()
+        if groups:
+            arrays["depth"], arrays["nvalid"] = depth.cpu().numpy(), nvalid.cpu().numpy()
+        dump_outputs(a.dump_outputs, arrays)
+        del arrays
     ms_per_step = elapsed / a.steps * 1e3
     value = n_units * W * H * D * a.steps / elapsed / 1e6
     model, nproc, _ = host_cpu()
-    exchange = {"backend": "rccl", "route": "C-ABI engine: sva_multi_create + sva_batch_sgm_d, "
-                "single-process communicator (ncclCommInitAll), grouped ncclSend/ncclRecv to "
-                "device 0", "rccl_ranks": N, "devices": N, "streams_per_device": S,
-                "units_checked": checked, "units_equal_single_context": checked - len(mism),
-                "remote_unit_recomputed": {"unit": 1 % n_units, "owner_device": (1 % n_units) % N,
-                                           "equal": (1 % n_units) not in mism},
-                "ok": not mism,
-                "compute_only_ms_per_step": round(compute_ms, 4),
-                "exposed_gather_ms_per_step": round(ms_per_step - compute_ms, 4),
-                "map_bytes_per_unit": W * H * 2 + (W * H * 4 if subpixel else 0)}
+    kernels, exchange, mism = timed_k, None, []
+    if a.full:
+        run(step, min(a.steps, 5), 1)                   # every kernel, after the timed region
+        kernels = kernel_table(ctxs)
+        for k in AGG_KERNELS:
+            if k in timed_k:
+                kernels[k] = timed_k[k]
+        for c in ctxs:
+            c.set_timing(0)
+        n_local = max(1, min(a.steps, 10))
+        compute_ms = run(step_local, n_local, 0) / n_local * 1e3
+        # every gathered map vs a single-context recompute on device 0
+        check = sva.Context(0)
+        cs = torch.cuda.Stream(devs[0])
+        check.set_stream(cs.cuda_stream)
+        got = maps.cpu()
+        checked = min(n_units, max(32, N))      # bounded: 32 units, every owner device
+        for u in range(checked):
+            L, R, p = units[u]
+            ref = torch.zeros((H, W), dtype=torch.int16, device=devs[0])
+            Ld, Rd = torch.from_numpy(L).to(devs[0]), torch.from_numpy(R).to(devs[0])
+            torch.cuda.synchronize(devs[0])
+            check.disparity_sgm_d(Ld.data_ptr(), Rd.data_ptr(), W, H, W, p, ref.data_ptr())
+            check.synchronize()
+            if not torch.equal(ref.cpu(), got[u]):
+                mism.append(u)
+        check.close()
+        exchange = {
+            "backend": "rccl", "route": "C-ABI engine: sva_multi_create + sva_batch_sgm_d, "
+            "single-process communicator (ncclCommInitAll), grouped ncclSend/ncclRecv to "
+            "device 0", "rccl_ranks": N, "devices": N, "streams_per_device": S,
+            "units_checked": checked, "units_equal_single_context": checked - len(mism),
+            "remote_unit_recomputed": {"unit": 1 % n_units, "owner_device": (1 % n_units) % N,
+                                       "equal": (1 % n_units) not in mism},
+            "ok": not mism,
+            "compute_only_ms_per_step": round(compute_ms, 4),
+            "exposed_gather_ms_per_step": round(ms_per_step - compute_ms, 4),
+            "map_bytes_per_unit": W * H * 2 + (W * H * 4 if subpixel else 0)}
+    else:
+        for c in ctxs:
+            c.set_timing(0)
     if "rig" in wl:
         metric = (f"Mdisparities/sec (W·H·D/s), camera array ({rig_label}), {W}x{H} D={D}, "
                   "gather + fuse")
@@ -1470,15 +1547,21 @@ def main():
                     gathered[b] = ev
 
     elapsed = timed(a, step, world, dev, ctxs)
-    kernels = breakdown(a, step, world, ctxs, kernel_table(ctxs))
-    # sanity: the result is a real disparity map (exact on the stripe interiors)
-    d0 = disps[0][0].cpu().numpy().view(np.uint16)
-    if rehearsal is not None and comm is not None:
-        last = disps[(it[0] - 1) % nbuf]
-        assert torch.equal(rehearsal[0], last), "overlapped gather copied the wrong buffer"
-    assert d0.max() < D, "disparity out of range"
+    if a.dump_outputs and rank == 0:
+        # this rank's maps of the last timed step, as disparity_sgm_d returned them
+        dump_outputs(a.dump_outputs, {"disparity": host_u16(disps[(it[0] - 1) % nbuf]),
+                                      "subpixel": sub.cpu().numpy()})
+    kernels = kernel_table(ctxs)         # sgm_paths + wta_hv, from the timed region
+    if a.full:
+        kernels = breakdown(a, step, world, ctxs, kernels)
+        # sanity: the result is a real disparity map (exact on the stripe interiors)
+        d0 = host_u16(disps[0][0])
+        if rehearsal is not None and comm is not None:
+            last = disps[(it[0] - 1) % nbuf]
+            assert torch.equal(rehearsal[0], last), "overlapped gather copied the wrong buffer"
+        assert d0.max() < D, "disparity out of range"
     exchange = None
-    if world > 1 or rccl1:
+    if a.full and (world > 1 or rccl1):
         def recompute(u):
             L, R, _ = synth.stereo_pair(H, W, D, 0, -1, seed=seed0 + u)
             Ld, Rd = torch.from_numpy(L).to(dev), torch.from_numpy(R).to(dev)

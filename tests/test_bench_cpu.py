@@ -279,3 +279,47 @@ def test_placement_report(bench):
     r = bench.placement_report([FakeCtx(4_193_100, 4_838_900), FakeCtx(0, 0)])
     assert r["contexts"] == [{"kept_ms": 4.1931, "worst_ms": 4.8389}]
     assert "fastest set is kept" in r["note"]
+
+
+def test_dump_outputs_whole_and_sampled(bench, tmp_path):
+    """--dump-outputs: float32 (float64 kept) .npy per array; above the size
+    limit every array is cut to the same seeded sample of its flat indices,
+    identical from call to call."""
+    import numpy as np
+    rng = np.random.default_rng(3)
+    maps = rng.integers(0, 65536, size=(2, 30, 40), dtype=np.uint16)
+    depth = rng.random((1, 30, 40))
+    nv = rng.integers(0, 9, size=(1, 30, 40), dtype=np.uint8)
+    arrays = {"disparity": maps, "depth": depth, "nvalid": nv}
+    w = bench.dump_outputs(str(tmp_path / "a"), arrays)
+    d = np.load(tmp_path / "a" / "disparity.npy")
+    assert d.dtype == np.float32 and np.array_equal(d, maps.astype(np.float32))
+    z = np.load(tmp_path / "a" / "depth.npy")
+    assert z.dtype == np.float64 and np.array_equal(z, depth)
+    assert np.load(tmp_path / "a" / "nvalid.npy").dtype == np.float32 and set(w) == set(arrays)
+    # 2400 * 4 + 1200 * 8 + 1200 * 4 = 24,000 bytes whole; a 6,000-byte limit keeps a quarter
+    for sub in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / sub), arrays, limit=6000)
+    b = {n: np.load(tmp_path / "b" / (n + ".npy")) for n in arrays}
+    c = {n: np.load(tmp_path / "c" / (n + ".npy")) for n in arrays}
+    assert [b[n].shape for n in sorted(b)] == [(300,), (600,), (300,)]
+    assert sum(v.nbytes for v in b.values()) <= 6000
+    assert all(np.array_equal(b[n], c[n]) for n in arrays)
+    assert np.isin(b["disparity"], maps.astype(np.float32)).all()
+    # a changed element inside the sample shows in the dump
+    idx = np.sort(np.random.default_rng(bench.DUMP_SEED).integers(0, depth.size, size=300))
+    depth2 = depth.copy()
+    depth2.reshape(-1)[idx[0]] += 1.0
+    bench.dump_outputs(str(tmp_path / "d"), dict(arrays, depth=depth2), limit=6000)
+    assert not np.array_equal(np.load(tmp_path / "d" / "depth.npy"), b["depth"])
+
+
+def test_plain_run_switches_the_side_measurements_off(bench, monkeypatch):
+    import sys
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 2, False, None)
+    assert a.no_cpu_baseline and a.pmc == "committed"
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "x"])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == "x" and not a.no_cpu_baseline and a.pmc == "live"

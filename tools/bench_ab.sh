@@ -20,7 +20,7 @@ for ((r = 0; r < REPS; r++)); do
     IFS='|' read -r label envs args <<< "$spec"
     log="gpurun_out/ab_${label}.log"
     # shellcheck disable=SC2086
-    env $envs timeout -k 10 "${TIMEOUT:-300}" python bench.py --no-cpu-baseline $args > "$log" 2>&1
+    env $envs timeout -k 10 "${TIMEOUT:-300}" python bench.py --full --no-cpu-baseline $args > "$log" 2>&1
     rc=$?
     echo "$label rep=$r rc=$rc $(grep -o '"value": [0-9.]*' "$log") $(grep -o '"kernels_ms": {[^}]*}' "$log")"
     if [ $rc -ne 0 ]; then tail -5 "$log"; exit $rc; fi
