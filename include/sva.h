@@ -158,13 +158,25 @@ int sva_kernel_time(void* ctx, const char* name, double* total_ms, int64_t* coun
  *                            times (1..8; 1 = no check; 0 = the default, 6).
  *   SVA_DEBUG_PLACEMENT_NS   get: the path kernel's time on the set the last
  *                            check kept, ns (0: no check ran).
- *   SVA_DEBUG_PLACEMENT_WORST_NS  get: the slowest set that check timed, ns. */
+ *   SVA_DEBUG_PLACEMENT_WORST_NS  get: the slowest set that check timed, ns.
+ *   SVA_DEBUG_DIAG_ROUTE     get: how the last single-frame aggregation carried
+ *                            its four diagonal directions: 0 = four L_r
+ *                            volumes, 1 = two pair-sum volumes (the pair
+ *                            route: native D = 128 with 2 * P2 <= 255, frames
+ *                            of at least the threshold below).
+ *   SVA_DEBUG_DIAG_PAIR_MIN_PIXELS  set / get: the smallest frame (W * H) that
+ *                            takes the pair route; -1 restores the built-in
+ *                            threshold (small frames are faster on four
+ *                            volumes), 0 lets the parity tests run the pair
+ *                            route at every size. */
 #define SVA_DEBUG_PLANE_SPLIT 1
 #define SVA_DEBUG_FAIL_COST_AT 2
 #define SVA_DEBUG_SIDE_IDLE 3
 #define SVA_DEBUG_PLACEMENT_TRIALS 4
 #define SVA_DEBUG_PLACEMENT_NS 5
 #define SVA_DEBUG_PLACEMENT_WORST_NS 6
+#define SVA_DEBUG_DIAG_ROUTE 7
+#define SVA_DEBUG_DIAG_PAIR_MIN_PIXELS 8
 int sva_set_debug(void* ctx, int key, int64_t value);
 int sva_get_debug(void* ctx, int key, int64_t* value);
 

@@ -40,6 +40,8 @@ SVA_DEBUG_SIDE_IDLE = 3
 SVA_DEBUG_PLACEMENT_TRIALS = 4
 SVA_DEBUG_PLACEMENT_NS = 5
 SVA_DEBUG_PLACEMENT_WORST_NS = 6
+SVA_DEBUG_DIAG_ROUTE = 7
+SVA_DEBUG_DIAG_PAIR_MIN_PIXELS = 8
 # The ABI this binding is written against (include/sva.h SVA_ABI_VERSION).
 ABI_VERSION = 6
 

@@ -40,6 +40,9 @@ struct PathGeom {
     // f's buffers at C + f*cstr, L8 + f*lstr, CK + f*ckstr, CKV + f*ckvstr
     int npair;
     size_t cstr, lstr, ckstr, ckvstr;
+    // the pair route: the diagonals as two pair-sum volumes
+    int pair;     // 1: directions 4..7 run as pair lines (sgm_paths_kernel<DPL, true>)
+    int dreal;    // the caller's disparities (< D: padded frame, §4.7)
 };
 
 // Tile-pipeline checkpoints.  With g.ckpt set, the
@@ -612,6 +615,174 @@ template <int DPL, bool PAD, bool PIN = false>
 __device__ __forceinline__ void load_state(rsrc_t r, unsigned off, unsigned (&A)[DPL / 2],
                                            unsigned& m, const unsigned (&padm)[DPL / 2]) {
     state_from_words<DPL, PAD, PIN>(bload<DPL / 4>(r, off), A, m, padm);
+}
+
+// One PAIR line: a down diagonal (direction 4 or 6, x step
+// rx) and the opposite up diagonal (5 or 7), which visits the same pixels
+// ((line + rx*y) mod W, y) in reverse and restarts between the same two rows.
+// L_r - C = u - m lies in [0, P2] (sgm_step_c), so with P2 <= 127 the pair sum
+//   E(p, d) = (L_dn - C) + (L_up - C) <= 254
+// fits the u8 volume word that one of the two directions had before, and the
+// final kernel adds the 2C back.  The wave
+//   1. walks the line down like path_line<.., CKPT = 3, SL>: no volume, the
+//      state at the last row of every 2^SL-row segment to the row-checkpoint
+//      plane rCK (at the pixel's column);
+//   2. comes back up segment by segment: the segment's rows of cost loaded
+//      once; the down recurrence re-run forward from the checkpoint above the
+//      segment (zero state at the top), its L - C rows kept u8-packed; the up
+//      recurrence backward over the same cost registers; E stored per pixel.
+// The checkpoints are wave-private: a wave reads back only what it stored
+// itself, after its stores have retired (vmcnt 0) and past the vector L1.
+// The next segment's cost rows and checkpoint are loaded while this one
+// computes.
+template <int DPL, int PF, int SL>
+__device__ __forceinline__ void pair_line(rsrc_t rC, rsrc_t rE, const PathGeom& g, int rx, int line,
+                                          int k, rsrc_t rCK) {
+    constexpr int NW = DPL / 4, NP = DPL / 2, SEG = 1 << SL;
+    path_line<DPL, true, PF, 3, SL>(rC, rC, g, rx, 1, line, k, rCK);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // own checkpoints retired before the loads below
+
+    const int W = g.W, H = g.H;
+    const unsigned uW = (unsigned)W, uD = (unsigned)g.D;
+    const unsigned P1 = (unsigned)g.P1, P2 = (unsigned)g.P2;
+    const unsigned lane_d = (unsigned)(k * DPL);
+    const int jrow = (int)((threadIdx.x >> 4) & 3);               // row of the line in its wave
+    const int l0 = __builtin_amdgcn_readfirstlane(line - jrow);
+    const int nseg = (H + SEG - 1) >> SL;
+    // a step into this column comes from across the image edge: the recurrence restarts
+    const int xdn = rx > 0 ? 0 : W - 1, xup = rx > 0 ? W - 1 : 0;
+    unsigned padm[NP];
+#pragma unroll
+    for (int j = 0; j < NP; j++) {
+        const int dl = k * DPL + pair_d<DPL>(j, 0), dh = k * DPL + pair_d<DPL>(j, 1);
+        padm[j] = (dl >= g.dreal ? 0x0000ffffu : 0u) | (dh >= g.dreal ? 0xffff0000u : 0u);
+    }
+    auto wrap = [&](int x) { return x >= W ? x - W : (x < 0 ? x + W : x); };
+    // the line's column in the first row of segment s
+    auto seg_x = [&](int s) {
+        int xb = (l0 + rx * (s << SL)) % W;        // wave-uniform
+        xb = xb < 0 ? xb + W : xb;
+        int x = xb + jrow;                         // jrow <= 3: three folds cover W = 1
+        x = x >= W ? x - W : x;
+        x = x >= W ? x - W : x;
+        x = x >= W ? x - W : x;
+        return x;
+    };
+    struct SegLoads {
+        Words<NW> c[SEG], ck;
+    };
+    auto issue = [&](int s, SegLoads& b) {
+        int x = seg_x(s);
+        // rows past the image lie past the volume: the range check returns 0,
+        // and nothing consumes them
+        if (s > 0)
+            b.ck = bload<NW, 16>(rCK, ((unsigned)(s - 1) * uW + (unsigned)wrap(x - rx)) * uD + lane_d);
+#pragma unroll
+        for (int r = 0; r < SEG; r++) {
+            b.c[r] = bload<NW>(rC, ((unsigned)((s << SL) + r) * uW + (unsigned)x) * uD + lane_d);
+            x = wrap(x + rx);
+        }
+    };
+    auto reset_if = [&](bool rs, unsigned (&A)[NP], unsigned& m) {
+        // (wave-uniform branch: only the steps of a wrap pay the selects)
+        if (__builtin_expect(__builtin_amdgcn_ballot_w64(rs) != 0, 0)) {
+#pragma unroll
+            for (int j = 0; j < NP; j++) A[j] = rs ? 0u : A[j];
+            m = rs ? 0u : m;
+        }
+    };
+
+    unsigned Au[NP], mu = 0u;
+#pragma unroll
+    for (int j = 0; j < NP; j++) Au[j] = 0u;       // bottom row: L = C
+    Edges eu;
+    SegLoads cur, nxt;
+    issue(nseg - 1, cur);
+    for (int s = nseg - 1; s >= 0; s--) {
+        __builtin_amdgcn_sched_barrier(0);
+        if (s > 0) issue(s - 1, nxt);
+        __builtin_amdgcn_sched_barrier(0);
+        const int y0 = s << SL;
+        const int nr = H - y0 < SEG ? H - y0 : SEG;       // rows of the segment inside the image
+        int x[SEG];
+        x[0] = seg_x(s);
+#pragma unroll
+        for (int r = 1; r < SEG; r++) x[r] = wrap(x[r - 1] + rx);
+        // ---- the down recurrence again, forward, from the state entering the segment
+        unsigned Ad[NP], md;
+        Edges ed;
+        if (s > 0) {
+            state_from_words<DPL, true>(cur.ck, Ad, md, padm);
+        } else {
+#pragma unroll
+            for (int j = 0; j < NP; j++) Ad[j] = 0u;
+            md = 0u;
+        }
+        unsigned Dn[SEG][NW];                             // L_dn - C per row, u8-packed
+        auto down_row = [&](int r, const Words<NW>& c) {
+            unsigned cp[NP], ow[NW], t[NP];
+            words_to_pairs<DPL>(c.w, cp);
+            sgm_step_c<DPL>(cp, Ad, md, ow, P1, P2, ed);
+#pragma unroll
+            for (int j = 0; j < NP; j++) t[j] = Ad[j] - cp[j];   // L >= C per half: no borrow
+            pairs_to_words<DPL>(t, Dn[r]);
+        };
+        auto up_row = [&](const Words<NW>& c, unsigned (&e)[NW]) {
+            unsigned cp[NP], ow[NW], t[NP];
+            words_to_pairs<DPL>(c.w, cp);
+            sgm_step_c<DPL>(cp, Au, mu, ow, P1, P2, eu);
+#pragma unroll
+            for (int j = 0; j < NP; j++) t[j] = Au[j] - cp[j];
+            pairs_to_words<DPL>(t, e);
+        };
+        // A whole segment that no line of the wave wraps in or next to (all
+        // but ~8 / W of them) runs as one straight block: step i of the down
+        // recurrence beside step i of the up recurrence, two independent
+        // dependency chains the scheduler interleaves, which halves the
+        // latency of the wave's return phase (it is the launch's longest
+        // chain).  A row's E is stored once both of its halves exist.
+        const bool inner = rx > 0 ? x[0] >= 1 && x[0] + SEG <= W - 1 : x[0] - SEG >= 0 && x[0] <= W - 2;
+        if (__builtin_expect(nr == SEG && __builtin_amdgcn_ballot_w64(!inner) == 0, 1)) {
+            unsigned Up[SEG][NW];
+            const unsigned off0 = ((unsigned)y0 * uW + (unsigned)x[0]) * uD + lane_d;
+            const unsigned stride = (unsigned)((W + rx) * (int)uD);
+            for_seq<SEG>([&](auto I) {
+                constexpr int rd = decltype(I)::value, ru = SEG - 1 - rd;
+                down_row(rd, cur.c[rd]);
+                up_row(cur.c[ru], Up[ru]);
+                if constexpr (rd >= SEG / 2) {
+                    unsigned e[NW];
+#pragma unroll
+                    for (int w = 0; w < NW; w++) e[w] = Dn[rd][w] + Up[rd][w];   // <= 2 * P2 <= 254 per byte
+                    bstore<NW>(rE, off0 + (unsigned)rd * stride, e);
+#pragma unroll
+                    for (int w = 0; w < NW; w++) e[w] = Dn[ru][w] + Up[ru][w];
+                    bstore<NW>(rE, off0 + (unsigned)ru * stride, e);
+                }
+            });
+        } else {
+            for_seq<SEG>([&](auto R) {
+                constexpr int r = decltype(R)::value;
+                if (r < nr) {
+                    reset_if(x[r] == xdn, Ad, md);
+                    down_row(r, cur.c[r]);
+                }
+            });
+            // ---- the up recurrence, backward over the same cost registers
+            for_seq<SEG>([&](auto Q) {
+                constexpr int r = SEG - 1 - decltype(Q)::value;
+                if (r < nr) {
+                    reset_if(x[r] == xup, Au, mu);
+                    unsigned e[NW];
+                    up_row(cur.c[r], e);
+#pragma unroll
+                    for (int w = 0; w < NW; w++) e[w] += Dn[r][w];       // <= 2 * P2 <= 254 per byte
+                    bstore<NW>(rE, ((unsigned)(y0 + r) * uW + (unsigned)x[r]) * uD + lane_d, e);
+                }
+            });
+        }
+        if (s > 0) cur = nxt;
+    }
 }
 
 }  // namespace sgm

@@ -36,6 +36,9 @@
 //      tune::kTileDiagDown / kTileDiagUp = 1, also recomputes a diagonal pair
 //      per tile from extra row-checkpoint planes; both constants are 0 in the
 //      product.)
+//      The pair route (sgm_paths_kernel<DPL, true>) is mode
+//      2 with the four diagonals as pair lines: two u8 pair-sum volumes
+//      [2][H][W][D] instead of four L_r volumes.
 //   (Mode 1, the round-2 route of DESIGN.md §4.6 -- six volumes, horizontal
 //   checkpoints only, finished by wta_h.hip -- was removed in ABI v5.)
 #include "sgm_common.h"
@@ -49,7 +52,11 @@ using namespace sgm;
 constexpr int PATH_BLOCK = 256;
 constexpr int LINES_PER_BLOCK = PATH_BLOCK / 16;
 
-template <int DPL>
+// PAIR (the pair route; one frame, tile pipeline only): the
+// four diagonals run as 2 * blk_w blocks of pair lines (sgm_common.h
+// pair_line) that write two pair-sum volumes, L8 = [2][H][W][D] (pairs 4+5,
+// 6+7), through two wave-private row-checkpoint planes after the vertical ones.
+template <int DPL, bool PAIR>
 __global__ __launch_bounds__(PATH_BLOCK) void sgm_paths_kernel(const uint8_t* __restrict__ C,
                                                                uint8_t* __restrict__ L8,
                                                                uint8_t* __restrict__ CK,
@@ -59,7 +66,31 @@ __global__ __launch_bounds__(PATH_BLOCK) void sgm_paths_kernel(const uint8_t* __
     // block ids -- every frame's of a batch before any vertical / diagonal
     // block -- and issue priority so they are never the tail.
     int b = blockIdx.x, r, lb, f;
-    if (b < 2 * g.blk_h * g.npair) {
+    if constexpr (PAIR) {
+        // The pair blocks are the launch's longest chains (H steps down, then
+        // H double steps back): they are dispatched first, with the highest
+        // issue priority; then the horizontal lines, then the vertical ones.
+        // Step-0 ablation at 1080p D=128, double-step blocks
+        // band-major / first in their band / all first: sgm_paths 0.609 /
+        // 0.527 / 0.477 ms against 0.515 for the four-volume kernel.
+        f = 0;
+        const int npb = 2 * g.blk_w;
+        if (b < npb) {
+            r = 4 + 2 * (b & 1);
+            lb = b >> 1;
+            // (priority 3 / 2: sgm_paths 0.521 / 0.531 ms, frame 0.823 / 0.837 ms)
+            __builtin_amdgcn_s_setprio(3);
+        } else if (b < npb + 2 * g.blk_h) {
+            b -= npb;
+            r = b / g.blk_h;
+            lb = b - r * g.blk_h;
+            __builtin_amdgcn_s_setprio(1);
+        } else {
+            b -= npb + 2 * g.blk_h;
+            r = 2 + (b & 1);
+            lb = b >> 1;
+        }
+    } else if (b < 2 * g.blk_h * g.npair) {
         f = b / (2 * g.blk_h);
         b -= f * 2 * g.blk_h;
         r = b / g.blk_h;
@@ -97,7 +128,20 @@ __global__ __launch_bounds__(PATH_BLOCK) void sgm_paths_kernel(const uint8_t* __
     // the tile pipeline's checkpoint segment (§4.9), rows and columns
     constexpr int SL = DPL <= 8 ? tune::kWtahvTileLog2 : tune::kWtahvTileLog2Wide;
     constexpr bool DOWN = diag_ckpt_down(DPL), UP = diag_ckpt_up(DPL);
-    if (r >= 4 && g.ckpt && (ry > 0 ? DOWN : UP)) {
+    if constexpr (PAIR) {
+        if (r >= 4) {
+            const int pr = r == 4 ? 0 : 1;                // pair 4+5, pair 6+7
+            const rsrc_t rCK = make_rsrc(CKV + (size_t)(2 + pr) * g.ckvvol, g.ckvvol);
+            const rsrc_t rE = make_rsrc(L8 + (size_t)pr * g.vol, g.vol);
+            pair_line<DPL, pf_v<DPL>(), SL>(rC, rE, g, rx, line, k, rCK);
+        } else if (r >= 2) {
+            const rsrc_t rCK = make_rsrc(CKV + (size_t)(r - 2) * g.ckvvol, g.ckvvol);
+            path_line<DPL, false, pf_v<DPL>(), 2, SL>(rC, rC, g, rx, ry, line, k, rCK);
+        } else {
+            const rsrc_t rCK = make_rsrc(CK + (size_t)r * g.ckvol, g.ckvol);
+            path_line<DPL, false, pf_h<DPL>(), 1, SL>(rC, rC, g, rx, ry, line, k, rCK);
+        }
+    } else if (r >= 4 && g.ckpt && (ry > 0 ? DOWN : UP)) {
         // tile pipeline, diagonals recomputed per tile: row
         // checkpoints only, in the vertical checkpoint block after the two
         // vertical planes: the down pair (4, 6), then the up pair (5, 7)
@@ -128,6 +172,21 @@ __global__ __launch_bounds__(PATH_BLOCK) void sgm_paths_kernel(const uint8_t* __
     }
 }
 
+// (a pair instance exists only for the D classes whose pair route is enabled)
+template <int DPL, bool EN>
+void paths_launch(bool pair, dim3 grid, hipStream_t s, hipEvent_t start, hipEvent_t stop,
+                  const uint8_t* C, uint8_t* L8, uint8_t* CK, uint8_t* CKV, const PathGeom& g) {
+    if constexpr (EN) {
+        if (pair) {
+            hipExtLaunchKernelGGL((sgm_paths_kernel<DPL, true>), grid, dim3(PATH_BLOCK), 0, s, start,
+                                  stop, 0, C, L8, CK, CKV, g);
+            return;
+        }
+    }
+    hipExtLaunchKernelGGL((sgm_paths_kernel<DPL, false>), grid, dim3(PATH_BLOCK), 0, s, start, stop,
+                          0, C, L8, CK, CKV, g);
+}
+
 }  // namespace
 
 bool paths_supported(int D) { return D == 64 || D == 128 || D == 192 || D == 256; }
@@ -148,8 +207,13 @@ TileGeom tile_geom(int W, int H, int D) {
     return t;
 }
 
+bool diag_pair_enabled(int D) {
+    return (D == 64 && tune::kDiagPair4) || (D == 128 && tune::kDiagPair8) ||
+           (D == 192 && tune::kDiagPair12) || (D == 256 && tune::kDiagPair16);
+}
+
 hipError_t launch_paths(Ctx& c, const uint8_t* C, int W, int H, int D, int P1, int P2,
-                        uint8_t* L8, uint8_t* CK, uint8_t* CKV, int npair) {
+                        uint8_t* L8, uint8_t* CK, uint8_t* CKV, int npair, bool pair, int dreal) {
     DispatchTimer t(c, "sgm_paths");
     PathGeom g;
     g.W = W; g.H = H; g.D = D; g.P1 = P1; g.P2 = P2;
@@ -171,19 +235,22 @@ hipError_t launch_paths(Ctx& c, const uint8_t* C, int W, int H, int D, int P1, i
     g.lstr = (size_t)tg.nvol * g.vol;
     g.ckstr = tg.hck_bytes;
     g.ckvstr = tg.vck_bytes + tg.dck_bytes;
-    dim3 grid((unsigned)((2 * g.blk_h + 6 * g.blk_w) * npair));
-#define SVA_PATHS_LAUNCH(DPL_)                                                               \
-    hipExtLaunchKernelGGL(sgm_paths_kernel<DPL_>, grid, dim3(PATH_BLOCK), 0, c.stream, t.start, \
-                          t.stop, 0, C, L8, CK, CKV, g);                                    \
-    t.used = true
+    // the pair route: one frame of the tile pipeline, u8 pair sums (2 * P2 <= 255),
+    // its two diagonal planes of CKV (pair_layout) taken by the caller
+    if (pair && (!CK || npair != 1 || 2 * P2 > 255 || !diag_pair_enabled(D) ||
+                 tile_geom(W, H, D).nvol != 4))
+        return hipErrorInvalidValue;
+    g.pair = pair ? 1 : 0;
+    g.dreal = dreal > 0 && dreal < D ? dreal : D;
+    dim3 grid((unsigned)((2 * g.blk_h + (pair ? 4 : 6) * g.blk_w) * npair));
+    t.used = true;
     switch (D) {
-        case 64: SVA_PATHS_LAUNCH(4); break;
-        case 128: SVA_PATHS_LAUNCH(8); break;
-        case 192: SVA_PATHS_LAUNCH(12); break;
-        case 256: SVA_PATHS_LAUNCH(16); break;
-        default: return hipErrorInvalidValue;
+        case 64: paths_launch<4, tune::kDiagPair4 != 0>(pair, grid, c.stream, t.start, t.stop, C, L8, CK, CKV, g); break;
+        case 128: paths_launch<8, tune::kDiagPair8 != 0>(pair, grid, c.stream, t.start, t.stop, C, L8, CK, CKV, g); break;
+        case 192: paths_launch<12, tune::kDiagPair12 != 0>(pair, grid, c.stream, t.start, t.stop, C, L8, CK, CKV, g); break;
+        case 256: paths_launch<16, tune::kDiagPair16 != 0>(pair, grid, c.stream, t.start, t.stop, C, L8, CK, CKV, g); break;
+        default: t.used = false; return hipErrorInvalidValue;
     }
-#undef SVA_PATHS_LAUNCH
     return hipGetLastError();
 }
 

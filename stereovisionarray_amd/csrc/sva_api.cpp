@@ -173,19 +173,34 @@ int check_sgm(Ctx* c, const sva_sgm_params* p, int W, int H, bool native = false
 // picks d*.  Dp is the native volume width, p->D <= Dp the caller's
 // disparities (§4.7).  (The round-2 route of §4.6 -- six volumes, finished
 // by wta_h -- was slower at every frame size measured and left in ABI v5.)
+// Checkpoint bytes of the pair route: the horizontal and vertical planes plus
+// one row-checkpoint plane per diagonal pair.
+size_t pair_ckpt_bytes(const TileGeom& tg) { return tg.hck_bytes + tg.vck_bytes + tg.vck_bytes; }
+
 int paths_wta(Ctx* c, const uint8_t* C, int W, int H, const sva_sgm_params* p, int Dp,
               uint16_t* disp, float* sub) {
     if (!wta_hv_supported(Dp)) return fail(c, SVA_ERR_UNSUPPORTED, "no tile pipeline for this D");
     const size_t nv = (size_t)W * H * (size_t)Dp;
     const TileGeom tg = tile_geom(W, H, Dp);
-    SVA_HIP(c, c->paths.ensure(nv * tg.nvol), "path workspace");
-    SVA_HIP(c, c->ckpt.ensure(tg.hck_bytes + tg.vck_bytes + tg.dck_bytes), "checkpoint workspace");
+    // The pair route where this D has it and the pair sums
+    // fit a u8: two pair-sum volumes and two more row-checkpoint planes
+    // (pair_ckpt_bytes) instead of four volumes, for frames large enough that
+    // the pair waves' chain is not the bound (tune::kDiagPairMinPixels).  Else
+    // today's four volumes.
+    const long long minpx = c->dbg_pair_min_pixels >= 0 ? (long long)c->dbg_pair_min_pixels
+                                                        : tune::kDiagPairMinPixels;
+    const bool pair = tg.nvol == 4 && diag_pair_ok(Dp, p->P2) && (long long)W * H >= minpx;
+    SVA_HIP(c, c->paths.ensure(nv * (pair ? 2 : tg.nvol)), "path workspace");
+    SVA_HIP(c, c->ckpt.ensure(pair ? pair_ckpt_bytes(tg) : tg.hck_bytes + tg.vck_bytes + tg.dck_bytes),
+            "checkpoint workspace");
     uint8_t* L4 = (uint8_t*)c->paths.ptr;
     uint8_t* CK = (uint8_t*)c->ckpt.ptr;
     uint8_t* CKV = CK + tg.hck_bytes;
-    SVA_HIP(c, launch_paths(*c, C, W, H, Dp, p->P1, p->P2, L4, CK, CKV), "paths launch");
-    SVA_HIP(c, launch_wta_hv(*c, C, L4, CK, CKV, W, H, Dp, p->P1, p->P2, p->dmin, disp, sub, p->D),
+    SVA_HIP(c, launch_paths(*c, C, W, H, Dp, p->P1, p->P2, L4, CK, CKV, 1, pair, p->D), "paths launch");
+    SVA_HIP(c, launch_wta_hv(*c, C, L4, CK, CKV, W, H, Dp, p->P1, p->P2, p->dmin, disp, sub, p->D, 1,
+                             pair),
             "wta launch");
+    c->last_diag_route = pair ? 1 : 0;
     return SVA_OK;
 }
 
@@ -622,7 +637,11 @@ int time_stage_set(Ctx* c, int W, int H, int D, int64_t* ns) {
     float best = 0.f;
     for (int r = 0; r < 4 && e == hipSuccess; r++) {
         e = hipEventRecord(a, c->stream);
-        if (e == hipSuccess) e = launch_paths(*c, C, W, H, D, 10, 120, L4, CK, CK + tg.hck_bytes);
+        // (the route a frame with the default penalties takes)
+        if (e == hipSuccess)
+            e = launch_paths(*c, C, W, H, D, 10, 120, L4, CK, CK + tg.hck_bytes, 1,
+                             tg.nvol == 4 && diag_pair_ok(D, 120) &&
+                                 (long long)W * H >= tune::kDiagPairMinPixels);
         if (e == hipSuccess) e = hipEventRecord(b, c->stream);
         if (e == hipSuccess) e = hipEventSynchronize(b);
         float ms = 0.f;
@@ -716,7 +735,11 @@ int sva_reserve(void* ctx, int W, int H, int D) {
     SVA_HIP(c, c->cost.ensure(nv), "reserve");
     // the frame route's path volumes: the 4 diagonal directions (tile pipeline)
     const TileGeom tg = tile_geom(W, H, D);
-    const size_t ckb = tg.hck_bytes + tg.vck_bytes + tg.dck_bytes;
+    // (the larger of the two diagonal routes' layouts: four volumes, and the
+    // pair route's two more row-checkpoint planes)
+    const size_t ckb = tg.nvol == 4 && diag_pair_enabled(D)
+                           ? pair_ckpt_bytes(tg)
+                           : tg.hck_bytes + tg.vck_bytes + tg.dck_bytes;
     SVA_HIP(c, c->paths.ensure(nv * tg.nvol), "reserve");
     SVA_HIP(c, c->ckpt.ensure(ckb), "reserve");
     // (once per allocation: a repeated reserve of a size the buffers already
@@ -774,6 +797,10 @@ int sva_set_debug(void* ctx, int key, int64_t value) {
             if (value < 0 || value > 8) return fail(c, SVA_ERR_INVALID_ARG, "placement trials must be 0..8");
             c->placement_trials = (int)value;
             return SVA_OK;
+        case SVA_DEBUG_DIAG_PAIR_MIN_PIXELS:
+            if (value < -1) return fail(c, SVA_ERR_INVALID_ARG, "pair route threshold must be >= -1");
+            c->dbg_pair_min_pixels = value;
+            return SVA_OK;
         default:
             return fail(c, SVA_ERR_INVALID_ARG, "unknown or read-only debug key");
     }
@@ -789,6 +816,10 @@ int sva_get_debug(void* ctx, int key, int64_t* value) {
         case SVA_DEBUG_PLACEMENT_TRIALS: *value = c->placement_trials; return SVA_OK;
         case SVA_DEBUG_PLACEMENT_NS: *value = c->placement_ns; return SVA_OK;
         case SVA_DEBUG_PLACEMENT_WORST_NS: *value = c->placement_worst_ns; return SVA_OK;
+        case SVA_DEBUG_DIAG_ROUTE: *value = c->last_diag_route; return SVA_OK;
+        case SVA_DEBUG_DIAG_PAIR_MIN_PIXELS:
+            *value = c->dbg_pair_min_pixels >= 0 ? c->dbg_pair_min_pixels : (int64_t)tune::kDiagPairMinPixels;
+            return SVA_OK;
         case SVA_DEBUG_SIDE_IDLE: {
             bool idle = true;
             for (hipStream_t s : c->side) {

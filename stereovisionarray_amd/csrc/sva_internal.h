@@ -86,6 +86,12 @@ struct Ctx {
     // failure (1-based frame of the next call, 0 = off)
     int dbg_plane_split = 0;
     int dbg_fail_cost_at = 0;
+    // SVA_DEBUG_DIAG_ROUTE: the diagonal route of the last frame's aggregation
+    // (0 = four volumes, 1 = pair volumes)
+    int last_diag_route = 0;
+    // SVA_DEBUG_DIAG_PAIR_MIN_PIXELS: smallest W * H on the pair route
+    // (-1 = tune::kDiagPairMinPixels)
+    int64_t dbg_pair_min_pixels = -1;
     // sva_reserve's placement check: sets to time (0 = tune::kPlacementTrials),
     // and the kept / slowest set's path-kernel time of the last check (ns)
     int placement_trials = 0;
@@ -173,9 +179,17 @@ hipError_t launch_cost(Ctx& c, const uint64_t* cl, const uint64_t* cr, int W, in
 // vck_bytes + dck_bytes (tile_geom below).  npair > 1 (tile pipeline only): a
 // batch of frames in one launch, each buffer holding npair such planes back
 // to back.
+// pair (one frame of the tile pipeline, diag_pair_ok): the pair route of
+// DESIGN.md §4.15, L8 = [2][H][W][D] pair sums (4+5, 6+7) and CKV = the two
+// vertical planes plus two wave-private row-checkpoint planes (pair_layout);
+// dreal as for launch_wta_hv.
 hipError_t launch_paths(Ctx& c, const uint8_t* C, int W, int H, int D, int P1, int P2,
                         uint8_t* L8, uint8_t* CK = nullptr, uint8_t* CKV = nullptr,
-                        int npair = 1);
+                        int npair = 1, bool pair = false, int dreal = 0);
+// The pair route: compiled in for this native D (tune::kDiagPair*), and usable
+// for a frame with these penalties (the u8 pair sum holds 2 * P2).
+bool diag_pair_enabled(int D);
+inline bool diag_pair_ok(int D, int P2) { return diag_pair_enabled(D) && 2 * P2 <= 255; }
 // Tile pipeline geometry: tiles of 16 columns x seg rows (seg = 2^seg_log2),
 // checkpoints every seg columns (horizontal lines) and every seg rows
 // (vertical lines).
@@ -215,9 +229,11 @@ inline int padded_D(int D) {
 // four diagonal volumes L4, WTA.  dreal < D: a padded frame (DESIGN.md
 // §4.7), WTA over d < dreal only.
 bool wta_hv_supported(int D);
+// pair: L4 holds the pair route's two pair-sum volumes (one frame).
 hipError_t launch_wta_hv(Ctx& c, const uint8_t* C, const uint8_t* L4, const uint8_t* CK,
                          const uint8_t* CKV, int W, int H, int D, int P1, int P2, int dmin,
-                         uint16_t* disp, float* sub, int dreal = 0, int npair = 1);
+                         uint16_t* disp, float* sub, int dreal = 0, int npair = 1,
+                         bool pair = false);
 // wta.hip
 hipError_t launch_sum(Ctx& c, const uint8_t* L8, int W, int H, int D, uint16_t* S);
 hipError_t launch_wta_from_sum(Ctx& c, const uint16_t* S, int W, int H, int D, int dmin,

@@ -100,6 +100,23 @@ constexpr int kStateMinTree = 1;
 // 3.772 / 3.863 / 3.944, 4K D=256 7.570 / 7.394 / 7.697.
 constexpr int kTileDiagDown = 0;
 constexpr int kTileDiagUp = 0;
+// The pair route: a frame (not a batch) whose 2 * P2 fits a
+// u8 has each diagonal and its opposite walked by one wave of sgm_paths,
+// which writes the two pair-sum volumes E = (L_a - C) + (L_b - C) instead of
+// four L_r volumes; wta_hv reads two volumes and adds 4C.  Per native D
+// (DPL = D / 16); measurements in §4.15.  Only the enabled classes compile a
+// pair instance of the two kernels.
+constexpr int kDiagPair4 = 0, kDiagPair8 = 1, kDiagPair12 = 0, kDiagPair16 = 0;
+// Smallest frame (W * H) that takes the pair route.  A pair wave is a chain of
+// H steps down and H double steps back, against H steps of a diagonal line
+// before, so small frames are bound by that chain, not by their bytes.  Frame
+// ms at D=128, four volumes / pair (in-process A/B, §4.15): 640x480 0.181 /
+// 0.257, 960x540 0.257 / 0.312, 1280x720 0.432 / 0.435, 1080p 0.854 / 0.823,
+// 2560x1440 1.503 / 1.453, 4K 3.42 / 3.11.
+constexpr long long kDiagPairMinPixels = 1600000;
+// prefetch depth (pixels) of wta_hv's two pair-volume loads: wta_hv ms at 1080p
+// D=128 for 2 / 3 / 4: 0.1862 / 0.1837 / 0.1815
+constexpr int kWtahvPfVolPair = 4;
 // The strip route: at D <= 128 sgm_paths writes
 // row checkpoints for all four diagonals and no volume at all, and
 // wta_strip_kernel recomputes all eight directions per tile, walking strips

@@ -47,11 +47,14 @@ struct WtaHvGeom {
 };
 
 // Prefetch depth (pixels) of the diagonal volumes in the last pass.
-template <int DPL> constexpr int pf_vol() {
-    return DPL >= 16 ? tune::kWtahvPfVol16 : DPL <= 4 ? tune::kWtahvPfVol4 : tune::kWtahvPfVol;
+template <int DPL, bool PAIR> constexpr int pf_vol() {
+    return PAIR ? tune::kWtahvPfVolPair : DPL >= 16 ? tune::kWtahvPfVol16 : DPL <= 4 ? tune::kWtahvPfVol4 : tune::kWtahvPfVol;
 }
 
-template <int DPL, int TYL, bool PAD>
+// PAIR (the pair route): L4 holds two pair-sum volumes
+// E = (L_a - C) + (L_b - C) for the diagonal pairs 4+5 and 6+7 instead of four
+// L_r volumes; the missing 4C enters V in phase V.
+template <int DPL, int TYL, bool PAD, bool PAIR>
 __global__ __launch_bounds__(TB, tune::kWtahvMinWaves) void wta_hv_kernel(const uint8_t* __restrict__ C,
                                                     const uint8_t* __restrict__ L4,
                                                     const uint8_t* __restrict__ CK,
@@ -60,7 +63,7 @@ __global__ __launch_bounds__(TB, tune::kWtahvMinWaves) void wta_hv_kernel(const 
                                                     float* __restrict__ sub) {
     constexpr int NW = DPL / 4, NP = DPL / 2;
     constexpr int TY = 1 << TYL;        // tile rows = checkpoint segment (rows and columns)
-    constexpr int kPfVol = pf_vol<DPL>();
+    constexpr int kPfVol = pf_vol<DPL, PAIR>();
     // bit 0: phase V keeps L_2 as u16, bit 1: phase H keeps L_0 as u16
     constexpr int KEEPM = DPL <= 8 ? tune::kWtahvKeepU16 : tune::kWtahvKeepU16Wide;
     constexpr bool KEEP16 = (KEEPM & 1) != 0, KEEP16H = (KEEPM & 2) != 0;
@@ -78,7 +81,8 @@ __global__ __launch_bounds__(TB, tune::kWtahvMinWaves) void wta_hv_kernel(const 
     // diagonals recomputed per tile (§4.11): the down pair (4, 6), the up pair (5, 7)
     constexpr bool DOWN = diag_ckpt_down(DPL), UP = diag_ckpt_up(DPL);
     constexpr int ND = (DOWN ? 2 : 0) + (UP ? 2 : 0);   // recomputed diagonals
-    constexpr int NV = 4 - ND;                          // diagonal volumes read
+    constexpr int NV = PAIR ? 2 : 4 - ND;               // diagonal volumes read
+    static_assert(!PAIR || ND == 0, "the pair route replaces all four diagonal volumes");
     C += (size_t)f * g.vol;
     L4 += (size_t)f * NV * g.vol;
     CK += (size_t)f * 2 * g.hck;
@@ -167,7 +171,7 @@ __global__ __launch_bounds__(TB, tune::kWtahvMinWaves) void wta_hv_kernel(const 
             for (int q = 0; q < NK; q++) dst[q] = KEEP16 ? A[q] : ow[q];
         };
         auto put_v = [&](int r, const unsigned (&ld)[NK], const unsigned (&Au)[NP],
-                         const unsigned (&lu)[NW]) {
+                         const unsigned (&lu)[NW], const unsigned (&cw)[NW]) {
             unsigned V[NP];
             if constexpr (KEEP16) {
 #pragma unroll
@@ -175,6 +179,13 @@ __global__ __launch_bounds__(TB, tune::kWtahvMinWaves) void wta_hv_kernel(const 
             } else {
                 words_to_pairs<DPL>(ld, V);
                 unpack_add<NW>(lu, V);
+            }
+            if constexpr (PAIR) {
+                // + 4C, what the two pair sums leave out (<= 1020 per half: no carry)
+                unsigned c4[NP];
+                words_to_pairs<DPL>(cw, c4);
+#pragma unroll
+                for (int p = 0; p < NP; p++) V[p] += c4[p] << 2;
             }
             unsigned* dst = &vsum[(r * TW + slot) * 16 * NP];
 #pragma unroll
@@ -194,10 +205,10 @@ __global__ __launch_bounds__(TB, tune::kWtahvMinWaves) void wta_hv_kernel(const 
                 if (r < ny) {
                     if constexpr (KEEP16) {
                         const unsigned none[NW] = {};
-                        put_v(r, LD[r], LU[r], none);
+                        put_v(r, LD[r], LU[r], none, cv[r].w);
                     } else {
                         unsigned V[NP] = {};
-                        put_v(r, LD[r], V, LU[r]);
+                        put_v(r, LD[r], V, LU[r], cv[r].w);
                     }
                 }
             });
@@ -222,7 +233,7 @@ __global__ __launch_bounds__(TB, tune::kWtahvMinWaves) void wta_hv_kernel(const 
                     unsigned lu[NW];
                     if constexpr (UNPACK1) sgm_step_c<DPL, PIN>(cvp[UNPACK1 ? r : 0], Ab, mb, lu, P1, P2, eb);
                     else sgm_step<DPL, PIN>(cv[r].w, Ab, mb, lu, P1, P2, eb);
-                    put_v(r, LD[r], Ab, lu);
+                    put_v(r, LD[r], Ab, lu, cv[r].w);
                 }
             });
         }
@@ -482,13 +493,27 @@ __global__ __launch_bounds__(TB, tune::kWtahvMinWaves) void wta_hv_kernel(const 
     }
 }
 
+// (PAIR instances exist only for the D classes whose pair route is enabled;
+// launch_wta_hv has refused pair = true for the others)
+template <int DPL, int TYL, bool PAIR>
+void wtahv_launch(bool pad, dim3 grid, hipStream_t s, hipEvent_t start, hipEvent_t stop,
+                  const uint8_t* C, const uint8_t* L4, const uint8_t* CK, const uint8_t* CKV,
+                  const WtaHvGeom& g, uint16_t* disp, float* sub) {
+    if (pad)
+        hipExtLaunchKernelGGL((wta_hv_kernel<DPL, TYL, true, PAIR>), grid, dim3(TB), 0, s, start,
+                              stop, 0, C, L4, CK, CKV, g, disp, sub);
+    else
+        hipExtLaunchKernelGGL((wta_hv_kernel<DPL, TYL, false, PAIR>), grid, dim3(TB), 0, s, start,
+                              stop, 0, C, L4, CK, CKV, g, disp, sub);
+}
+
 }  // namespace
 
 bool wta_hv_supported(int D) { return D == 64 || D == 128 || D == 192 || D == 256; }
 
 hipError_t launch_wta_hv(Ctx& c, const uint8_t* C, const uint8_t* L4, const uint8_t* CK,
                          const uint8_t* CKV, int W, int H, int D, int P1, int P2, int dmin,
-                         uint16_t* disp, float* sub, int dreal, int npair) {
+                         uint16_t* disp, float* sub, int dreal, int npair, bool pair) {
     // D <= 128 on the strip route: all eight directions recomputed per tile
     // from checkpoints, no diagonal volume (wta_strip.hip)
     if (tune::kStripRoute != 0 && wta_strip_supported(D))
@@ -512,22 +537,28 @@ hipError_t launch_wta_hv(Ctx& c, const uint8_t* C, const uint8_t* L4, const uint
     g.tiles = g.ntx * g.nty;
     const dim3 grid((unsigned)(g.tiles * npair));
 #define SVA_WTAHV(DPL_, TYL_)                                                                 \
-    if (pad)                                                                                  \
-        hipExtLaunchKernelGGL((wta_hv_kernel<DPL_, TYL_, true>), grid, dim3(TB), 0, c.stream, \
-                              t.start, t.stop, 0, C, L4, CK, CKV, g, disp, sub);              \
-    else                                                                                      \
-        hipExtLaunchKernelGGL((wta_hv_kernel<DPL_, TYL_, false>), grid, dim3(TB), 0,          \
-                              c.stream, t.start, t.stop, 0, C, L4, CK, CKV, g, disp, sub);    \
+    wtahv_launch<DPL_, TYL_, false>(pad, grid, c.stream, t.start, t.stop, C, L4, CK, CKV, g,  \
+                                    disp, sub);                                               \
     t.used = true
+#define SVA_WTAHV_P(DPL_, TYL_, EN_)                                                          \
+    if (pair) {                                                                               \
+        wtahv_launch<DPL_, TYL_, (EN_) != 0>(pad, grid, c.stream, t.start, t.stop, C, L4, CK, \
+                                             CKV, g, disp, sub);                              \
+        t.used = true;                                                                        \
+    } else {                                                                                  \
+        SVA_WTAHV(DPL_, TYL_);                                                                \
+    }
     constexpr int TYL = tune::kWtahvTileLog2, TYLW = tune::kWtahvTileLog2Wide;
     if (tg.seg_log2 != (D <= 128 ? TYL : TYLW)) return hipErrorInvalidValue;
+    if (pair && (npair != 1 || !diag_pair_ok(D, P2) || tg.nvol != 4)) return hipErrorInvalidValue;
     switch (D) {
-        case 64: SVA_WTAHV(4, TYL); break;
-        case 128: SVA_WTAHV(8, TYL); break;
-        case 192: SVA_WTAHV(12, TYLW); break;
-        case 256: SVA_WTAHV(16, TYLW); break;
+        case 64: SVA_WTAHV_P(4, TYL, tune::kDiagPair4); break;
+        case 128: SVA_WTAHV_P(8, TYL, tune::kDiagPair8); break;
+        case 192: SVA_WTAHV_P(12, TYLW, tune::kDiagPair12); break;
+        case 256: SVA_WTAHV_P(16, TYLW, tune::kDiagPair16); break;
         default: return hipErrorInvalidValue;
     }
+#undef SVA_WTAHV_P
 #undef SVA_WTAHV
     return hipGetLastError();
 }
