@@ -623,32 +623,143 @@ __device__ __forceinline__ void load_state(rsrc_t r, unsigned off, unsigned (&A)
 // L_r - C = u - m lies in [0, P2] (sgm_step_c), so with P2 <= 127 the pair sum
 //   E(p, d) = (L_dn - C) + (L_up - C) <= 254
 // fits the u8 volume word that one of the two directions had before, and the
-// final kernel adds the 2C back.  The wave
-//   1. walks the line down like path_line<.., CKPT = 3, SL>: no volume, the
-//      state at the last row of every 2^SL-row segment to the row-checkpoint
-//      plane rCK (at the pixel's column);
-//   2. comes back up segment by segment: the segment's rows of cost loaded
-//      once; the down recurrence re-run forward from the checkpoint above the
-//      segment (zero state at the top), its L - C rows kept u8-packed; the up
-//      recurrence backward over the same cost registers; E stored per pixel.
-// The checkpoints are wave-private: a wave reads back only what it stored
-// itself, after its stores have retired (vmcnt 0) and past the vector L1.
-// The next segment's cost rows and checkpoint are loaded while this one
-// computes.
+// final kernel adds the 2C back.
+//
+// The two recurrences MEET IN THE MIDDLE.  A line is worked
+// by two 16-lane rows of one wave, role T (`role` 0) and role B (1), which
+// execute one instruction stream on per-lane addresses; M is the split row, a
+// multiple of the segment SEG = 2^SL with about half the rows on either side.
+//   1. T runs the down recurrence over rows 0 .. M-1 and stores the state at
+//      the last row of every segment above the split's to the row-checkpoint
+//      plane rCK (at the pixel's column, plane row = segment); B runs the up
+//      recurrence over rows H-1 .. M and stores the state at the first row of
+//      every segment below the split's (plane row = segment: the two sets of
+//      plane rows are disjoint).  The role with fewer rows first takes `lead`
+//      steps of cost 0 from zero state, which stays zero (u = min(P1, 0, P2)),
+//      so both roles take the same number of steps.  Both states at the split
+//      stay in registers.
+//   2. B continues upward through the segments above M, T downward through
+//      the ones below: the segment's rows of cost loaded once; the down
+//      recurrence forward over them (B: re-run from T's checkpoint above the
+//      segment, zero state at the top; T: from its live state), its L - C rows
+//      kept u8-packed; the up recurrence backward over the same cost registers
+//      (B: live state; T: from B's checkpoint below the segment, zero state at
+//      the bottom); E stored per pixel.
+// A line's chain is H/2 steps and then H/2 double steps, where one row walking
+// down and back had H and H.  The checkpoints are wave-private: both roles of
+// a line sit in one wave, which reads back only what it stored itself, after
+// its stores have retired (vmcnt 0) and past the vector L1.  The next
+// segment's cost rows and checkpoint are loaded while this one computes.
 template <int DPL, int PF, int SL>
 __device__ __forceinline__ void pair_line(rsrc_t rC, rsrc_t rE, const PathGeom& g, int rx, int line,
-                                          int k, rsrc_t rCK) {
+                                          int role, int k, rsrc_t rCK) {
     constexpr int NW = DPL / 4, NP = DPL / 2, SEG = 1 << SL;
-    path_line<DPL, true, PF, 3, SL>(rC, rC, g, rx, 1, line, k, rCK);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // own checkpoints retired before the loads below
-
+    static_assert(PF >= SEG, "the lead steps sit in the prefetch prologue");
     const int W = g.W, H = g.H;
     const unsigned uW = (unsigned)W, uD = (unsigned)g.D;
+    const unsigned WD = uW * uD;
     const unsigned P1 = (unsigned)g.P1, P2 = (unsigned)g.P2;
     const unsigned lane_d = (unsigned)(k * DPL);
-    const int jrow = (int)((threadIdx.x >> 4) & 3);               // row of the line in its wave
-    const int l0 = __builtin_amdgcn_readfirstlane(line - jrow);
     const int nseg = (H + SEG - 1) >> SL;
+    const int qs = nseg >> 1;                      // segments above the split
+    const int M = qs << SL;
+    const bool up = role != 0;
+    auto wrap = [&](int x) { return x >= W ? x - W : (x < 0 ? x + W : x); };
+    // the line's column in row y (any integer y)
+    auto col_of = [&](int y) {
+        const int x = (line + rx * y) % W;
+        return x < 0 ? x + W : x;
+    };
+
+    unsigned A1[NP], m1 = 0u;                      // the role's state at the split
+    {
+        // ---- phase 1: T rows 0 .. M-1 downward, B rows H-1 .. M upward ----
+        const int n1 = M > H - M ? M : H - M;      // steps, lead included
+        const int lead = n1 - (up ? H - M : M);
+        const int ry = up ? -1 : 1, rxl = up ? -rx : rx;
+        // the cursors start `lead` rows outside the image: those loads (out of
+        // range: 0, or in-range garbage where the offset wraps) are replaced by 0
+        const int yv = up ? H - 1 + lead : -lead;
+        const int xv = col_of(yv);
+        const unsigned stride = (unsigned)((ry * W + rxl) * g.D);
+        const unsigned wfix = rxl > 0 ? 0u - WD : WD;    // offset correction where x wraps
+        unsigned coff = (unsigned)(yv * W + xv) * uD + lane_d;
+        unsigned poff = coff;
+        // each lane's next wrap: after its step tw - 1, then every W steps
+        int twc = rxl > 0 ? W - xv : xv + 1, twp = twc;
+        // checkpoint rows as z = y (B) / y + 1 (T) relative to the first one:
+        // a hit where z0 -/+ step is a multiple of SEG in [0, zn).  zT + step
+        // and zB - step are wave-uniform, so the steps without a hit in either
+        // role pay two scalar tests.
+        const int zT = 1 - (n1 - M) - SEG, zB = H - 1 + (n1 - (H - M)) - (M + SEG);
+        const int z0 = up ? zB : zT;
+        const int zn = up ? H - (M + SEG) : M - 2 * SEG + 1;
+#pragma unroll
+        for (int j = 0; j < NP; j++) A1[j] = 0u;   // L(q) = 0, m = 0  =>  L = C
+        Edges e1;
+        Words<NW> ring[PF];
+#pragma unroll
+        for (int p = 0; p < PF; p++) {
+            ring[p] = bload<NW>(rC, poff);
+#pragma unroll
+            for (int w = 0; w < NW; w++) ring[p].w[w] = p < lead ? 0u : ring[p].w[w];
+            poff += stride;
+            if (p < PF - 1) {                      // the advance past pixel PF-1 is checked by step 0
+                const bool wr = p + 1 == twp;
+                poff = wr ? poff + wfix : poff;
+                twp = wr ? twp + W : twp;
+            }
+        }
+        auto step = [&](int p, bool refill, int ts) {
+            unsigned cw[NW];
+#pragma unroll
+            for (int w = 0; w < NW; w++) cw[w] = ring[p].w[w];
+            unsigned ow[NW];
+            sgm_step<DPL>(cw, A1, m1, ow, P1, P2, e1);
+            if (__builtin_expect((((zT + ts) & (SEG - 1)) == 0) | (((zB - ts) & (SEG - 1)) == 0), 0)) {
+                const int zc = up ? z0 - ts : z0 + ts;
+                if ((zc & (SEG - 1)) == 0 && zc >= 0 && zc < zn) {
+                    // the pixel's volume offset minus the rows the plane does not hold
+                    const int y = zc + (up ? M + SEG : SEG - 1);
+                    bstore<NW, tune::kCkptStoreAux>(rCK, coff - (unsigned)(y - (y >> SL)) * WD, ow);
+                }
+            }
+            coff += stride;
+            // One wave-uniform branch, taken only on the steps where a line of
+            // the wave wraps: the compute cursor restarts there (L = C), and
+            // the prefetch cursor's previous advance (past pixel ts + PF - 1)
+            // is corrected before its next load.
+            const bool cwr = ts + 1 == twc;
+            const bool pwr = refill && ts + PF == twp;
+            if (__builtin_expect(__builtin_amdgcn_ballot_w64(cwr || pwr) != 0, 0)) {
+                coff = cwr ? coff + wfix : coff;
+                twc = cwr ? twc + W : twc;
+#pragma unroll
+                for (int j = 0; j < NP; j++) A1[j] = cwr ? 0u : A1[j];
+                m1 = cwr ? 0u : m1;
+                poff = pwr ? poff + wfix : poff;
+                twp = pwr ? twp + W : twp;
+            }
+            if (refill) {
+                __builtin_amdgcn_sched_barrier(0);
+                ring[p] = bload<NW>(rC, poff);
+                poff += stride;                    // wrap corrected by the next step
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        };
+        int t = 0;
+        for (; t + PF <= n1; t += PF) {
+#pragma unroll
+            for (int p = 0; p < PF; p++) step(p, true, t + p);
+        }
+#pragma unroll
+        for (int p = 0; p < PF; p++)
+            if (t + p < n1) step(p, false, t + p);
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // own checkpoints retired before the loads below
+
+    // ---- phase 2: iteration i is segment qs - 1 - i for B, qs + i for T ----
+    const int nit = nseg - qs;                     // T's segments; B has qs <= nit
     // a step into this column comes from across the image edge: the recurrence restarts
     const int xdn = rx > 0 ? 0 : W - 1, xup = rx > 0 ? W - 1 : 0;
     unsigned padm[NP];
@@ -657,31 +768,32 @@ __device__ __forceinline__ void pair_line(rsrc_t rC, rsrc_t rE, const PathGeom& 
         const int dl = k * DPL + pair_d<DPL>(j, 0), dh = k * DPL + pair_d<DPL>(j, 1);
         padm[j] = (dl >= g.dreal ? 0x0000ffffu : 0u) | (dh >= g.dreal ? 0xffff0000u : 0u);
     }
-    auto wrap = [&](int x) { return x >= W ? x - W : (x < 0 ? x + W : x); };
-    // the line's column in the first row of segment s
-    auto seg_x = [&](int s) {
-        int xb = (l0 + rx * (s << SL)) % W;        // wave-uniform
-        xb = xb < 0 ? xb + W : xb;
-        int x = xb + jrow;                         // jrow <= 3: three folds cover W = 1
-        x = x >= W ? x - W : x;
-        x = x >= W ? x - W : x;
-        x = x >= W ? x - W : x;
-        return x;
+    // (B past its last segment, when nseg is odd: it re-reads segment 0, stores nothing)
+    auto seg_of = [&](int i) {
+        const int s = up ? qs - 1 - i : qs + i;
+        return s < 0 ? 0 : s;
     };
+    // the column moves by SEG * rx mod W from a segment to the next one down
+    int s8 = (SEG * rx) % W;
+    s8 = s8 < 0 ? s8 + W : s8;
+    const int ds8 = up ? -s8 : s8;
     struct SegLoads {
         Words<NW> c[SEG], ck;
     };
-    auto issue = [&](int s, SegLoads& b) {
-        int x = seg_x(s);
+    // x: the line's column in the first row of segment s
+    auto issue = [&](int s, int x, SegLoads& b) {
+        const int xa = wrap(x - rx);
         // rows past the image lie past the volume: the range check returns 0,
         // and nothing consumes them
-        if (s > 0)
-            b.ck = bload<NW, 16>(rCK, ((unsigned)(s - 1) * uW + (unsigned)wrap(x - rx)) * uD + lane_d);
 #pragma unroll
         for (int r = 0; r < SEG; r++) {
             b.c[r] = bload<NW>(rC, ((unsigned)((s << SL) + r) * uW + (unsigned)x) * uD + lane_d);
             x = wrap(x + rx);
         }
+        // B: T's state in the row above the segment; T: B's in the row below it
+        const bool has = up ? s > 0 : s + 1 < nseg;
+        const unsigned o = ((unsigned)(up ? s - 1 : s + 1) * uW + (unsigned)(up ? xa : x)) * uD + lane_d;
+        b.ck = bload<NW, 16>(rCK, has ? o : lane_d);
     };
     auto reset_if = [&](bool rs, unsigned (&A)[NP], unsigned& m) {
         // (wave-uniform branch: only the steps of a wrap pay the selects)
@@ -692,31 +804,49 @@ __device__ __forceinline__ void pair_line(rsrc_t rC, rsrc_t rE, const PathGeom& 
         }
     };
 
-    unsigned Au[NP], mu = 0u;
+    // the role's live recurrence: T's down state, B's up state; the other one
+    // is restored at every segment
+    unsigned Ad[NP], md = up ? 0u : m1, Au[NP], mu = up ? m1 : 0u;
 #pragma unroll
-    for (int j = 0; j < NP; j++) Au[j] = 0u;       // bottom row: L = C
-    Edges eu;
+    for (int j = 0; j < NP; j++) {
+        Ad[j] = up ? 0u : A1[j];
+        Au[j] = up ? A1[j] : 0u;
+    }
+    Edges ed, eu;
     SegLoads cur, nxt;
-    issue(nseg - 1, cur);
-    for (int s = nseg - 1; s >= 0; s--) {
+    int xs = col_of(seg_of(0) << SL), xn = xs;
+    issue(seg_of(0), xs, cur);
+    for (int i = 0; i < nit; i++) {
         __builtin_amdgcn_sched_barrier(0);
-        if (s > 0) issue(s - 1, nxt);
+        if (i + 1 < nit) {
+            xn = wrap(xs + ds8);
+            issue(seg_of(i + 1), xn, nxt);
+        }
         __builtin_amdgcn_sched_barrier(0);
+        const int s = seg_of(i);
+        const bool act = !up || i < qs;                   // B sits out T's extra segment
         const int y0 = s << SL;
         const int nr = H - y0 < SEG ? H - y0 : SEG;       // rows of the segment inside the image
         int x[SEG];
-        x[0] = seg_x(s);
+        x[0] = xs;
 #pragma unroll
         for (int r = 1; r < SEG; r++) x[r] = wrap(x[r - 1] + rx);
-        // ---- the down recurrence again, forward, from the state entering the segment
-        unsigned Ad[NP], md;
-        Edges ed;
-        if (s > 0) {
-            state_from_words<DPL, true>(cur.ck, Ad, md, padm);
-        } else {
+        // ---- the state entering the segment for the recurrence that is not
+        // live: B's down state from the checkpoint above (zero at the top),
+        // T's up state from the checkpoint below (zero at the bottom)
+        {
+            const bool has = up ? s > 0 : s + 1 < nseg;
+            unsigned Ak[NP], mk;
+            state_from_words<DPL, true>(cur.ck, Ak, mk, padm);
 #pragma unroll
-            for (int j = 0; j < NP; j++) Ad[j] = 0u;
-            md = 0u;
+            for (int j = 0; j < NP; j++) {
+                const unsigned a = has ? Ak[j] : 0u;
+                Ad[j] = up ? a : Ad[j];
+                Au[j] = up ? Au[j] : a;
+            }
+            mk = has ? mk : 0u;
+            md = up ? mk : md;
+            mu = up ? mu : mk;
         }
         unsigned Dn[SEG][NW];                             // L_dn - C per row, u8-packed
         auto down_row = [&](int r, const Words<NW>& c) {
@@ -739,10 +869,10 @@ __device__ __forceinline__ void pair_line(rsrc_t rC, rsrc_t rE, const PathGeom& 
         // but ~8 / W of them) runs as one straight block: step i of the down
         // recurrence beside step i of the up recurrence, two independent
         // dependency chains the scheduler interleaves, which halves the
-        // latency of the wave's return phase (it is the launch's longest
-        // chain).  A row's E is stored once both of its halves exist.
+        // latency of the wave's second phase.  A row's E is stored once both
+        // of its halves exist.
         const bool inner = rx > 0 ? x[0] >= 1 && x[0] + SEG <= W - 1 : x[0] - SEG >= 0 && x[0] <= W - 2;
-        if (__builtin_expect(nr == SEG && __builtin_amdgcn_ballot_w64(!inner) == 0, 1)) {
+        if (__builtin_expect(__builtin_amdgcn_ballot_w64(!inner || nr != SEG || !act) == 0, 1)) {
             unsigned Up[SEG][NW];
             const unsigned off0 = ((unsigned)y0 * uW + (unsigned)x[0]) * uD + lane_d;
             const unsigned stride = (unsigned)((W + rx) * (int)uD);
@@ -763,7 +893,7 @@ __device__ __forceinline__ void pair_line(rsrc_t rC, rsrc_t rE, const PathGeom& 
         } else {
             for_seq<SEG>([&](auto R) {
                 constexpr int r = decltype(R)::value;
-                if (r < nr) {
+                if (r < nr && act) {                      // (per 16-lane row)
                     reset_if(x[r] == xdn, Ad, md);
                     down_row(r, cur.c[r]);
                 }
@@ -771,7 +901,7 @@ __device__ __forceinline__ void pair_line(rsrc_t rC, rsrc_t rE, const PathGeom& 
             // ---- the up recurrence, backward over the same cost registers
             for_seq<SEG>([&](auto Q) {
                 constexpr int r = SEG - 1 - decltype(Q)::value;
-                if (r < nr) {
+                if (r < nr && act) {
                     reset_if(x[r] == xup, Au, mu);
                     unsigned e[NW];
                     up_row(cur.c[r], e);
@@ -781,7 +911,10 @@ __device__ __forceinline__ void pair_line(rsrc_t rC, rsrc_t rE, const PathGeom& 
                 }
             });
         }
-        if (s > 0) cur = nxt;
+        if (i + 1 < nit) {
+            cur = nxt;
+            xs = xn;
+        }
     }
 }
 

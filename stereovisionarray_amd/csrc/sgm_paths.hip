@@ -38,7 +38,8 @@
 //      product.)
 //      The pair route (sgm_paths_kernel<DPL, true>) is mode
 //      2 with the four diagonals as pair lines: two u8 pair-sum volumes
-//      [2][H][W][D] instead of four L_r volumes.
+//      [2][H][W][D] instead of four L_r volumes.  A pair line takes two DPP
+//      rows of a wave (§4.16), so a wave carries 2 and a workgroup 8 of them.
 //   (Mode 1, the round-2 route of DESIGN.md §4.6 -- six volumes, horizontal
 //   checkpoints only, finished by wta_h.hip -- was removed in ABI v5.)
 #include "sgm_common.h"
@@ -51,11 +52,13 @@ using namespace sgm;
 
 constexpr int PATH_BLOCK = 256;
 constexpr int LINES_PER_BLOCK = PATH_BLOCK / 16;
+constexpr int PAIR_LINES = LINES_PER_BLOCK / 2;   // a pair line is two rows: roles T and B
 
 // PAIR (the pair route; one frame, tile pipeline only): the
-// four diagonals run as 2 * blk_w blocks of pair lines (sgm_common.h
-// pair_line) that write two pair-sum volumes, L8 = [2][H][W][D] (pairs 4+5,
-// 6+7), through two wave-private row-checkpoint planes after the vertical ones.
+// four diagonals run as 4 * blk_w blocks of 8 pair lines (sgm_common.h
+// pair_line: two 16-lane rows per line, which meet in the middle, §4.16) that
+// write two pair-sum volumes, L8 = [2][H][W][D] (pairs 4+5, 6+7), through two
+// wave-private row-checkpoint planes after the vertical ones.
 template <int DPL, bool PAIR>
 __global__ __launch_bounds__(PATH_BLOCK) void sgm_paths_kernel(const uint8_t* __restrict__ C,
                                                                uint8_t* __restrict__ L8,
@@ -67,18 +70,24 @@ __global__ __launch_bounds__(PATH_BLOCK) void sgm_paths_kernel(const uint8_t* __
     // block -- and issue priority so they are never the tail.
     int b = blockIdx.x, r, lb, f;
     if constexpr (PAIR) {
-        // The pair blocks are the launch's longest chains (H steps down, then
-        // H double steps back): they are dispatched first, with the highest
-        // issue priority; then the horizontal lines, then the vertical ones.
-        // Step-0 ablation at 1080p D=128, double-step blocks
-        // band-major / first in their band / all first: sgm_paths 0.609 /
-        // 0.527 / 0.477 ms against 0.515 for the four-volume kernel.
+        // The pair blocks carry most of the launch's instructions (a role is
+        // H/2 steps, then H/2 double steps): they are
+        // dispatched first, with the highest issue priority; then the
+        // horizontal lines (W steps, the longest chain of a 16:9 frame), then
+        // the vertical ones.  At 120 VGPRs (4 waves per SIMD) the whole grid
+        // is resident at 1080p (856 workgroups on 1024 slots).  In-process A/B
+        // at 1080p D=128 (profiles/r08_meet/ab_orders_1080p_d128.log.txt),
+        // frame / sgm_paths ms: this order, priorities pair 3 / horizontal 1
+        // 0.790 / 0.487 (two builds), 3 / 2 0.793 / 0.490, 2 / 1 0.792 /
+        // 0.489; horizontal blocks first, horizontal 1 / pair 3 0.796 / 0.490,
+        // horizontal 3 / pair 2 0.818 / 0.514; the kernel that walked down and
+        // back 0.822, 0.825 / 0.517, 0.521.  (Step-0 ablation of §4.16, pair
+        // blocks after the vertical ones: 0.914 / 0.605.)
         f = 0;
-        const int npb = 2 * g.blk_w;
+        const int npb = 4 * g.blk_w;
         if (b < npb) {
             r = 4 + 2 * (b & 1);
-            lb = b >> 1;
-            // (priority 3 / 2: sgm_paths 0.521 / 0.531 ms, frame 0.823 / 0.837 ms)
+            lb = b >> 1;                                  // a block of PAIR_LINES lines
             __builtin_amdgcn_s_setprio(3);
         } else if (b < npb + 2 * g.blk_h) {
             b -= npb;
@@ -118,10 +127,20 @@ __global__ __launch_bounds__(PATH_BLOCK) void sgm_paths_kernel(const uint8_t* __
         CK += (size_t)f * g.ckstr;
         CKV += (size_t)f * g.ckvstr;
     }
-    const int line = lb * LINES_PER_BLOCK + (threadIdx.x >> 4);
+    int line = lb * LINES_PER_BLOCK + (threadIdx.x >> 4);
+    int role = 0;
+    if constexpr (PAIR) {
+        if (r >= 4) {
+            // a pair line takes two rows of a wave: rows 0, 1 are role T of
+            // lines l, l + 1 and rows 2, 3 role B of the same two lines
+            const int row = (int)(threadIdx.x >> 4);
+            line = lb * PAIR_LINES + 2 * (row >> 2) + (row & 1);
+            role = (row >> 1) & 1;
+        }
+    }
     const int k = threadIdx.x & 15;
     const int nlines = r < 2 ? g.H : g.W;
-    if (line >= nlines) return;  // whole 16-lane row leaves together
+    if (line >= nlines) return;  // whole 16-lane row leaves together (both roles of a pair line)
     int rx, ry;
     dir_of(r, rx, ry);
     const rsrc_t rC = make_rsrc(C, g.vol);
@@ -133,7 +152,7 @@ __global__ __launch_bounds__(PATH_BLOCK) void sgm_paths_kernel(const uint8_t* __
             const int pr = r == 4 ? 0 : 1;                // pair 4+5, pair 6+7
             const rsrc_t rCK = make_rsrc(CKV + (size_t)(2 + pr) * g.ckvvol, g.ckvvol);
             const rsrc_t rE = make_rsrc(L8 + (size_t)pr * g.vol, g.vol);
-            pair_line<DPL, pf_v<DPL>(), SL>(rC, rE, g, rx, line, k, rCK);
+            pair_line<DPL, pf_v<DPL>(), SL>(rC, rE, g, rx, line, role, k, rCK);
         } else if (r >= 2) {
             const rsrc_t rCK = make_rsrc(CKV + (size_t)(r - 2) * g.ckvvol, g.ckvvol);
             path_line<DPL, false, pf_v<DPL>(), 2, SL>(rC, rC, g, rx, ry, line, k, rCK);
@@ -242,7 +261,8 @@ hipError_t launch_paths(Ctx& c, const uint8_t* C, int W, int H, int D, int P1, i
         return hipErrorInvalidValue;
     g.pair = pair ? 1 : 0;
     g.dreal = dreal > 0 && dreal < D ? dreal : D;
-    dim3 grid((unsigned)((2 * g.blk_h + (pair ? 4 : 6) * g.blk_w) * npair));
+    // (pair: 2 * 2 * blk_w blocks of 8 pair lines + 2 * blk_w vertical blocks)
+    dim3 grid((unsigned)((2 * g.blk_h + 6 * g.blk_w) * npair));
     t.used = true;
     switch (D) {
         case 64: paths_launch<4, tune::kDiagPair4 != 0>(pair, grid, c.stream, t.start, t.stop, C, L8, CK, CKV, g); break;

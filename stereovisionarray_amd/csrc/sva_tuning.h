@@ -100,20 +100,31 @@ constexpr int kStateMinTree = 1;
 // 3.772 / 3.863 / 3.944, 4K D=256 7.570 / 7.394 / 7.697.
 constexpr int kTileDiagDown = 0;
 constexpr int kTileDiagUp = 0;
-// The pair route: a frame (not a batch) whose 2 * P2 fits a
-// u8 has each diagonal and its opposite walked by one wave of sgm_paths,
-// which writes the two pair-sum volumes E = (L_a - C) + (L_b - C) instead of
-// four L_r volumes; wta_hv reads two volumes and adds 4C.  Per native D
-// (DPL = D / 16); measurements in §4.15.  Only the enabled classes compile a
-// pair instance of the two kernels.
+// The pair route: a frame (not a batch) whose 2 * P2
+// fits a u8 has each diagonal and its opposite walked by one wave of
+// sgm_paths, which writes the two pair-sum volumes E = (L_a - C) + (L_b - C)
+// instead of four L_r volumes; wta_hv reads two volumes and adds 4C.  Per
+// native D (DPL = D / 16); measurements in §4.15.  Only the enabled classes
+// compile a pair instance of the two kernels.
 constexpr int kDiagPair4 = 0, kDiagPair8 = 1, kDiagPair12 = 0, kDiagPair16 = 0;
-// Smallest frame (W * H) that takes the pair route.  A pair wave is a chain of
-// H steps down and H double steps back, against H steps of a diagonal line
-// before, so small frames are bound by that chain, not by their bytes.  Frame
-// ms at D=128, four volumes / pair (in-process A/B, §4.15): 640x480 0.181 /
-// 0.257, 960x540 0.257 / 0.312, 1280x720 0.432 / 0.435, 1080p 0.854 / 0.823,
-// 2560x1440 1.503 / 1.453, 4K 3.42 / 3.11.
-constexpr long long kDiagPairMinPixels = 1600000;
+// Smallest frame (W * H) that takes the pair route.  A pair line's two roles
+// are each a chain of H/2 steps and then H/2 double steps (§4.16; H and H
+// before the two recurrences met in the middle), against H steps of a
+// diagonal line on four volumes, so the smallest frames are still bound by
+// that chain, not by their bytes.  Frame ms at D=128, four volumes (two
+// copies) / pair (in-process A/B, profiles/r08_meet/ab_routes_*): 640x480
+// 0.181, 0.179 / 0.188, 960x540 0.254, 0.255 / 0.275, 1280x720 0.437, 0.435 /
+// 0.404, 1080p 0.867, 0.865 / 0.793, 2560x1440 1.524, 1.501 / 1.365, 4K 3.63,
+// 3.58 / 3.03.  (Walking down and back: 0.181 / 0.257, 0.257 / 0.312, 0.432 /
+// 0.435, 0.854 / 0.823, 1.503 / 1.453, 3.42 / 3.11, and a threshold of 1.6 M.)
+// The crossover is not monotonic in pixels (the pair blocks' share of the CUs
+// depends on W, their chain on H): 1024x768 0.337 / 0.346, 1280x800 0.472 /
+// 0.445, 1920x540 0.503 / 0.524, 1080x1080 0.539 / 0.558, 1600x900 0.605 /
+// 0.614 lose or win by shape, and every size measured from 1400x1050 up wins
+// (1400x1050 0.623 / 0.594, 1440x1080 0.650 / 0.615, 1680x1050 0.719 / 0.711,
+// 1600x1200 0.791 / 0.751, 2048x1024 0.838 / 0.799).  The threshold sits
+// above the largest frame that lost (1600x900, 1.44 M).
+constexpr long long kDiagPairMinPixels = 1450000;
 // prefetch depth (pixels) of wta_hv's two pair-volume loads: wta_hv ms at 1080p
 // D=128 for 2 / 3 / 4: 0.1862 / 0.1837 / 0.1815
 constexpr int kWtahvPfVolPair = 4;
