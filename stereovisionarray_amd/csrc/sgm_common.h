@@ -253,7 +253,10 @@ struct Edges {
     unsigned X = INF2, Y = INF2;
 };
 
-template <int DPL, bool PIN = false>
+// GIVEN_M (path minima): the caller supplies every step's
+// entering m (read from the planes the path kernel wrote), so the step forms
+// no minimum of the new state and leaves m alone.
+template <int DPL, bool PIN = false, bool GIVEN_M = false>
 __device__ __forceinline__ void sgm_step_c(const unsigned (&c)[DPL / 2], unsigned (&A)[DPL / 2],
                                            unsigned& m, unsigned (&ow)[DPL / 4], unsigned P1,
                                            unsigned P2, Edges& e) {
@@ -325,7 +328,7 @@ __device__ __forceinline__ void sgm_step_c(const unsigned (&c)[DPL / 2], unsigne
 #pragma unroll
     for (int j = 0; j < NP; j++) A[j] = add3(min3_u16x2(tp[j], A[j], mP2), c[j], K);
     pairs_to_words<DPL>(A, ow);
-    m = row_min_u32<PIN>(lane_min_u16<NP>(A));
+    if constexpr (!GIVEN_M) m = row_min_u32<PIN>(lane_min_u16<NP>(A));
 }
 
 template <int DPL>
@@ -337,13 +340,39 @@ __device__ __forceinline__ void sgm_step_c(const unsigned (&c)[DPL / 2], unsigne
 }
 
 // The same step on u8-packed cost words (DPL/4 dwords of 4 disparities).
-template <int DPL, bool PIN = false>
+template <int DPL, bool PIN = false, bool GIVEN_M = false>
 __device__ __forceinline__ void sgm_step(const unsigned (&cw)[DPL / 4], unsigned (&A)[DPL / 2],
                                          unsigned& m, unsigned (&ow)[DPL / 4], unsigned P1,
                                          unsigned P2, Edges& e) {
     unsigned c[DPL / 2];
     words_to_pairs<DPL>(cw, c);
-    sgm_step_c<DPL, PIN>(c, A, m, ow, P1, P2, e);
+    sgm_step_c<DPL, PIN, GIVEN_M>(c, A, m, ow, P1, P2, e);
+}
+
+// ---- path minima -----------------------------------------
+// With tune::kPathMinima* the horizontal and vertical lines of the frame
+// route also leave the ENTERING minimum of every pixel, the m its step
+// consumed (m of the line's previous pixel, 0 at the line start; m <= 254),
+// one byte each: [2][H][ns][8] for directions 0, 1 and then [2][nsy][W][8]
+// for directions 2, 3.  A segment's 8 bytes are in the line's walking order,
+// placed by pixel: byte i belongs to the segment's pixel i for directions 0
+// and 2, to pixel 7 - i for directions 1 and 3, so step i of wta_hv's
+// recurrences takes byte i in a ragged segment too (its bytes of pixels
+// outside the image are never read).
+constexpr int kMinimaSeg = 8;
+
+// The last eight entering minima of a line, newest in the top byte.
+struct MinWindow {
+    unsigned lo = 0u, hi = 0u;
+    __device__ __forceinline__ void push(unsigned m) {     // two v_alignbit
+        lo = __builtin_amdgcn_alignbit(hi, lo, 8);
+        hi = __builtin_amdgcn_alignbit(m, hi, 8);
+    }
+};
+
+// Byte i of a segment's minima words.
+__device__ __forceinline__ unsigned minima_byte(const Words<2>& w, int i) {
+    return (w.w[i >> 2] >> ((i & 3) * 8)) & 0xffu;
 }
 
 // Direction table, identical to oracle svo_direction().
@@ -368,10 +397,14 @@ template <int DPL> constexpr int pf_v() {
 // checkpoints every 2^SL pixels (rows for 2 and 3) to rCK instead of the full
 // L_r line to rL (SL is a template parameter: a runtime segment test cost the
 // latency-bound lines of small frames 20 %).
-template <int DPL, bool DIAG, int PF, int CKPT = 0, int SL = 0>
+// MN (CKPT 1 and 2, path minima, §4.17): the line also stores each segment's
+// entering minima to rMN ([H][ns][8] or [nsy][W][8], this direction's plane).
+template <int DPL, bool DIAG, int PF, int CKPT = 0, int SL = 0, bool MN = false>
 __device__ __forceinline__ void path_line(rsrc_t rC, rsrc_t rL, const PathGeom& g, int rx, int ry,
-                                          int line, int k, rsrc_t rCK) {
+                                          int line, int k, rsrc_t rCK, rsrc_t rMN) {
     constexpr int NW = DPL / 4, NP = DPL / 2;
+    static_assert(!MN || ((CKPT == 1 || CKPT == 2) && (1 << SL) == kMinimaSeg),
+                  "path minima: horizontal and vertical checkpoint lines, 8-pixel segments");
     const int W = g.W, H = g.H, D = g.D;
     const unsigned P1 = (unsigned)g.P1, P2 = (unsigned)g.P2;
     const int steps = ry == 0 ? W : H;
@@ -405,6 +438,7 @@ __device__ __forceinline__ void path_line(rsrc_t rC, rsrc_t rL, const PathGeom& 
         lead = CKPT == 1 ? (rx > 0 ? 0 : (SEG - W % SEG) % SEG) : (ry > 0 ? 0 : (SEG - H % SEG) % SEG);
         pc.off -= (unsigned)lead * stride;
     }
+    static_assert(!(MN && STATIC_HITS), "path minima are stored by the runtime segment test");
     const int nsteps = steps + lead;
     // Diagonal lines wrap without per-step x tracking.  Line l visits
     // x = (l + rx*t) mod W and wraps between pixels s and s+1 when s + 1 =
@@ -429,6 +463,26 @@ __device__ __forceinline__ void path_line(rsrc_t rC, rsrc_t rL, const PathGeom& 
     for (int j = 0; j < NP; j++) A[j] = 0u;   // L(q) = 0, m = 0  =>  L = C
     unsigned m = 0u;
     Edges edges;
+    MinWindow mw;
+    // A segment's minima leave with its checkpoint, in the same out-of-line
+    // block; a line that ends inside a segment (directions 0 and 2, W or H not
+    // a multiple of 8) flushes there, its bytes moved down to their pixels'
+    // places.  `i` = the pixel's place in its segment.  Every lane of the row
+    // holds the same window: lane 0 stores it.
+    // The segment test is integer arithmetic on wave-uniform values (scalar
+    // unit): e = pixels walked (forward lines) or the pixel's coordinate
+    // (backward lines); a segment ends where e is a multiple of 8, a forward
+    // line also at e = steps; the checkpoint is stored unless e = ck_none.
+    const bool fwd = CKPT == 1 ? rx > 0 : ry > 0;
+    const int mn_end = fwd ? steps : -1, ck_none = fwd ? steps : 0, mn_fmask = fwd ? kMinimaSeg - 1 : 0;
+    auto store_minima = [&](unsigned seg_off, int e) {
+        unsigned long long w = ((unsigned long long)mw.hi << 32) | mw.lo;
+        w >>= (unsigned)(-e & mn_fmask) * 8u;     // (7 - the pixel's place) bytes, forward lines
+        if (k == 0) {
+            const unsigned ww[2] = {(unsigned)w, (unsigned)(w >> 32)};
+            bstore<2, tune::kCkptStoreAux>(rMN, seg_off * (unsigned)kMinimaSeg, ww);
+        }
+    };
 
     Words<NW> ring[PF];
 #pragma unroll
@@ -462,6 +516,7 @@ __device__ __forceinline__ void path_line(rsrc_t rC, rsrc_t rL, const PathGeom& 
 #pragma unroll
         for (int w = 0; w < NW; w++) cw[w] = ring[p].w[w];
         unsigned ow[NW];
+        if constexpr (MN) mw.push(m);
         sgm_step<DPL>(cw, A, m, ow, P1, P2, edges);
         if constexpr (CKPT == 1 && STATIC_HITS) {
             // the last pixel of a segment (rx > 0) or its first (rx < 0) is at
@@ -481,6 +536,17 @@ __device__ __forceinline__ void path_line(rsrc_t rC, rsrc_t rL, const PathGeom& 
                 if (ry > 0 ? y + 1 < H : y > 0)
                     bstore<NW, tune::kCkptStoreAux>(rCK, ((unsigned)((y >> SL) * W + x0) * (unsigned)D +
                                              (unsigned)(k * DPL)), ow);
+            }
+        } else if constexpr (MN) {
+            // the segment's last pixel in walking order, or the line's last
+            constexpr int SEG = 1 << SL;
+            const int e = fwd ? ts + 1 : steps - 1 - ts;
+            if (__builtin_expect((int)((e & (SEG - 1)) == 0) | (int)(e == mn_end), 0)) {
+                const int sg = (fwd ? e - 1 : e) >> SL;
+                const unsigned so = CKPT == 1 ? (unsigned)(y0 * g.ns + sg) : (unsigned)(sg * W + x0);
+                if (e != ck_none)
+                    bstore<NW, tune::kCkptStoreAux>(rCK, so * (unsigned)D + (unsigned)(k * DPL), ow);
+                store_minima(so, e);
             }
         } else if constexpr (CKPT == 1) {
             // ts is the (wave-uniform) step index; x the pixel just computed
@@ -589,7 +655,9 @@ __device__ __forceinline__ void unpack_add(const unsigned (&w)[NW], unsigned (&S
 // checkpoint truncated; they restart at 255.  Every real disparity evolves
 // the same from 255 as from the true value: a padded neighbour enters only
 // as A + P1 >= 255 >= m + P2 (m <= 62), and never sets the row minimum.
-template <int DPL, bool PAD, bool PIN = false>
+// GIVEN_M (path minima, §4.17): the caller has m from the minima planes (the
+// first step's byte): no minimum is formed here, m is left alone.
+template <int DPL, bool PAD, bool PIN = false, bool GIVEN_M = false>
 __device__ __forceinline__ void state_from_words(const Words<DPL / 4>& w, unsigned (&A)[DPL / 2],
                                                  unsigned& m, const unsigned (&padm)[DPL / 2]) {
     constexpr int NP = DPL / 2;
@@ -598,7 +666,8 @@ __device__ __forceinline__ void state_from_words(const Words<DPL / 4>& w, unsign
 #pragma unroll
         for (int j = 0; j < NP; j++) A[j] |= padm[j] & 0x00ff00ffu;   // A < 256: OR = max
     }
-    if constexpr (tune::kStateMinTree) {
+    if constexpr (GIVEN_M) {
+    } else if constexpr (tune::kStateMinTree) {
         m = row_min_u32<PIN>(lane_min_u16<NP>(A));
     } else {
         unsigned mm = 0xffffffffu;
@@ -611,10 +680,10 @@ __device__ __forceinline__ void state_from_words(const Words<DPL / 4>& w, unsign
         m = row_min_u32<PIN>(mm);
     }
 }
-template <int DPL, bool PAD, bool PIN = false>
+template <int DPL, bool PAD, bool PIN = false, bool GIVEN_M = false>
 __device__ __forceinline__ void load_state(rsrc_t r, unsigned off, unsigned (&A)[DPL / 2],
                                            unsigned& m, const unsigned (&padm)[DPL / 2]) {
-    state_from_words<DPL, PAD, PIN>(bload<DPL / 4>(r, off), A, m, padm);
+    state_from_words<DPL, PAD, PIN, GIVEN_M>(bload<DPL / 4>(r, off), A, m, padm);
 }
 
 // One PAIR line: a down diagonal (direction 4 or 6, x step

@@ -40,6 +40,10 @@
 //      2 with the four diagonals as pair lines: two u8 pair-sum volumes
 //      [2][H][W][D] instead of four L_r volumes.  A pair line takes two DPP
 //      rows of a wave (§4.16), so a wave carries 2 and a workgroup 8 of them.
+//      With path minima (sgm_paths_kernel<DPL, PAIR, true>)
+//      the horizontal and vertical lines of either mode-2 route also store
+//      each pixel's entering minimum, 8 bytes per segment beside its
+//      checkpoint, which wta_hv.hip reads instead of forming it again.
 //   (Mode 1, the round-2 route of DESIGN.md §4.6 -- six volumes, horizontal
 //   checkpoints only, finished by wta_h.hip -- was removed in ABI v5.)
 #include "sgm_common.h"
@@ -59,11 +63,16 @@ constexpr int PAIR_LINES = LINES_PER_BLOCK / 2;   // a pair line is two rows: ro
 // pair_line: two 16-lane rows per line, which meet in the middle, §4.16) that
 // write two pair-sum volumes, L8 = [2][H][W][D] (pairs 4+5, 6+7), through two
 // wave-private row-checkpoint planes after the vertical ones.
-template <int DPL, bool PAIR>
+// MN (path minima; one frame, tile pipeline only): the
+// horizontal and vertical lines also store every pixel's entering minimum to
+// MNP, [2][H][ns][8] then [2][nsy][W][8] (sgm_common.h), which wta_hv reads
+// instead of recomputing it.
+template <int DPL, bool PAIR, bool MN>
 __global__ __launch_bounds__(PATH_BLOCK) void sgm_paths_kernel(const uint8_t* __restrict__ C,
                                                                uint8_t* __restrict__ L8,
                                                                uint8_t* __restrict__ CK,
                                                                uint8_t* __restrict__ CKV,
+                                                               uint8_t* __restrict__ MNP,
                                                                PathGeom g) {
     // Horizontal directions (W steps per line, the longest) get the lowest
     // block ids -- every frame's of a batch before any vertical / diagonal
@@ -147,6 +156,11 @@ __global__ __launch_bounds__(PATH_BLOCK) void sgm_paths_kernel(const uint8_t* __
     // the tile pipeline's checkpoint segment (§4.9), rows and columns
     constexpr int SL = DPL <= 8 ? tune::kWtahvTileLog2 : tune::kWtahvTileLog2Wide;
     constexpr bool DOWN = diag_ckpt_down(DPL), UP = diag_ckpt_up(DPL);
+    // this direction's minima plane (directions 0..3 of an MN launch)
+    const size_t mnh = (size_t)g.H * g.ns * kMinimaSeg, mnv = (size_t)g.nsy * g.W * kMinimaSeg;
+    const rsrc_t rMN = !MN || r >= 4 ? rC
+                       : r >= 2 ? make_rsrc(MNP + 2 * mnh + (size_t)(r - 2) * mnv, mnv)
+                                : make_rsrc(MNP + (size_t)r * mnh, mnh);
     if constexpr (PAIR) {
         if (r >= 4) {
             const int pr = r == 4 ? 0 : 1;                // pair 4+5, pair 6+7
@@ -155,10 +169,10 @@ __global__ __launch_bounds__(PATH_BLOCK) void sgm_paths_kernel(const uint8_t* __
             pair_line<DPL, pf_v<DPL>(), SL>(rC, rE, g, rx, line, role, k, rCK);
         } else if (r >= 2) {
             const rsrc_t rCK = make_rsrc(CKV + (size_t)(r - 2) * g.ckvvol, g.ckvvol);
-            path_line<DPL, false, pf_v<DPL>(), 2, SL>(rC, rC, g, rx, ry, line, k, rCK);
+            path_line<DPL, false, pf_v<DPL>(), 2, SL, MN>(rC, rC, g, rx, ry, line, k, rCK, rMN);
         } else {
             const rsrc_t rCK = make_rsrc(CK + (size_t)r * g.ckvol, g.ckvol);
-            path_line<DPL, false, pf_h<DPL>(), 1, SL>(rC, rC, g, rx, ry, line, k, rCK);
+            path_line<DPL, false, pf_h<DPL>(), 1, SL, MN>(rC, rC, g, rx, ry, line, k, rCK, rMN);
         }
     } else if (r >= 4 && g.ckpt && (ry > 0 ? DOWN : UP)) {
         // tile pipeline, diagonals recomputed per tile: row
@@ -166,7 +180,7 @@ __global__ __launch_bounds__(PATH_BLOCK) void sgm_paths_kernel(const uint8_t* __
         // vertical planes: the down pair (4, 6), then the up pair (5, 7)
         const int plane = ry > 0 ? 2 + (r == 4 ? 0 : 1) : 2 + (DOWN ? 2 : 0) + (r == 5 ? 0 : 1);
         const rsrc_t rCK = make_rsrc(CKV + (size_t)plane * g.ckvvol, g.ckvvol);
-        path_line<DPL, true, pf_v<DPL>(), 3, SL>(rC, rC, g, rx, ry, line, k, rCK);
+        path_line<DPL, true, pf_v<DPL>(), 3, SL>(rC, rC, g, rx, ry, line, k, rCK, rCK);
     } else if (r >= 4) {
         // volume slot: every direction (8 volumes), or the tile pipeline's
         // diagonals that stay volumes, in direction order
@@ -175,35 +189,50 @@ __global__ __launch_bounds__(PATH_BLOCK) void sgm_paths_kernel(const uint8_t* __
                        : UP ? (r == 4 ? 0 : 1)            // 4, 6
                        : r - 4;
         const rsrc_t rL = make_rsrc(L8 + (size_t)slot * g.vol, g.vol);
-        path_line<DPL, true, pf_v<DPL>()>(rC, rL, g, rx, ry, line, k, rL);
+        path_line<DPL, true, pf_v<DPL>()>(rC, rL, g, rx, ry, line, k, rL, rL);
     } else if (r >= 2 && g.ckpt) {
         const rsrc_t rCK = make_rsrc(CKV + (size_t)(r - 2) * g.ckvvol, g.ckvvol);
-        path_line<DPL, false, pf_v<DPL>(), 2, SL>(rC, rC, g, rx, ry, line, k, rCK);
+        path_line<DPL, false, pf_v<DPL>(), 2, SL, MN>(rC, rC, g, rx, ry, line, k, rCK, rMN);
     } else if (r >= 2) {
         const rsrc_t rL = make_rsrc(L8 + (size_t)r * g.vol, g.vol);
-        path_line<DPL, false, pf_v<DPL>()>(rC, rL, g, rx, ry, line, k, rL);
+        path_line<DPL, false, pf_v<DPL>()>(rC, rL, g, rx, ry, line, k, rL, rL);
     } else if (g.ckpt) {
         const rsrc_t rCK = make_rsrc(CK + (size_t)r * g.ckvol, g.ckvol);
-        path_line<DPL, false, pf_h<DPL>(), 1, SL>(rC, rC, g, rx, ry, line, k, rCK);
+        path_line<DPL, false, pf_h<DPL>(), 1, SL, MN>(rC, rC, g, rx, ry, line, k, rCK, rMN);
     } else {
         const rsrc_t rL = make_rsrc(L8 + (size_t)r * g.vol, g.vol);
-        path_line<DPL, false, pf_h<DPL>()>(rC, rL, g, rx, ry, line, k, rL);
+        path_line<DPL, false, pf_h<DPL>()>(rC, rL, g, rx, ry, line, k, rL, rL);
     }
 }
 
-// (a pair instance exists only for the D classes whose pair route is enabled)
-template <int DPL, bool EN>
-void paths_launch(bool pair, dim3 grid, hipStream_t s, hipEvent_t start, hipEvent_t stop,
-                  const uint8_t* C, uint8_t* L8, uint8_t* CK, uint8_t* CKV, const PathGeom& g) {
+// (a pair instance exists only for the D classes whose pair route is enabled,
+// a minima instance only for those with tune::kPathMinima*; launch_paths has
+// refused the others)
+template <int DPL, bool EN, bool MN>
+void paths_launch_mn(bool pair, dim3 grid, hipStream_t s, hipEvent_t start, hipEvent_t stop,
+                     const uint8_t* C, uint8_t* L8, uint8_t* CK, uint8_t* CKV, uint8_t* MNP,
+                     const PathGeom& g) {
     if constexpr (EN) {
         if (pair) {
-            hipExtLaunchKernelGGL((sgm_paths_kernel<DPL, true>), grid, dim3(PATH_BLOCK), 0, s, start,
-                                  stop, 0, C, L8, CK, CKV, g);
+            hipExtLaunchKernelGGL((sgm_paths_kernel<DPL, true, MN>), grid, dim3(PATH_BLOCK), 0, s,
+                                  start, stop, 0, C, L8, CK, CKV, MNP, g);
             return;
         }
     }
-    hipExtLaunchKernelGGL((sgm_paths_kernel<DPL, false>), grid, dim3(PATH_BLOCK), 0, s, start, stop,
-                          0, C, L8, CK, CKV, g);
+    hipExtLaunchKernelGGL((sgm_paths_kernel<DPL, false, MN>), grid, dim3(PATH_BLOCK), 0, s, start,
+                          stop, 0, C, L8, CK, CKV, MNP, g);
+}
+template <int DPL, bool EN, bool MNEN>
+void paths_launch(bool pair, dim3 grid, hipStream_t s, hipEvent_t start, hipEvent_t stop,
+                  const uint8_t* C, uint8_t* L8, uint8_t* CK, uint8_t* CKV, uint8_t* MNP,
+                  const PathGeom& g) {
+    if constexpr (MNEN) {
+        if (MNP) {
+            paths_launch_mn<DPL, EN, true>(pair, grid, s, start, stop, C, L8, CK, CKV, MNP, g);
+            return;
+        }
+    }
+    paths_launch_mn<DPL, EN, false>(pair, grid, s, start, stop, C, L8, CK, CKV, nullptr, g);
 }
 
 }  // namespace
@@ -223,7 +252,14 @@ TileGeom tile_geom(int W, int H, int D) {
     const int ndp = (diag_ckpt_down(dpl) ? 2 : 0) + (diag_ckpt_up(dpl) ? 2 : 0);
     t.dck_bytes = (size_t)ndp / 2 * t.vck_bytes;   // one plane per recomputed diagonal
     t.nvol = 4 - ndp;
+    t.hmn_bytes = 2 * (size_t)H * t.nsx * sgm::kMinimaSeg;
+    t.vmn_bytes = 2 * (size_t)t.nty * W * sgm::kMinimaSeg;
     return t;
+}
+
+bool path_minima_enabled(int D) {
+    return (D == 64 && tune::kPathMinima4) || (D == 128 && tune::kPathMinima8) ||
+           (D == 192 && tune::kPathMinima12) || (D == 256 && tune::kPathMinima16);
 }
 
 bool diag_pair_enabled(int D) {
@@ -232,7 +268,8 @@ bool diag_pair_enabled(int D) {
 }
 
 hipError_t launch_paths(Ctx& c, const uint8_t* C, int W, int H, int D, int P1, int P2,
-                        uint8_t* L8, uint8_t* CK, uint8_t* CKV, int npair, bool pair, int dreal) {
+                        uint8_t* L8, uint8_t* CK, uint8_t* CKV, int npair, bool pair, int dreal,
+                        uint8_t* MN) {
     DispatchTimer t(c, "sgm_paths");
     PathGeom g;
     g.W = W; g.H = H; g.D = D; g.P1 = P1; g.P2 = P2;
@@ -260,15 +297,18 @@ hipError_t launch_paths(Ctx& c, const uint8_t* C, int W, int H, int D, int P1, i
                  tile_geom(W, H, D).nvol != 4))
         return hipErrorInvalidValue;
     g.pair = pair ? 1 : 0;
+    // path minima: one frame of the tile pipeline, 8-pixel segments
+    if (MN && (!CK || npair != 1 || !path_minima_enabled(D) || (1 << tg.seg_log2) != sgm::kMinimaSeg))
+        return hipErrorInvalidValue;
     g.dreal = dreal > 0 && dreal < D ? dreal : D;
     // (pair: 2 * 2 * blk_w blocks of 8 pair lines + 2 * blk_w vertical blocks)
     dim3 grid((unsigned)((2 * g.blk_h + 6 * g.blk_w) * npair));
     t.used = true;
     switch (D) {
-        case 64: paths_launch<4, tune::kDiagPair4 != 0>(pair, grid, c.stream, t.start, t.stop, C, L8, CK, CKV, g); break;
-        case 128: paths_launch<8, tune::kDiagPair8 != 0>(pair, grid, c.stream, t.start, t.stop, C, L8, CK, CKV, g); break;
-        case 192: paths_launch<12, tune::kDiagPair12 != 0>(pair, grid, c.stream, t.start, t.stop, C, L8, CK, CKV, g); break;
-        case 256: paths_launch<16, tune::kDiagPair16 != 0>(pair, grid, c.stream, t.start, t.stop, C, L8, CK, CKV, g); break;
+        case 64: paths_launch<4, tune::kDiagPair4 != 0, tune::kPathMinima4 != 0>(pair, grid, c.stream, t.start, t.stop, C, L8, CK, CKV, MN, g); break;
+        case 128: paths_launch<8, tune::kDiagPair8 != 0, tune::kPathMinima8 != 0>(pair, grid, c.stream, t.start, t.stop, C, L8, CK, CKV, MN, g); break;
+        case 192: paths_launch<12, tune::kDiagPair12 != 0, tune::kPathMinima12 != 0>(pair, grid, c.stream, t.start, t.stop, C, L8, CK, CKV, MN, g); break;
+        case 256: paths_launch<16, tune::kDiagPair16 != 0, tune::kPathMinima16 != 0>(pair, grid, c.stream, t.start, t.stop, C, L8, CK, CKV, MN, g); break;
         default: t.used = false; return hipErrorInvalidValue;
     }
     return hipGetLastError();

@@ -176,6 +176,15 @@ int check_sgm(Ctx* c, const sva_sgm_params* p, int W, int H, bool native = false
 // Checkpoint bytes of the pair route: the horizontal and vertical planes plus
 // one row-checkpoint plane per diagonal pair.
 size_t pair_ckpt_bytes(const TileGeom& tg) { return tg.hck_bytes + tg.vck_bytes + tg.vck_bytes; }
+// Checkpoint bytes of a frame on either diagonal route; the minima planes of
+// the horizontal and vertical lines follow them in the
+// context's checkpoint allocation where this D has them.
+size_t frame_ckpt_bytes(const TileGeom& tg, bool pair) {
+    return pair ? pair_ckpt_bytes(tg) : tg.hck_bytes + tg.vck_bytes + tg.dck_bytes;
+}
+size_t frame_minima_bytes(const TileGeom& tg, int Dp) {
+    return tg.nvol == 4 && path_minima_enabled(Dp) ? tg.hmn_bytes + tg.vmn_bytes : 0;
+}
 
 int paths_wta(Ctx* c, const uint8_t* C, int W, int H, const sva_sgm_params* p, int Dp,
               uint16_t* disp, float* sub) {
@@ -191,14 +200,16 @@ int paths_wta(Ctx* c, const uint8_t* C, int W, int H, const sva_sgm_params* p, i
                                                         : tune::kDiagPairMinPixels;
     const bool pair = tg.nvol == 4 && diag_pair_ok(Dp, p->P2) && (long long)W * H >= minpx;
     SVA_HIP(c, c->paths.ensure(nv * (pair ? 2 : tg.nvol)), "path workspace");
-    SVA_HIP(c, c->ckpt.ensure(pair ? pair_ckpt_bytes(tg) : tg.hck_bytes + tg.vck_bytes + tg.dck_bytes),
-            "checkpoint workspace");
+    const size_t ckb = frame_ckpt_bytes(tg, pair), mnb = frame_minima_bytes(tg, Dp);
+    SVA_HIP(c, c->ckpt.ensure(ckb + mnb), "checkpoint workspace");
     uint8_t* L4 = (uint8_t*)c->paths.ptr;
     uint8_t* CK = (uint8_t*)c->ckpt.ptr;
     uint8_t* CKV = CK + tg.hck_bytes;
-    SVA_HIP(c, launch_paths(*c, C, W, H, Dp, p->P1, p->P2, L4, CK, CKV, 1, pair, p->D), "paths launch");
+    uint8_t* MN = mnb ? CK + ckb : nullptr;     // (ckb is a multiple of D: 8-byte aligned)
+    SVA_HIP(c, launch_paths(*c, C, W, H, Dp, p->P1, p->P2, L4, CK, CKV, 1, pair, p->D, MN),
+            "paths launch");
     SVA_HIP(c, launch_wta_hv(*c, C, L4, CK, CKV, W, H, Dp, p->P1, p->P2, p->dmin, disp, sub, p->D, 1,
-                             pair),
+                             pair, MN),
             "wta launch");
     c->last_diag_route = pair ? 1 : 0;
     return SVA_OK;
@@ -638,10 +649,11 @@ int time_stage_set(Ctx* c, int W, int H, int D, int64_t* ns) {
     for (int r = 0; r < 4 && e == hipSuccess; r++) {
         e = hipEventRecord(a, c->stream);
         // (the route a frame with the default penalties takes)
+        const bool pair = tg.nvol == 4 && diag_pair_ok(D, 120) &&
+                          (long long)W * H >= tune::kDiagPairMinPixels;
         if (e == hipSuccess)
-            e = launch_paths(*c, C, W, H, D, 10, 120, L4, CK, CK + tg.hck_bytes, 1,
-                             tg.nvol == 4 && diag_pair_ok(D, 120) &&
-                                 (long long)W * H >= tune::kDiagPairMinPixels);
+            e = launch_paths(*c, C, W, H, D, 10, 120, L4, CK, CK + tg.hck_bytes, 1, pair, 0,
+                             frame_minima_bytes(tg, D) ? CK + frame_ckpt_bytes(tg, pair) : nullptr);
         if (e == hipSuccess) e = hipEventRecord(b, c->stream);
         if (e == hipSuccess) e = hipEventSynchronize(b);
         float ms = 0.f;
@@ -737,9 +749,8 @@ int sva_reserve(void* ctx, int W, int H, int D) {
     const TileGeom tg = tile_geom(W, H, D);
     // (the larger of the two diagonal routes' layouts: four volumes, and the
     // pair route's two more row-checkpoint planes)
-    const size_t ckb = tg.nvol == 4 && diag_pair_enabled(D)
-                           ? pair_ckpt_bytes(tg)
-                           : tg.hck_bytes + tg.vck_bytes + tg.dck_bytes;
+    const size_t ckb = frame_ckpt_bytes(tg, tg.nvol == 4 && diag_pair_enabled(D)) +
+                       frame_minima_bytes(tg, D);
     SVA_HIP(c, c->paths.ensure(nv * tg.nvol), "reserve");
     SVA_HIP(c, c->ckpt.ensure(ckb), "reserve");
     // (once per allocation: a repeated reserve of a size the buffers already

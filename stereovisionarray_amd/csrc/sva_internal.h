@@ -183,9 +183,14 @@ hipError_t launch_cost(Ctx& c, const uint64_t* cl, const uint64_t* cr, int W, in
 // DESIGN.md §4.15, L8 = [2][H][W][D] pair sums (4+5, 6+7) and CKV = the two
 // vertical planes plus two wave-private row-checkpoint planes (pair_layout);
 // dreal as for launch_wta_hv.
+// MN (one frame of the tile pipeline, path_minima_enabled): the horizontal and
+// vertical lines also store their entering minima, hmn_bytes + vmn_bytes of
+// tile_geom, for launch_wta_hv(.., MN).
 hipError_t launch_paths(Ctx& c, const uint8_t* C, int W, int H, int D, int P1, int P2,
                         uint8_t* L8, uint8_t* CK = nullptr, uint8_t* CKV = nullptr,
-                        int npair = 1, bool pair = false, int dreal = 0);
+                        int npair = 1, bool pair = false, int dreal = 0, uint8_t* MN = nullptr);
+// Path minima: compiled in for this native D (tune::kPathMinima*).
+bool path_minima_enabled(int D);
 // The pair route: compiled in for this native D (tune::kDiagPair*), and usable
 // for a frame with these penalties (the u8 pair sum holds 2 * P2).
 bool diag_pair_enabled(int D);
@@ -201,6 +206,8 @@ struct TileGeom {
     size_t vck_bytes;         // [2][nty][W][D]: directions 2, 3
     size_t dck_bytes;         // [2][nty][W][D]: directions 4, 6 (0 when they are volumes)
     int nvol;                 // diagonal volumes the path kernel writes: 2 (5, 7) or 4
+    size_t hmn_bytes;         // [2][H][nsx][8]: entering minima of directions 0, 1 (§4.17)
+    size_t vmn_bytes;         // [2][nty][W][8]: of directions 2, 3
 };
 TileGeom tile_geom(int W, int H, int D);
 // Which diagonal pairs the path kernel leaves as row checkpoints instead of
@@ -230,10 +237,12 @@ inline int padded_D(int D) {
 // §4.7), WTA over d < dreal only.
 bool wta_hv_supported(int D);
 // pair: L4 holds the pair route's two pair-sum volumes (one frame).
+// MN: the minima planes of launch_paths(.., MN) for the same frame; the
+// recurrences read each step's m there (one frame, path_minima_enabled).
 hipError_t launch_wta_hv(Ctx& c, const uint8_t* C, const uint8_t* L4, const uint8_t* CK,
                          const uint8_t* CKV, int W, int H, int D, int P1, int P2, int dmin,
                          uint16_t* disp, float* sub, int dreal = 0, int npair = 1,
-                         bool pair = false);
+                         bool pair = false, const uint8_t* MN = nullptr);
 // wta.hip
 hipError_t launch_sum(Ctx& c, const uint8_t* L8, int W, int H, int D, uint16_t* S);
 hipError_t launch_wta_from_sum(Ctx& c, const uint16_t* S, int W, int H, int D, int dmin,

@@ -125,6 +125,26 @@ constexpr int kDiagPair4 = 0, kDiagPair8 = 1, kDiagPair12 = 0, kDiagPair16 = 0;
 // 1600x1200 0.791 / 0.751, 2048x1024 0.838 / 0.799).  The threshold sits
 // above the largest frame that lost (1600x900, 1.44 M).
 constexpr long long kDiagPairMinPixels = 1450000;
+// Path minima: on the frame route the horizontal and
+// vertical lines of sgm_paths also store every pixel's entering minimum (one
+// byte; 8 bytes per segment beside its checkpoint), and wta_hv's four
+// recurrences read m instead of forming it (7 VALU of each step, 4 of them
+// half-rate DPP).  Per native D (DPL = D / 16); only the enabled classes
+// compile the minima instances of the two kernels.  The stage entries and
+// the batch route keep the instances without.  D=128, 1080p
+// (profiles/r09_minima/): wta_hv static VALU 1,607 -> 1,416, SQ_INSTS_VALU
+// 103.5 M -> 91.2 M; bench lines, parent / this alternating, ms per step
+// 0.7980-0.7986 / 0.7887-0.7897 and, in a second visit, 0.7967-0.7995 /
+// 0.7901-0.7909 (wta_hv 0.195 -> 0.1895, sgm_paths 0.5035 -> 0.5005): -1.1 %,
+// less than the VALU ratio because wta_hv was not on its VALU ceiling alone
+// (§4.17).  The four-volume route forced at 1080p, in-process: wta_hv 0.250,
+// 0.243 -> 0.248, frame 0.877, 0.870 -> 0.875, nothing beyond the spread of
+// the two parent copies, and never slower; it shares the switch.  D=192 /
+// 256 measured with the switch on (ab_wide_*): frame 1.302, 1.285 -> 1.290 and
+// 1.653, 1.678 -> 1.667, inside the spread of two copies of one build: off.
+// D=64 is not built (its lines store checkpoints at static positions,
+// kStaticCkptHitsMaxDpl, and would need their own flush).
+constexpr int kPathMinima4 = 0, kPathMinima8 = 1, kPathMinima12 = 0, kPathMinima16 = 0;
 // prefetch depth (pixels) of wta_hv's two pair-volume loads: wta_hv ms at 1080p
 // D=128 for 2 / 3 / 4: 0.1862 / 0.1837 / 0.1815
 constexpr int kWtahvPfVolPair = 4;

@@ -19,6 +19,8 @@
 //            and the first-minimum WTA (+ parabola) picks d*.
 // Every recurrence restarts from the exact state the path kernel had, so L,
 // S, d* and the sub-pixel value are bit-identical to the 8-volume route.
+// On the frame route of the D classes with tune::kPathMinima* every step's m
+// is read from the path kernel's minima planes as well.
 //
 // Bytes per disparity: 1 C read (phase H re-reads the tile's cost words from
 // L2, where phase V just brought them) + 4 volume reads, and the path kernel
@@ -54,11 +56,17 @@ template <int DPL, bool PAIR> constexpr int pf_vol() {
 // PAIR (the pair route): L4 holds two pair-sum volumes
 // E = (L_a - C) + (L_b - C) for the diagonal pairs 4+5 and 6+7 instead of four
 // L_r volumes; the missing 4C enters V in phase V.
-template <int DPL, int TYL, bool PAD, bool PAIR>
+// MN (path minima): every step of phase V and phase H takes
+// its m from the planes the path kernel wrote (MNP: [2][H][nsx][8], then
+// [2][nty][W][8]; byte i of a segment = step i of the recurrence, in both
+// directions) instead of reducing the state it just formed: the only row
+// minimum left is the WTA's.
+template <int DPL, int TYL, bool PAD, bool PAIR, bool MN>
 __global__ __launch_bounds__(TB, tune::kWtahvMinWaves) void wta_hv_kernel(const uint8_t* __restrict__ C,
                                                     const uint8_t* __restrict__ L4,
                                                     const uint8_t* __restrict__ CK,
-                                                    const uint8_t* __restrict__ CKV, WtaHvGeom g,
+                                                    const uint8_t* __restrict__ CKV,
+                                                    const uint8_t* __restrict__ MNP, WtaHvGeom g,
                                                     uint16_t* __restrict__ disp,
                                                     float* __restrict__ sub) {
     constexpr int NW = DPL / 4, NP = DPL / 2;
@@ -83,6 +91,7 @@ __global__ __launch_bounds__(TB, tune::kWtahvMinWaves) void wta_hv_kernel(const 
     constexpr int ND = (DOWN ? 2 : 0) + (UP ? 2 : 0);   // recomputed diagonals
     constexpr int NV = PAIR ? 2 : 4 - ND;               // diagonal volumes read
     static_assert(!PAIR || ND == 0, "the pair route replaces all four diagonal volumes");
+    static_assert(!MN || (TY == kMinimaSeg && ND == 0), "path minima: 8-pixel segments, no phase D");
     C += (size_t)f * g.vol;
     L4 += (size_t)f * NV * g.vol;
     CK += (size_t)f * 2 * g.hck;
@@ -139,6 +148,25 @@ __global__ __launch_bounds__(TB, tune::kWtahvMinWaves) void wta_hv_kernel(const 
             ch[j] = bload<NW>(rC, (yh * uW + (unsigned)(hx + j)) * uD + lane_d);
     };
     if constexpr (tune::kWtahvRowCFirst != 0) load_row();
+    // the slot's entering minima: phase V's column segment (directions 2, 3)
+    // and phase H's row segment (0, 1), 8 bytes each, the same in all 16 lanes
+    Words<2> mv[2] = {}, mh[2] = {};
+    if constexpr (MN) {
+        const unsigned hmn = (unsigned)H * (unsigned)g.nsx * (unsigned)kMinimaSeg;
+        const unsigned vmn = (unsigned)g.nty * uW * (unsigned)kMinimaSeg;
+        const unsigned vo = ((unsigned)ty * uW + xv) * (unsigned)kMinimaSeg;
+        const unsigned ho = ((unsigned)(y0 + (slot / SPR)) * (unsigned)g.nsx +
+                             (unsigned)((x0 + (slot % SPR) * TY) >> TYL)) * (unsigned)kMinimaSeg;
+#pragma unroll
+        for (int d = 0; d < 2; d++) {
+            mv[d] = bload<2>(make_rsrc(MNP + 2 * (size_t)hmn + (size_t)d * vmn, vmn), vo);
+            mh[d] = bload<2>(make_rsrc(MNP + (size_t)d * hmn, hmn), ho);
+        }
+    }
+    // m of step i (MN), else the running minimum the last step left
+    auto given_m = [](unsigned& m, const Words<2>& w, int i) {
+        if constexpr (MN) m = minima_byte(w, i);
+    };
 
     auto zero_state = [](unsigned (&A)[NP], unsigned& m) {
 #pragma unroll
@@ -153,12 +181,12 @@ __global__ __launch_bounds__(TB, tune::kWtahvMinWaves) void wta_hv_kernel(const 
     // chains per wave).
     if (vcol) {
         if (ty > 0)
-            load_state<DPL, PAD, PIN>(make_rsrc(CKV, g.vck), ((unsigned)(ty - 1) * uW + xv) * uD + lane_d,
+            load_state<DPL, PAD, PIN, MN>(make_rsrc(CKV, g.vck), ((unsigned)(ty - 1) * uW + xv) * uD + lane_d,
                                  Aa, ma, padm);
         else
             zero_state(Aa, ma);
         if (y0 + TY < H)
-            load_state<DPL, PAD, PIN>(make_rsrc(CKV + g.vck, g.vck),
+            load_state<DPL, PAD, PIN, MN>(make_rsrc(CKV + g.vck, g.vck),
                                  ((unsigned)(ty + 1) * uW + xv) * uD + lane_d, Ab, mb, padm);
         else
             zero_state(Ab, mb);
@@ -197,8 +225,16 @@ __global__ __launch_bounds__(TB, tune::kWtahvMinWaves) void wta_hv_kernel(const 
             for_seq<TY>([&](auto I) {
                 constexpr int i = decltype(I)::value, ru = TY - 1 - i;
                 unsigned ow[NW];
-                if (i < ny) { sgm_step<DPL, PIN>(cv[i].w, Aa, ma, ow, P1, P2, ea); keep(LD[i], Aa, ow); }
-                if (ru < ny) { sgm_step<DPL, PIN>(cv[ru].w, Ab, mb, ow, P1, P2, eb); keep(LU[ru], Ab, ow); }
+                if (i < ny) {
+                    given_m(ma, mv[0], i);
+                    sgm_step<DPL, PIN, MN>(cv[i].w, Aa, ma, ow, P1, P2, ea);
+                    keep(LD[i], Aa, ow);
+                }
+                if (ru < ny) {
+                    given_m(mb, mv[1], i);
+                    sgm_step<DPL, PIN, MN>(cv[ru].w, Ab, mb, ow, P1, P2, eb);
+                    keep(LU[ru], Ab, ow);
+                }
             });
             for_seq<TY>([&](auto R) {
                 constexpr int r = decltype(R)::value;
@@ -218,11 +254,12 @@ __global__ __launch_bounds__(TB, tune::kWtahvMinWaves) void wta_hv_kernel(const 
                 constexpr int i = decltype(I)::value;
                 unsigned ow[NW];
                 if (i < ny) {
+                    given_m(ma, mv[0], i);
                     if constexpr (UNPACK1) {
                         words_to_pairs<DPL>(cv[i].w, cvp[i]);
-                        sgm_step_c<DPL, PIN>(cvp[i], Aa, ma, ow, P1, P2, ea);
+                        sgm_step_c<DPL, PIN, MN>(cvp[i], Aa, ma, ow, P1, P2, ea);
                     } else {
-                        sgm_step<DPL, PIN>(cv[i].w, Aa, ma, ow, P1, P2, ea);
+                        sgm_step<DPL, PIN, MN>(cv[i].w, Aa, ma, ow, P1, P2, ea);
                     }
                     keep(LD[i], Aa, ow);
                 }
@@ -231,8 +268,9 @@ __global__ __launch_bounds__(TB, tune::kWtahvMinWaves) void wta_hv_kernel(const 
                 constexpr int r = TY - 1 - decltype(Q)::value;
                 if (r < ny) {
                     unsigned lu[NW];
-                    if constexpr (UNPACK1) sgm_step_c<DPL, PIN>(cvp[UNPACK1 ? r : 0], Ab, mb, lu, P1, P2, eb);
-                    else sgm_step<DPL, PIN>(cv[r].w, Ab, mb, lu, P1, P2, eb);
+                    given_m(mb, mv[1], TY - 1 - r);
+                    if constexpr (UNPACK1) sgm_step_c<DPL, PIN, MN>(cvp[UNPACK1 ? r : 0], Ab, mb, lu, P1, P2, eb);
+                    else sgm_step<DPL, PIN, MN>(cv[r].w, Ab, mb, lu, P1, P2, eb);
                     put_v(r, LD[r], Ab, lu, cv[r].w);
                 }
             });
@@ -361,7 +399,7 @@ __global__ __launch_bounds__(TB, tune::kWtahvMinWaves) void wta_hv_kernel(const 
     // the sum and the WTA per pixel
     if (!hrow) return;                                 // whole 16-lane row leaves together
     if constexpr (tune::kWtahvEarlyLoads == 0) issue_first();
-    if (hs > 0) state_from_words<DPL, PAD, PIN>(ckw[0], Aa, ma, padm);
+    if (hs > 0) state_from_words<DPL, PAD, PIN, MN>(ckw[0], Aa, ma, padm);
     else zero_state(Aa, ma);
     // L_0 of the segment's pixels, kept like phase V's L_2 (KEEP16H)
     constexpr int NKH = KEEP16H ? NP : NW;
@@ -371,17 +409,18 @@ __global__ __launch_bounds__(TB, tune::kWtahvMinWaves) void wta_hv_kernel(const 
         constexpr int i = decltype(I)::value;
         unsigned ow[NW];
         if (i < nh) {
+            given_m(ma, mh[0], i);
             if constexpr (UNPACK1) {
                 words_to_pairs<DPL>(ch[i].w, chp[i]);
-                sgm_step_c<DPL, PIN>(chp[i], Aa, ma, ow, P1, P2, ea);
+                sgm_step_c<DPL, PIN, MN>(chp[i], Aa, ma, ow, P1, P2, ea);
             } else {
-                sgm_step<DPL, PIN>(ch[i].w, Aa, ma, ow, P1, P2, ea);
+                sgm_step<DPL, PIN, MN>(ch[i].w, Aa, ma, ow, P1, P2, ea);
             }
 #pragma unroll
             for (int q = 0; q < NKH; q++) LF[i][q] = KEEP16H ? Aa[q] : ow[q];
         }
     });
-    if (hx + TY < W) state_from_words<DPL, PAD, PIN>(ckw[1], Aa, ma, padm);
+    if (hx + TY < W) state_from_words<DPL, PAD, PIN, MN>(ckw[1], Aa, ma, padm);
     else zero_state(Aa, ma);
     unsigned dres = 0u, sm = 0u, s0 = 0u;
     const bool want_sub = sub != nullptr;
@@ -395,8 +434,9 @@ __global__ __launch_bounds__(TB, tune::kWtahvMinWaves) void wta_hv_kernel(const 
         constexpr int q = decltype(Q)::value, j = TY - 1 - q, s = q % kPfVol;
         if (j < nh) {
             unsigned ow[NW];
-            if constexpr (UNPACK1) sgm_step_c<DPL, PIN>(chp[UNPACK1 ? j : 0], Aa, ma, ow, P1, P2, ea);
-            else sgm_step<DPL, PIN>(ch[j].w, Aa, ma, ow, P1, P2, ea);
+            given_m(ma, mh[1], q);
+            if constexpr (UNPACK1) sgm_step_c<DPL, PIN, MN>(chp[UNPACK1 ? j : 0], Aa, ma, ow, P1, P2, ea);
+            else sgm_step<DPL, PIN, MN>(ch[j].w, Aa, ma, ow, P1, P2, ea);
             unsigned* const vpix = vrow + j * 16 * NP;                     // this pixel's V
             unsigned S[NP];
 #pragma unroll
@@ -493,18 +533,33 @@ __global__ __launch_bounds__(TB, tune::kWtahvMinWaves) void wta_hv_kernel(const 
     }
 }
 
-// (PAIR instances exist only for the D classes whose pair route is enabled;
-// launch_wta_hv has refused pair = true for the others)
-template <int DPL, int TYL, bool PAIR>
+// (PAIR instances exist only for the D classes whose pair route is enabled,
+// minima instances only for those with tune::kPathMinima*; launch_wta_hv has
+// refused pair = true or a minima plane for the others)
+template <int DPL, int TYL, bool PAIR, bool MN>
+void wtahv_launch_mn(bool pad, dim3 grid, hipStream_t s, hipEvent_t start, hipEvent_t stop,
+                     const uint8_t* C, const uint8_t* L4, const uint8_t* CK, const uint8_t* CKV,
+                     const uint8_t* MNP, const WtaHvGeom& g, uint16_t* disp, float* sub) {
+    if (pad)
+        hipExtLaunchKernelGGL((wta_hv_kernel<DPL, TYL, true, PAIR, MN>), grid, dim3(TB), 0, s, start,
+                              stop, 0, C, L4, CK, CKV, MNP, g, disp, sub);
+    else
+        hipExtLaunchKernelGGL((wta_hv_kernel<DPL, TYL, false, PAIR, MN>), grid, dim3(TB), 0, s, start,
+                              stop, 0, C, L4, CK, CKV, MNP, g, disp, sub);
+}
+template <int DPL, int TYL, bool PAIR, bool MNEN>
 void wtahv_launch(bool pad, dim3 grid, hipStream_t s, hipEvent_t start, hipEvent_t stop,
                   const uint8_t* C, const uint8_t* L4, const uint8_t* CK, const uint8_t* CKV,
-                  const WtaHvGeom& g, uint16_t* disp, float* sub) {
-    if (pad)
-        hipExtLaunchKernelGGL((wta_hv_kernel<DPL, TYL, true, PAIR>), grid, dim3(TB), 0, s, start,
-                              stop, 0, C, L4, CK, CKV, g, disp, sub);
-    else
-        hipExtLaunchKernelGGL((wta_hv_kernel<DPL, TYL, false, PAIR>), grid, dim3(TB), 0, s, start,
-                              stop, 0, C, L4, CK, CKV, g, disp, sub);
+                  const uint8_t* MNP, const WtaHvGeom& g, uint16_t* disp, float* sub) {
+    if constexpr (MNEN) {
+        if (MNP) {
+            wtahv_launch_mn<DPL, TYL, PAIR, true>(pad, grid, s, start, stop, C, L4, CK, CKV, MNP, g,
+                                                  disp, sub);
+            return;
+        }
+    }
+    wtahv_launch_mn<DPL, TYL, PAIR, false>(pad, grid, s, start, stop, C, L4, CK, CKV, nullptr, g,
+                                           disp, sub);
 }
 
 }  // namespace
@@ -513,7 +568,8 @@ bool wta_hv_supported(int D) { return D == 64 || D == 128 || D == 192 || D == 25
 
 hipError_t launch_wta_hv(Ctx& c, const uint8_t* C, const uint8_t* L4, const uint8_t* CK,
                          const uint8_t* CKV, int W, int H, int D, int P1, int P2, int dmin,
-                         uint16_t* disp, float* sub, int dreal, int npair, bool pair) {
+                         uint16_t* disp, float* sub, int dreal, int npair, bool pair,
+                         const uint8_t* MN) {
     // D <= 128 on the strip route: all eight directions recomputed per tile
     // from checkpoints, no diagonal volume (wta_strip.hip)
     if (tune::kStripRoute != 0 && wta_strip_supported(D))
@@ -536,26 +592,30 @@ hipError_t launch_wta_hv(Ctx& c, const uint8_t* C, const uint8_t* L4, const uint
     if (npair < 1) return hipErrorInvalidValue;
     g.tiles = g.ntx * g.nty;
     const dim3 grid((unsigned)(g.tiles * npair));
-#define SVA_WTAHV(DPL_, TYL_)                                                                 \
-    wtahv_launch<DPL_, TYL_, false>(pad, grid, c.stream, t.start, t.stop, C, L4, CK, CKV, g,  \
-                                    disp, sub);                                               \
+#define SVA_WTAHV(DPL_, TYL_, MN_)                                                            \
+    wtahv_launch<DPL_, TYL_, false, (MN_) != 0>(pad, grid, c.stream, t.start, t.stop, C, L4,  \
+                                                CK, CKV, MN, g, disp, sub);                   \
     t.used = true
-#define SVA_WTAHV_P(DPL_, TYL_, EN_)                                                          \
+#define SVA_WTAHV_P(DPL_, TYL_, EN_, MN_)                                                     \
     if (pair) {                                                                               \
-        wtahv_launch<DPL_, TYL_, (EN_) != 0>(pad, grid, c.stream, t.start, t.stop, C, L4, CK, \
-                                             CKV, g, disp, sub);                              \
+        wtahv_launch<DPL_, TYL_, (EN_) != 0, (MN_) != 0>(pad, grid, c.stream, t.start,        \
+                                                         t.stop, C, L4, CK, CKV, MN, g, disp, \
+                                                         sub);                                \
         t.used = true;                                                                        \
     } else {                                                                                  \
-        SVA_WTAHV(DPL_, TYL_);                                                                \
+        SVA_WTAHV(DPL_, TYL_, MN_);                                                           \
     }
     constexpr int TYL = tune::kWtahvTileLog2, TYLW = tune::kWtahvTileLog2Wide;
     if (tg.seg_log2 != (D <= 128 ? TYL : TYLW)) return hipErrorInvalidValue;
     if (pair && (npair != 1 || !diag_pair_ok(D, P2) || tg.nvol != 4)) return hipErrorInvalidValue;
+    if (MN && (npair != 1 || !path_minima_enabled(D) || (1 << tg.seg_log2) != sgm::kMinimaSeg ||
+               tg.nvol != 4))
+        return hipErrorInvalidValue;
     switch (D) {
-        case 64: SVA_WTAHV_P(4, TYL, tune::kDiagPair4); break;
-        case 128: SVA_WTAHV_P(8, TYL, tune::kDiagPair8); break;
-        case 192: SVA_WTAHV_P(12, TYLW, tune::kDiagPair12); break;
-        case 256: SVA_WTAHV_P(16, TYLW, tune::kDiagPair16); break;
+        case 64: SVA_WTAHV_P(4, TYL, tune::kDiagPair4, tune::kPathMinima4); break;
+        case 128: SVA_WTAHV_P(8, TYL, tune::kDiagPair8, tune::kPathMinima8); break;
+        case 192: SVA_WTAHV_P(12, TYLW, tune::kDiagPair12, tune::kPathMinima12); break;
+        case 256: SVA_WTAHV_P(16, TYLW, tune::kDiagPair16, tune::kPathMinima16); break;
         default: return hipErrorInvalidValue;
     }
 #undef SVA_WTAHV_P
