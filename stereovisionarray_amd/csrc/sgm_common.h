@@ -176,65 +176,50 @@ __device__ __forceinline__ unsigned lane_min_u16(const unsigned (&A)[NP]) {
     return mf.x < mf.y ? mf.x : mf.y;
 }
 
-// ---- pair layout of the recurrence state (tune::kSplitPairs, §4.14) -------
-// Lane k holds its DPL disparities as NP = DPL/2 packed u16 pairs.  Local
-// disparity e (0 <= e < DPL) sits in pair pair_of(e), half half_of(e);
-// pair_d(j, h) is the inverse.  Split: pair j = (e = j, e = j + NP).
-// Adjacent: pair j = (2j, 2j + 1).
-template <int DPL> __host__ __device__ constexpr int pair_d(int j, int h) {
-    return tune::kSplitPairs ? j + h * (DPL / 2) : 2 * j + h;
-}
-template <int DPL> __host__ __device__ constexpr int pair_of(int e) {
-    return tune::kSplitPairs ? e % (DPL / 2) : e >> 1;
-}
-template <int DPL> __host__ __device__ constexpr int half_of(int e) {
-    return tune::kSplitPairs ? e / (DPL / 2) : e & 1;
-}
+// ---- pair layout of the recurrence state ----------------
+// Lane k holds its DPL disparities as NP = DPL/2 packed u16 pairs, split:
+// pair j = (e = j, e = j + NP) of the lane's local disparities 0 <= e < DPL,
+// so a pair's d-1 / d+1 neighbours are whole registers.  Local disparity e
+// sits in pair pair_of(e), half half_of(e); pair_d(j, h) is the inverse.
+// HBM formats (C, L_r volumes, checkpoints) stay in d order.
+template <int DPL> __host__ __device__ constexpr int pair_d(int j, int h) { return j + h * (DPL / 2); }
+template <int DPL> __host__ __device__ constexpr int pair_of(int e) { return e % (DPL / 2); }
+template <int DPL> __host__ __device__ constexpr int half_of(int e) { return e / (DPL / 2); }
 
 // d-ordered u8 words (C, L_r volumes, checkpoints) -> state-layout pairs:
-// one v_perm per pair in both layouts.
+// one v_perm per pair.
 template <int DPL>
 __device__ __forceinline__ void words_to_pairs(const unsigned (&w)[DPL / 4], unsigned (&A)[DPL / 2]) {
-    constexpr int NW = DPL / 4, NP = DPL / 2;
-    if constexpr (tune::kSplitPairs != 0) {
+    constexpr int NP = DPL / 2;
 #pragma unroll
-        for (int j = 0; j < NP; j++) {
-            constexpr unsigned Z = 0x0cu;     // v_perm selector: zero byte
-            const int el = j, eh = j + NP;
-            const unsigned sel = (unsigned)(el & 3) | (Z << 8) | ((4u + (unsigned)(eh & 3)) << 16) | (Z << 24);
-            A[j] = __builtin_amdgcn_perm(w[eh >> 2], w[el >> 2], sel);
-        }
-    } else {
-#pragma unroll
-        for (int q = 0; q < NW; q++) unpack4(w[q], A[2 * q], A[2 * q + 1]);
+    for (int j = 0; j < NP; j++) {
+        constexpr unsigned Z = 0x0cu;     // v_perm selector: zero byte
+        const int el = j, eh = j + NP;
+        const unsigned sel = (unsigned)(el & 3) | (Z << 8) | ((4u + (unsigned)(eh & 3)) << 16) | (Z << 24);
+        A[j] = __builtin_amdgcn_perm(w[eh >> 2], w[el >> 2], sel);
     }
 }
 
-// State-layout pairs (values < 256) -> d-ordered u8 words.  Split: pairs
-// (2i, 2i + 1) first merge into T_i = (A_2i.lo, A_2i+1.lo, A_2i.hi,
-// A_2i+1.hi) bytes, then each word takes two byte pairs of two T's.
+// State-layout pairs (values < 256) -> d-ordered u8 words: pairs (2i, 2i + 1)
+// first merge into T_i = (A_2i.lo, A_2i+1.lo, A_2i.hi, A_2i+1.hi) bytes, then
+// each word takes two byte pairs of two T's.
 template <int DPL>
 __device__ __forceinline__ void pairs_to_words(const unsigned (&A)[DPL / 2], unsigned (&ow)[DPL / 4]) {
     constexpr int NW = DPL / 4, NP = DPL / 2;
-    if constexpr (tune::kSplitPairs != 0) {
-        unsigned T[NP / 2];
+    unsigned T[NP / 2];
 #pragma unroll
-        for (int i = 0; i < NP / 2; i++) T[i] = __builtin_amdgcn_perm(A[2 * i + 1], A[2 * i], 0x06020400u);
-        if constexpr (NP == 2) {
-            ow[0] = T[0];                     // (d0, d2), (d1, d3) -> d0 d1 d2 d3
-        } else {
-#pragma unroll
-            for (int q = 0; q < NW; q++) {
-                const int e0 = 4 * q, e2 = 4 * q + 2;
-                const int a = (e0 % NP) / 2, ha = e0 / NP, b = (e2 % NP) / 2, hb = e2 / NP;
-                const unsigned sel = (unsigned)(2 * ha) | ((unsigned)(2 * ha + 1) << 8) |
-                                     ((unsigned)(4 + 2 * hb) << 16) | ((unsigned)(5 + 2 * hb) << 24);
-                ow[q] = __builtin_amdgcn_perm(T[b], T[a], sel);
-            }
-        }
+    for (int i = 0; i < NP / 2; i++) T[i] = __builtin_amdgcn_perm(A[2 * i + 1], A[2 * i], 0x06020400u);
+    if constexpr (NP == 2) {
+        ow[0] = T[0];                     // (d0, d2), (d1, d3) -> d0 d1 d2 d3
     } else {
 #pragma unroll
-        for (int w = 0; w < NW; w++) ow[w] = pack4(A[2 * w], A[2 * w + 1]);
+        for (int q = 0; q < NW; q++) {
+            const int e0 = 4 * q, e2 = 4 * q + 2;
+            const int a = (e0 % NP) / 2, ha = e0 / NP, b = (e2 % NP) / 2, hb = e2 / NP;
+            const unsigned sel = (unsigned)(2 * ha) | ((unsigned)(2 * ha + 1) << 8) |
+                                 ((unsigned)(4 + 2 * hb) << 16) | ((unsigned)(5 + 2 * hb) << 24);
+            ow[q] = __builtin_amdgcn_perm(T[b], T[a], sel);
+        }
     }
 }
 
@@ -262,69 +247,40 @@ __device__ __forceinline__ void sgm_step_c(const unsigned (&c)[DPL / 2], unsigne
                                            unsigned P2, Edges& e) {
     constexpr int NP = DPL / 2;
     // neighbours: X = lane k-1's last pair, Y = lane k+1's first pair (its
-    // high half holds L(d0 - 1) and its low half L(d0 + DPL) in both layouts)
+    // high half holds L(d0 - 1) and its low half L(d0 + DPL))
     e.X = row_shr1(A[NP - 1], e.X);
     e.Y = row_shl1(A[0], e.Y);
     const unsigned X = e.X, Y = e.Y;
-    // lo[j] / hi[j]: the pairs whose min is pair j's min(A(d-1), A(d+1))
+    // lo[j] / hi[j]: the pairs whose min is pair j's min(A(d-1), A(d+1)).
+    // Pair j = (j, j + NP): its d-1 pair is pair j-1 and its d+1 pair is pair
+    // j+1, whole registers, except (X.hi, A[NP-1].lo) for j = 0 and
+    // (A[0].hi, Y.lo) for j = NP-1
     unsigned lo[NP], hi[NP];
-    if constexpr (tune::kSplitPairs != 0) {
-        // pair j = (j, j + NP): its d-1 pair is pair j-1 and its d+1 pair is
-        // pair j+1, whole registers, except (X.hi, A[NP-1].lo) for j = 0 and
-        // (A[0].hi, Y.lo) for j = NP-1
 #pragma unroll
-        for (int j = 0; j < NP; j++) {
-            lo[j] = j == 0 ? __builtin_amdgcn_alignbit(A[NP - 1], X, 16) : A[j - 1];
-            hi[j] = j == NP - 1 ? __builtin_amdgcn_alignbit(Y, A[0], 16) : A[j + 1];
-        }
-    } else {
-        // pair j = (2j, 2j+1): d-1 is (A[j-1].hi, A[j].lo), d+1 the next one
-        unsigned M[NP];
-        M[0] = __builtin_amdgcn_alignbit(A[0], X, 16);
-#pragma unroll
-        for (int j = 1; j < NP; j++) M[j] = __builtin_amdgcn_alignbit(A[j], A[j - 1], 16);
-        const unsigned Qlast = __builtin_amdgcn_alignbit(Y, A[NP - 1], 16);
-#pragma unroll
-        for (int j = 0; j < NP; j++) {
-            lo[j] = M[j];
-            hi[j] = j < NP - 1 ? M[j + 1] : Qlast;
-        }
+    for (int j = 0; j < NP; j++) {
+        lo[j] = j == 0 ? __builtin_amdgcn_alignbit(A[NP - 1], X, 16) : A[j - 1];
+        hi[j] = j == NP - 1 ? __builtin_amdgcn_alignbit(Y, A[0], 16) : A[j + 1];
     }
     // K = -(m * 0x10001) in one v_mul_i32_i24 (m < 2^10; the literal's low 24
     // bits are -65537), and m + P2 in both halves = P2 * 0x10001 - K: two VALU
     // where m | m << 16, its negation and the sum took three plus a copy of P2
-    unsigned K, mP2;
+    unsigned K;
     asm("v_mul_i32_i24_e32 %0, 0xfffeffff, %1" : "=v"(K) : "v"(m));
-    if constexpr (tune::kStepMadP2 != 0) {
-        // m + P2 in both halves straight from m (v_mad_u32_u24: m * 0x10001 +
-        // P2 * 0x10001, beside K instead of after it): one dependent
-        // instruction less on the step's critical path m -> min3 -> add3
-        // (asm: in plain C the compiler splits m * 0x10001 into a shift-add;
-        // here it re-materialises the uniform P2 * 0x10001 with one v_mov
-        // per step, off the critical path)
-        asm("v_mad_u32_u24 %0, %1, %2, %3" : "=&v"(mP2) : "v"(m), "s"(0x10001u), "v"(P2 * 0x10001u));
-    } else {
-        mP2 = P2 * 0x10001u - K;
-    }
+    const unsigned mP2 = P2 * 0x10001u - K;
     // Stage-major over the NP independent pairs, and a min TREE below: each
     // packed op's result is consumed one pair later, not by the next
     // instruction (gfx950 puts an s_nop between dependent VOP3P ops).
     u16x2 t[NP];
 #pragma unroll
     for (int j = 0; j < NP; j++) t[j] = vmin2(as_v2(lo[j]), as_v2(hi[j]));
+    // + P1 in both halves as ONE 32-bit add (VOP2, full issue rate; the packed
+    // v_pk_add_u16 is a 64-bit VOP3P encoding that issues at half rate,
+    // profiles/r06_v1/microbench_valu.txt): t <= 448 + 193 per half (INF never
+    // reaches t, see min3_u16x2), so the low half never carries
     unsigned tp[NP];
-    if constexpr (tune::kStepAddU32 != 0) {
-        // + P1 in both halves as ONE 32-bit add (VOP2, full issue rate; the
-        // packed v_pk_add_u16 is a 64-bit VOP3P encoding that issues at half
-        // rate, profiles/r06_v1/microbench_valu.txt): t <= 448 + 193 per half
-        // (INF never reaches t, see min3_u16x2), so the low half never carries
-        const unsigned P1x2 = P1 * 0x10001u;
+    const unsigned P1x2 = P1 * 0x10001u;
 #pragma unroll
-        for (int j = 0; j < NP; j++) tp[j] = as_u32(t[j]) + P1x2;
-    } else {
-#pragma unroll
-        for (int j = 0; j < NP; j++) tp[j] = as_u32(t[j] + splat2(P1));
-    }
+    for (int j = 0; j < NP; j++) tp[j] = as_u32(t[j]) + P1x2;
 #pragma unroll
     for (int j = 0; j < NP; j++) A[j] = add3(min3_u16x2(tp[j], A[j], mP2), c[j], K);
     pairs_to_words<DPL>(A, ow);
@@ -393,10 +349,10 @@ template <int DPL> constexpr int pf_v() {
 
 
 // One path line over a materialised cost volume C.  CKPT
-// 1 (horizontal lines) / 2 (vertical lines) / 3 (down-diagonal lines): store
-// checkpoints every 2^SL pixels (rows for 2 and 3) to rCK instead of the full
-// L_r line to rL (SL is a template parameter: a runtime segment test cost the
-// latency-bound lines of small frames 20 %).
+// 1 (horizontal lines) / 2 (vertical lines): store checkpoints every 2^SL
+// pixels (columns / rows) to rCK instead of the full L_r line to rL (SL is a
+// template parameter: a runtime segment test cost the latency-bound lines of
+// small frames 20 %).
 // MN (CKPT 1 and 2, path minima, §4.17): the line also stores each segment's
 // entering minima to rMN ([H][ns][8] or [nsy][W][8], this direction's plane).
 template <int DPL, bool DIAG, int PF, int CKPT = 0, int SL = 0, bool MN = false>
@@ -559,19 +515,6 @@ __device__ __forceinline__ void path_line(rsrc_t rC, rsrc_t rL, const PathGeom& 
             if (__builtin_expect(hit, 0))   // default policy (tune::kCkptStoreAux): the WTA kernel reads these back soon
                 bstore<NW, tune::kCkptStoreAux>(rCK, ((unsigned)(y0 * g.ns + (x >> SL)) * (unsigned)D +
                                          (unsigned)(k * DPL)), ow);
-        } else if constexpr (CKPT == 3) {
-            // diagonal line with row checkpoints: a down
-            // line (ry = +1) keeps the last row of every row segment but the
-            // image's last, an up line (ry = -1) the first row of every
-            // segment but the first, in the row checkpoint plane [nsy][W][D]
-            // at this pixel's column: the pixel's volume offset minus the
-            // rows the plane does not hold
-            const int y = ry > 0 ? ts : H - 1 - ts;
-            constexpr int SEG = 1 << SL;
-            const bool hit = ry > 0 ? (((y + 1) & (SEG - 1)) == 0 && y + 1 < H)
-                                    : ((y & (SEG - 1)) == 0 && y > 0);
-            if (__builtin_expect(hit, 0))
-                bstore<NW, tune::kCkptStoreAux>(rCK, cc.off - (unsigned)(y - (y >> SL)) * WD, ow);
         } else if constexpr (CKPT == 2) {
             // vertical line x0: direction 2 (down) keeps the last row of every
             // row segment but the column's last, direction 3 (up) the first row
@@ -666,19 +609,8 @@ __device__ __forceinline__ void state_from_words(const Words<DPL / 4>& w, unsign
 #pragma unroll
         for (int j = 0; j < NP; j++) A[j] |= padm[j] & 0x00ff00ffu;   // A < 256: OR = max
     }
-    if constexpr (GIVEN_M) {
-    } else if constexpr (tune::kStateMinTree) {
-        m = row_min_u32<PIN>(lane_min_u16<NP>(A));
-    } else {
-        unsigned mm = 0xffffffffu;
-#pragma unroll
-        for (int j = 0; j < NP; j++) {
-            const unsigned lo = A[j] & 0xffffu, hi = A[j] >> 16;
-            mm = mm < lo ? mm : lo;
-            mm = mm < hi ? mm : hi;
-        }
-        m = row_min_u32<PIN>(mm);
-    }
+    // (the packed-u16 min tree of the recurrence step)
+    if constexpr (!GIVEN_M) m = row_min_u32<PIN>(lane_min_u16<NP>(A));
 }
 template <int DPL, bool PAD, bool PIN = false, bool GIVEN_M = false>
 __device__ __forceinline__ void load_state(rsrc_t r, unsigned off, unsigned (&A)[DPL / 2],

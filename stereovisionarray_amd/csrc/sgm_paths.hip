@@ -32,10 +32,7 @@
 //      slots 0..3); horizontal lines store checkpoints every seg columns
 //      ([2][H][nsx][D]) and vertical lines every seg rows ([2][nsy][W][D];
 //      seg = 2^tile_geom().seg_log2), and wta_hv.hip recomputes those four
-//      per tile: 8 C reads + 4 L writes.  (The measured §4.11 experiment,
-//      tune::kTileDiagDown / kTileDiagUp = 1, also recomputes a diagonal pair
-//      per tile from extra row-checkpoint planes; both constants are 0 in the
-//      product.)
+//      per tile: 8 C reads + 4 L writes.
 //      The pair route (sgm_paths_kernel<DPL, true>) is mode
 //      2 with the four diagonals as pair lines: two u8 pair-sum volumes
 //      [2][H][W][D] instead of four L_r volumes.  A pair line takes two DPP
@@ -155,7 +152,6 @@ __global__ __launch_bounds__(PATH_BLOCK) void sgm_paths_kernel(const uint8_t* __
     const rsrc_t rC = make_rsrc(C, g.vol);
     // the tile pipeline's checkpoint segment (§4.9), rows and columns
     constexpr int SL = DPL <= 8 ? tune::kWtahvTileLog2 : tune::kWtahvTileLog2Wide;
-    constexpr bool DOWN = diag_ckpt_down(DPL), UP = diag_ckpt_up(DPL);
     // this direction's minima plane (directions 0..3 of an MN launch)
     const size_t mnh = (size_t)g.H * g.ns * kMinimaSeg, mnv = (size_t)g.nsy * g.W * kMinimaSeg;
     const rsrc_t rMN = !MN || r >= 4 ? rC
@@ -174,29 +170,19 @@ __global__ __launch_bounds__(PATH_BLOCK) void sgm_paths_kernel(const uint8_t* __
             const rsrc_t rCK = make_rsrc(CK + (size_t)r * g.ckvol, g.ckvol);
             path_line<DPL, false, pf_h<DPL>(), 1, SL, MN>(rC, rC, g, rx, ry, line, k, rCK, rMN);
         }
-    } else if (r >= 4 && g.ckpt && (ry > 0 ? DOWN : UP)) {
-        // tile pipeline, diagonals recomputed per tile: row
-        // checkpoints only, in the vertical checkpoint block after the two
-        // vertical planes: the down pair (4, 6), then the up pair (5, 7)
-        const int plane = ry > 0 ? 2 + (r == 4 ? 0 : 1) : 2 + (DOWN ? 2 : 0) + (r == 5 ? 0 : 1);
-        const rsrc_t rCK = make_rsrc(CKV + (size_t)plane * g.ckvvol, g.ckvvol);
-        path_line<DPL, true, pf_v<DPL>(), 3, SL>(rC, rC, g, rx, ry, line, k, rCK, rCK);
     } else if (r >= 4) {
         // volume slot: every direction (8 volumes), or the tile pipeline's
-        // diagonals that stay volumes, in direction order
-        const int slot = !g.ckpt ? r
-                       : DOWN ? (r == 5 ? 0 : 1)          // 5, 7 (UP is then off here)
-                       : UP ? (r == 4 ? 0 : 1)            // 4, 6
-                       : r - 4;
+        // four diagonals in direction order
+        const int slot = !g.ckpt ? r : r - 4;
         const rsrc_t rL = make_rsrc(L8 + (size_t)slot * g.vol, g.vol);
         path_line<DPL, true, pf_v<DPL>()>(rC, rL, g, rx, ry, line, k, rL, rL);
-    } else if (r >= 2 && g.ckpt) {
+    } else if (const bool tile = g.ckpt != 0; r >= 2 && tile) {   // (tile: checkpoint lines)
         const rsrc_t rCK = make_rsrc(CKV + (size_t)(r - 2) * g.ckvvol, g.ckvvol);
         path_line<DPL, false, pf_v<DPL>(), 2, SL, MN>(rC, rC, g, rx, ry, line, k, rCK, rMN);
     } else if (r >= 2) {
         const rsrc_t rL = make_rsrc(L8 + (size_t)r * g.vol, g.vol);
         path_line<DPL, false, pf_v<DPL>()>(rC, rL, g, rx, ry, line, k, rL, rL);
-    } else if (g.ckpt) {
+    } else if (tile) {
         const rsrc_t rCK = make_rsrc(CK + (size_t)r * g.ckvol, g.ckvol);
         path_line<DPL, false, pf_h<DPL>(), 1, SL, MN>(rC, rC, g, rx, ry, line, k, rCK, rMN);
     } else {
@@ -248,10 +234,6 @@ TileGeom tile_geom(int W, int H, int D) {
     t.nsx = (W + seg - 1) >> t.seg_log2;
     t.hck_bytes = 2 * (size_t)H * t.nsx * D;
     t.vck_bytes = 2 * (size_t)t.nty * W * D;
-    const int dpl = D / 16;
-    const int ndp = (diag_ckpt_down(dpl) ? 2 : 0) + (diag_ckpt_up(dpl) ? 2 : 0);
-    t.dck_bytes = (size_t)ndp / 2 * t.vck_bytes;   // one plane per recomputed diagonal
-    t.nvol = 4 - ndp;
     t.hmn_bytes = 2 * (size_t)H * t.nsx * sgm::kMinimaSeg;
     t.vmn_bytes = 2 * (size_t)t.nty * W * sgm::kMinimaSeg;
     return t;
@@ -288,13 +270,12 @@ hipError_t launch_paths(Ctx& c, const uint8_t* C, int W, int H, int D, int P1, i
     if (npair < 1 || (npair > 1 && !CK)) return hipErrorInvalidValue;
     g.npair = npair;
     g.cstr = g.vol;
-    g.lstr = (size_t)tg.nvol * g.vol;
+    g.lstr = (size_t)kDiagVolumes * g.vol;
     g.ckstr = tg.hck_bytes;
-    g.ckvstr = tg.vck_bytes + tg.dck_bytes;
+    g.ckvstr = tg.vck_bytes;
     // the pair route: one frame of the tile pipeline, u8 pair sums (2 * P2 <= 255),
     // its two diagonal planes of CKV (pair_layout) taken by the caller
-    if (pair && (!CK || npair != 1 || 2 * P2 > 255 || !diag_pair_enabled(D) ||
-                 tile_geom(W, H, D).nvol != 4))
+    if (pair && (!CK || npair != 1 || 2 * P2 > 255 || !diag_pair_enabled(D)))
         return hipErrorInvalidValue;
     g.pair = pair ? 1 : 0;
     // path minima: one frame of the tile pipeline, 8-pixel segments

@@ -180,10 +180,10 @@ size_t pair_ckpt_bytes(const TileGeom& tg) { return tg.hck_bytes + tg.vck_bytes 
 // the horizontal and vertical lines follow them in the
 // context's checkpoint allocation where this D has them.
 size_t frame_ckpt_bytes(const TileGeom& tg, bool pair) {
-    return pair ? pair_ckpt_bytes(tg) : tg.hck_bytes + tg.vck_bytes + tg.dck_bytes;
+    return pair ? pair_ckpt_bytes(tg) : tg.hck_bytes + tg.vck_bytes;
 }
 size_t frame_minima_bytes(const TileGeom& tg, int Dp) {
-    return tg.nvol == 4 && path_minima_enabled(Dp) ? tg.hmn_bytes + tg.vmn_bytes : 0;
+    return path_minima_enabled(Dp) ? tg.hmn_bytes + tg.vmn_bytes : 0;
 }
 
 int paths_wta(Ctx* c, const uint8_t* C, int W, int H, const sva_sgm_params* p, int Dp,
@@ -198,8 +198,8 @@ int paths_wta(Ctx* c, const uint8_t* C, int W, int H, const sva_sgm_params* p, i
     // today's four volumes.
     const long long minpx = c->dbg_pair_min_pixels >= 0 ? (long long)c->dbg_pair_min_pixels
                                                         : tune::kDiagPairMinPixels;
-    const bool pair = tg.nvol == 4 && diag_pair_ok(Dp, p->P2) && (long long)W * H >= minpx;
-    SVA_HIP(c, c->paths.ensure(nv * (pair ? 2 : tg.nvol)), "path workspace");
+    const bool pair = diag_pair_ok(Dp, p->P2) && (long long)W * H >= minpx;
+    SVA_HIP(c, c->paths.ensure(nv * (pair ? 2 : kDiagVolumes)), "path workspace");
     const size_t ckb = frame_ckpt_bytes(tg, pair), mnb = frame_minima_bytes(tg, Dp);
     SVA_HIP(c, c->ckpt.ensure(ckb + mnb), "checkpoint workspace");
     uint8_t* L4 = (uint8_t*)c->paths.ptr;
@@ -224,10 +224,10 @@ sva_tile_layout tile_layout(int W, int H, int D) {
     l.nsx = tg.nsx;
     l.nsy = tg.nty;
     l.cost_bytes = (size_t)W * H * (size_t)D;
-    l.diag_volumes = tg.nvol;
-    l.diag_bytes = (size_t)tg.nvol * l.cost_bytes;
+    l.diag_volumes = kDiagVolumes;
+    l.diag_bytes = (size_t)kDiagVolumes * l.cost_bytes;
     l.hckpt_bytes = tg.hck_bytes;
-    l.vckpt_bytes = tg.vck_bytes + tg.dck_bytes;
+    l.vckpt_bytes = tg.vck_bytes;
     return l;
 }
 
@@ -242,11 +242,11 @@ int check_tile_buffers(Ctx* c, int W, int H, int D, const void* C, size_t C_byte
         return fail(c, SVA_ERR_INVALID_ARG, "null stage buffer");
     if (C_bytes < l.cost_bytes) return fail(c, SVA_ERR_INVALID_ARG, "cost buffer smaller than [H][W][D]");
     if (diag_bytes < l.diag_bytes)
-        return fail(c, SVA_ERR_INVALID_ARG, "diagonal volume buffer smaller than [nvol][H][W][D]");
+        return fail(c, SVA_ERR_INVALID_ARG, "diagonal volume buffer smaller than [4][H][W][D]");
     if (hck_bytes < l.hckpt_bytes)
         return fail(c, SVA_ERR_INVALID_ARG, "horizontal checkpoint buffer smaller than [2][H][nsx][D]");
     if (vck_bytes < l.vckpt_bytes)
-        return fail(c, SVA_ERR_INVALID_ARG, "row checkpoint buffer smaller than [np][nsy][W][D]");
+        return fail(c, SVA_ERR_INVALID_ARG, "row checkpoint buffer smaller than [2][nsy][W][D]");
     return SVA_OK;
 }
 
@@ -338,12 +338,12 @@ int run_sgm_batch(Ctx* c, const sva_pair_d* jobs, int n, int W, int H, size_t pi
     const int Dp = padded_D(p->D);
     const size_t np = (size_t)W * H, nv = np * (size_t)Dp;
     const TileGeom tg = tile_geom(W, H, Dp);
-    const size_t ckb = tg.hck_bytes + tg.vck_bytes + tg.dck_bytes;
+    const size_t ckb = tg.hck_bytes + tg.vck_bytes;
     const int sb = tune::kBatchSubFrames > 0 ? std::min(n, tune::kBatchSubFrames) : n;
     const int nsub = (n + sb - 1) / sb;
     SVA_HIP(c, c->cost.ensure(nv * n), "cost workspace");
     // the aggregation workspaces serve one sub-batch at a time (same stream)
-    SVA_HIP(c, c->paths.ensure(nv * tg.nvol * sb), "path workspace");
+    SVA_HIP(c, c->paths.ensure(nv * kDiagVolumes * sb), "path workspace");
     SVA_HIP(c, c->ckpt.ensure(ckb * sb), "checkpoint workspace");
     uint8_t* C = (uint8_t*)c->cost.ptr;
     const int ns = std::min(n, tune::kBatchCostStreams);
@@ -649,8 +649,7 @@ int time_stage_set(Ctx* c, int W, int H, int D, int64_t* ns) {
     for (int r = 0; r < 4 && e == hipSuccess; r++) {
         e = hipEventRecord(a, c->stream);
         // (the route a frame with the default penalties takes)
-        const bool pair = tg.nvol == 4 && diag_pair_ok(D, 120) &&
-                          (long long)W * H >= tune::kDiagPairMinPixels;
+        const bool pair = diag_pair_ok(D, 120) && (long long)W * H >= tune::kDiagPairMinPixels;
         if (e == hipSuccess)
             e = launch_paths(*c, C, W, H, D, 10, 120, L4, CK, CK + tg.hck_bytes, 1, pair, 0,
                              frame_minima_bytes(tg, D) ? CK + frame_ckpt_bytes(tg, pair) : nullptr);
@@ -749,15 +748,14 @@ int sva_reserve(void* ctx, int W, int H, int D) {
     const TileGeom tg = tile_geom(W, H, D);
     // (the larger of the two diagonal routes' layouts: four volumes, and the
     // pair route's two more row-checkpoint planes)
-    const size_t ckb = frame_ckpt_bytes(tg, tg.nvol == 4 && diag_pair_enabled(D)) +
-                       frame_minima_bytes(tg, D);
-    SVA_HIP(c, c->paths.ensure(nv * tg.nvol), "reserve");
+    const size_t ckb = frame_ckpt_bytes(tg, diag_pair_enabled(D)) + frame_minima_bytes(tg, D);
+    SVA_HIP(c, c->paths.ensure(nv * kDiagVolumes), "reserve");
     SVA_HIP(c, c->ckpt.ensure(ckb), "reserve");
     // (once per allocation: a repeated reserve of a size the buffers already
     // hold keeps the set the last check chose)
     const int trials = c->placement_trials > 0 ? c->placement_trials : tune::kPlacementTrials;
     if (trials > 1 && wta_hv_supported(D) && nv < ((size_t)1 << 32) &&
-        nv + nv * tg.nvol + ckb >= tune::kPlacementMinBytes && c->paths.ptr != c->placement_paths)
+        nv + nv * kDiagVolumes + ckb >= tune::kPlacementMinBytes && c->paths.ptr != c->placement_paths)
         return place_stage_buffers(c, W, H, D, trials);
     return SVA_OK;
 }
@@ -895,8 +893,7 @@ int sva_disparity_sgm_batch_d(void* ctx, const sva_pair_d* jobs, int n, int W, i
     // under tune::kBatchMaxBytes
     const int Dp = padded_D(p0->D);
     const TileGeom tg = tile_geom(W, H, Dp);
-    const size_t per = (size_t)W * H * (size_t)Dp * (1 + tg.nvol) + tg.hck_bytes + tg.vck_bytes +
-                       tg.dck_bytes;
+    const size_t per = (size_t)W * H * (size_t)Dp * (1 + kDiagVolumes) + tg.hck_bytes + tg.vck_bytes;
     int chunk = tune::kBatchMaxPairs;
     while (chunk > 1 && per * (size_t)chunk > tune::kBatchMaxBytes) chunk--;
     const size_t np = (size_t)W * H;

@@ -12,9 +12,6 @@ typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
 
 __device__ __forceinline__ unsigned as_u32(u16x2 v) { return __builtin_bit_cast(unsigned, v); }
 __device__ __forceinline__ u16x2 as_v2(unsigned v) { return __builtin_bit_cast(u16x2, v); }
-__device__ __forceinline__ u16x2 splat2(unsigned v) {
-    return (u16x2){(unsigned short)v, (unsigned short)v};
-}
 __device__ __forceinline__ u16x2 vmin2(u16x2 a, u16x2 b) { return __builtin_elementwise_min(a, b); }
 
 // DPP control words (GFX9 encoding).
@@ -60,11 +57,6 @@ __device__ __forceinline__ void unpack4(unsigned w, unsigned& p01, unsigned& p23
     // v_perm_b32 selector: byte k of result = sel byte; 0x0c = zero.
     p01 = __builtin_amdgcn_perm(0u, w, 0x0c010c00u);
     p23 = __builtin_amdgcn_perm(0u, w, 0x0c030c02u);
-}
-// Pack two u16x2 pairs (values < 256) into one dword of 4 u8.
-__device__ __forceinline__ unsigned pack4(unsigned p01, unsigned p23) {
-    // result bytes: [p01.b0, p01.b2, p23.b0, p23.b2]; src0 = p23 (bytes 4..7), src1 = p01 (0..3)
-    return __builtin_amdgcn_perm(p23, p01, 0x06040200u);
 }
 
 // Disparity padding: a frame with D not in {64,128,192,256}

@@ -173,12 +173,11 @@ hipError_t launch_census_cost2(Ctx& c, const uint8_t* left, const uint8_t* right
 hipError_t launch_cost(Ctx& c, const uint64_t* cl, const uint64_t* cr, int W, int H, int D,
                        int dmin, int dir, uint8_t* C, int dreal = 0);
 // sgm_paths.hip -- all 8 directions in one launch.  CK == CKV == nullptr:
-// L8 = [8][H][W][D] u8.  CK and CKV set (the tile pipeline, DESIGN.md §4.9,
-// §4.11): L8 = [nvol][H][W][D] (directions 5, 7, or 4..7), CK = [2][H][nsx][D]
-// and CKV = the vertical then the down-diagonal row checkpoints,
-// vck_bytes + dck_bytes (tile_geom below).  npair > 1 (tile pipeline only): a
-// batch of frames in one launch, each buffer holding npair such planes back
-// to back.
+// L8 = [8][H][W][D] u8.  CK and CKV set (the tile pipeline):
+// L8 = [4][H][W][D] (directions 4..7), CK = [2][H][nsx][D] and CKV =
+// [2][nty][W][D], the vertical checkpoints (tile_geom below).  npair > 1 (tile
+// pipeline only): a batch of frames in one launch, each buffer holding npair
+// such planes back to back.
 // pair (one frame of the tile pipeline, diag_pair_ok): the pair route of
 // DESIGN.md §4.15, L8 = [2][H][W][D] pair sums (4+5, 6+7) and CKV = the two
 // vertical planes plus two wave-private row-checkpoint planes (pair_layout);
@@ -198,33 +197,17 @@ inline bool diag_pair_ok(int D, int P2) { return diag_pair_enabled(D) && 2 * P2 
 // Tile pipeline geometry: tiles of 16 columns x seg rows (seg = 2^seg_log2),
 // checkpoints every seg columns (horizontal lines) and every seg rows
 // (vertical lines).
+constexpr int kDiagVolumes = 4;   // [4][H][W][D]: the diagonal directions 4..7
 struct TileGeom {
     int seg_log2;
     int ntx, nty;             // tiles per row / per column (nty = vertical segments)
     int nsx;                  // horizontal segments per row
     size_t hck_bytes;         // [2][H][nsx][D]
     size_t vck_bytes;         // [2][nty][W][D]: directions 2, 3
-    size_t dck_bytes;         // [2][nty][W][D]: directions 4, 6 (0 when they are volumes)
-    int nvol;                 // diagonal volumes the path kernel writes: 2 (5, 7) or 4
     size_t hmn_bytes;         // [2][H][nsx][8]: entering minima of directions 0, 1 (§4.17)
     size_t vmn_bytes;         // [2][nty][W][8]: of directions 2, 3
 };
 TileGeom tile_geom(int W, int H, int D);
-// Which diagonal pairs the path kernel leaves as row checkpoints instead of
-// volumes, per lane width DPL = D / 16: all four on the strip route (D <= 128,
-// tune::kStripRoute), else the §4.11 experiment's switches.
-constexpr bool diag_ckpt_down(int dpl) {
-    return (tune::kStripRoute != 0 && dpl <= 8) || tune::kTileDiagDown != 0;
-}
-constexpr bool diag_ckpt_up(int dpl) {
-    return (tune::kStripRoute != 0 && dpl <= 8) || tune::kTileDiagUp != 0;
-}
-// wta_strip.hip -- the strip route's final kernel (all eight directions per
-// tile from the checkpoints of launch_paths at D <= 128, no volume)
-bool wta_strip_supported(int D);
-hipError_t launch_wta_strip(Ctx& c, const uint8_t* C, const uint8_t* CK, const uint8_t* CKV, int W,
-                            int H, int D, int P1, int P2, int dmin, uint16_t* disp, float* sub,
-                            int dreal = 0, int npair = 1);
 bool paths_supported(int D);
 // Native volume width of a frame with D disparities: 64, 128, 192 or 256
 // (the smallest >= D), 0 when D is outside 1..256.

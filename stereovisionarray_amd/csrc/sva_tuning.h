@@ -13,31 +13,6 @@ namespace sva {
 namespace tune {
 
 // ---- sgm_paths.hip / sgm_common.h ------------------------
-// The recurrence step's "+ P1" as one v_add_u32 per pair (1) instead of
-// v_pk_add_u16 (0): VOP2 issues at ~2x the rate of VOP3P on gfx950
-// (profiles/r06_v1/microbench_valu.txt).
-constexpr int kStepAddU32 = 1;
-// Pair layout of the recurrence state: pair j of lane k
-// holds disparities (k*DPL + j, k*DPL + j + DPL/2) (1, "split") instead of
-// (k*DPL + 2j, k*DPL + 2j + 1) (0).  Split pairs have their d-1 / d+1
-// neighbours in whole registers, so the step needs 2 v_alignbit instead of
-// DPL/2 + 1; packing a u8 volume word costs 2 v_perm instead of 1.  HBM
-// formats (C, L_r volumes, checkpoints) stay in d order either way.  Static
-// VALU of wta_hv D=64/128/192/256 -3.3/-5.9/-6.8/-7.6 %; in-process A/B,
-// frame ms split / adjacent (profiles/r06_v8/, two runs): 1080p D=128 0.8817
-// / 0.8828 and 0.8772 / 0.8792, D=64 0.5082 / 0.5175 and 0.5053 / 0.5116
-// (sgm_paths -2.5 %), D=192 1.3132 / 1.3205, D=256 1.7015 / 1.7098 and
-// 1.6991 / 1.7094, 640x480 D=64 0.1260 / 0.1276 and 0.1274 / 0.1297.
-constexpr int kSplitPairs = 1;
-// m + P2 of the step as one v_mad_u32_u24 from m (1), beside K, instead of
-// P2 * 0x10001 - K after it (0): the chain row minimum -> m + P2 -> min3 ->
-// add3 one instruction shorter, for the latency-bound lines of small frames,
-// at one v_mov per step (the uniform P2 * 0x10001 re-materialised in a VGPR).
-// Frame ms on / off (profiles/r06_v12/): 640x480 D=64 0.1272 / 0.1263,
-// 960x540 D=64 0.1653 / 0.1654, 1080p D=64 0.5151 / 0.5078 (sgm_paths
-// 0.289 / 0.281), 1080p D=128 0.8823 / 0.8818: a lone line's step is not
-// bound by that chain.  Off.
-constexpr int kStepMadP2 = 0;
 // Prefetch ring depth in steps, per line kind and disparities per lane
 // (D = 16 * DPL).  Horizontal lines are few (2H) and long (W steps) and run
 // alone once the vertical/diagonal lines drain, so they get the deeper ring.
@@ -81,25 +56,7 @@ constexpr int kCkptStoreAux = 0;
 // only (DPL 4).
 constexpr int kStaticCkptHitsMaxDpl = 4;
 
-// Minimum of a path state restored from a checkpoint (sgm_common.h
-// state_from_words): the packed-u16 min tree of the recurrence step (1) or
-// one scalar min per half (0).  -104 static VALU in wta_hv<8>; wta_hv
-// within 1 % either way, never slower beyond noise
-// (profiles/r03_v8/ab_state_min_tree.log.txt).
-constexpr int kStateMinTree = 1;
-
 // ---- wta_hv.hip -------------------------------------------
-// The down diagonals (directions 4 and 6) recomputed per tile from row
-// checkpoints with a 7-column halo (1), or written as volumes by sgm_paths
-// and read back (0).  The up diagonals (5 and 7) likewise,
-// from the checkpoint row below the tile.  Both 0: the recompute moves
-// sgm_paths' saved bytes into VALU on the VALU-bound wta_hv.  Frame ms,
-// none / down pair / all four, in-process A/B with equal maps
-// (profiles/r04_v3/ab_diag_recompute.log.txt): 1080p D=128 0.891 / 0.936 /
-// 1.010, D=192 1.324 / 1.355 / 1.367, D=256 1.735 / 1.836 / 1.931, 4K D=128
-// 3.772 / 3.863 / 3.944, 4K D=256 7.570 / 7.394 / 7.697.
-constexpr int kTileDiagDown = 0;
-constexpr int kTileDiagUp = 0;
 // The pair route: a frame (not a batch) whose 2 * P2
 // fits a u8 has each diagonal and its opposite walked by one wave of
 // sgm_paths, which writes the two pair-sum volumes E = (L_a - C) + (L_b - C)
@@ -148,22 +105,6 @@ constexpr int kPathMinima4 = 0, kPathMinima8 = 1, kPathMinima12 = 0, kPathMinima
 // prefetch depth (pixels) of wta_hv's two pair-volume loads: wta_hv ms at 1080p
 // D=128 for 2 / 3 / 4: 0.1862 / 0.1837 / 0.1815
 constexpr int kWtahvPfVolPair = 4;
-// The strip route: at D <= 128 sgm_paths writes
-// row checkpoints for all four diagonals and no volume at all, and
-// wta_strip_kernel recomputes all eight directions per tile, walking strips
-// of tiles so that every diagonal line runs once (no per-tile halo).
-// kStripTileW: tile columns (16 or 32; 32 x 16 lanes = 512 threads);
-// kStripCols: strip length in columns (rounded to whole tiles, evened out).
-// Built, bit-exact (265 GPU tests with it on) and measured slower
-// (profiles/r06_v2/ab_*.log.txt, frame ms product / strip / 32-wide strip):
-// 1080p D=128 0.883 / 0.962 / 1.078, 1080p D=64 0.542 / 0.705 / 0.782,
-// 640x480 D=64 0.129 / 0.203 / 0.207 -- the final kernel is VALU-issue-bound
-// at 0.83 of the measured mix ceiling.  Off.
-constexpr int kStripRoute = 0;
-constexpr int kStripTileW = 16;
-constexpr int kStripCols = 128;
-// minimum waves per SIMD asked of the compiler (launch bounds)
-constexpr int kStripMinWaves = 3;
 // log2 of the tile rows and of the checkpoint segment (tiles are 16 x 2^this).
 // Round 6 re-check of 16 x 16 (checkpoints every 16: -0.13 GB per 1080p
 // D=128 frame, now that wta_hv streams its bytes; profiles/r06_v11/), frame
@@ -181,29 +122,6 @@ constexpr int kWtahvTileLog2Wide = 3;      // D > 128
 constexpr int kWtahvPfVol = 3;             // D=128, D=192
 constexpr int kWtahvPfVol4 = 4;            // D=64
 constexpr int kWtahvPfVol16 = 2;           // D=256
-// Phase V's opposite recurrences one after the other (0) or interleaved (1).
-constexpr int kWtahvInterleaveV = 0;
-// Phase H's checkpoint and first volume loads issued before the barrier.
-constexpr int kWtahvEarlyLoads = 1;
-// Phase H's cost words loaded with phase V's at the start (1) or after phase
-// V's recurrences (0).
-constexpr int kWtahvRowCFirst = 1;
-// Phase V's L_2 (bit 0) and phase H's L_0 (bit 1) kept per pixel as the
-// step's u16 pairs (V and S need only packed adds) instead of u8-packed (two
-// v_perm per word to re-expand, half the registers).  D <= 128: both, wta_hv
-// 0.273 -> 0.266 ms at 1080p D=128.  Above D = 128 both copies would cost a
-// wave per SIMD (D=192: 157 -> 169 VGPRs); phase V's alone costs no register
-// (157 / 194 VGPRs at D=192 / 256, as with none) and phase H's alone keeps
-// the occupancy too, so they were measured one at a time
-// (profiles/r03_v8/ab_wtahv_keep_u16_wide.log.txt, wta_hv at 1080p): none /
-// V / H  D=192 0.4138 / 0.4096 / 0.4107 ms, D=256 0.5832 / 0.5740 / 0.5717,
-// D=150 0.3981 / 0.3903 / 0.3936, D=232 0.5805 / 0.5653 / 0.5653.  The
-// shorter volume prefetch at D >= 192 (kWtahvPfVol*) then left room for both
-// (D=192 154-161 VGPRs, 3 waves/SIMD): V+H vs V, wta_hv D=192 0.3806-0.3813
-// vs 0.3966-0.4018 ms, D=256 0.5053 vs 0.5125, 4K 1.995 vs 2.015
-// (ab_wtahv_pf_vol_keep.log.txt).
-constexpr int kWtahvKeepU16 = 3;
-constexpr int kWtahvKeepU16Wide = 3;
 // The row minimum's last DPP step pinned next to its move (sva_device.h
 // row_min_u32<true>: one v_min_u32_dpp instead of v_mov 0 + v_mov_dpp + v_min),
 // in the recurrences and in the WTA.  wta_hv, in-process, 3 variants x 2
@@ -213,31 +131,6 @@ constexpr int kWtahvKeepU16Wide = 3;
 // and 1-2 % slower at 4K, so the path kernel stays unpinned.)
 constexpr int kWtahvPinRowMin = 1;
 constexpr int kWtahvPinWta = 1;
-// Sub-pixel neighbours S(d*-1), S(d*+1): through LDS (1: S written over the
-// pixel's dead V block, two u16 reads by the owning lane) or gathered in
-// registers (0: per-pair selects, a v_perm and a 4-step DPP OR-reduction).
-// 9 % fewer static VALU in wta_hv<8>; wta_hv in-process, 0 -> 1
-// (profiles/r03_v8/ab_wtahv_subpixel_lds.log.txt): 1080p D=128 0.2514 / 0.2529
-// -> 0.2495 / 0.2450 ms, D=64 0.150 -> 0.144, D=192 0.393 -> 0.380, D=256
-// 0.556 -> 0.538, 4K D=256 2.215 -> 2.158.
-constexpr int kWtahvSubLds = 1;
-// Round 5 (wta_hv VALU).  kWtahvKeyPerm: the WTA keys
-// (S << 16 | d) built with one v_perm per half from a per-lane disparity
-// pair register, 2 VALU per pair instead of 4.  kWtahvSubDeferred: the
-// owning lane reads S(d*-1), S(d*+1) of its pixel once after the row
-// segment (every pixel's S stays in its own LDS block), instead of an
-// exec-masked read block per pixel.
-constexpr int kWtahvKeyPerm = 1;
-constexpr int kWtahvSubDeferred = 1;
-// Round 6: each pixel's cost words expanded to u16 pairs once per phase and
-// kept for the phase's second recurrence (down/up, left/right) instead of
-// twice; bit b for DPL = 4 (b + 1).  Costs NP VGPRs per row of the tile
-// (D=128: 111 -> 129, 4 -> 3 waves/SIMD, so never there).  Measured with
-// bits 0 and 3 (D=64, D=256), wta_hv ms on / off (profiles/r06_v8/r7l_ab_*):
-// 1080p D=64 0.1423 / 0.1421, D=256 0.4830 / 0.4862, 640x480 D=64 0.0261 /
-// 0.0268, 4K D=256 1.9735 / 1.9745 -- noise: the kernel streams its bytes at
-// ~5.9 TB/s, and fewer VALU do not move it.  Off.
-constexpr int kWtahvUnpackOnce = 0;
 // Minimum waves per SIMD asked of the compiler for wta_hv (launch bounds).
 // Round 6: u8 keeps + phase H's cost loads after phase V + a 2-pixel volume
 // prefetch bring D=128 to 90 VGPRs with no scratch, 5 waves/SIMD -- and the
@@ -246,17 +139,6 @@ constexpr int kWtahvUnpackOnce = 0;
 // within noise; profiles/r06_v7/ab_o5_*): it sits on its instruction-mix
 // ceiling and its bytes at once.
 constexpr int kWtahvMinWaves = 1;
-// LDS V blocks at D = 256 (8 u16 pairs = two 16-byte chunks per lane): 1 swaps
-// a lane's two chunks when ((k >> 2) ^ (k >> 3)) & 1, which makes every
-// ds_write_b128 (8-lane groups, 32 banks) and ds_read_b128 (16-lane groups
-// spanning two slot rows, 64 banks) of the block conflict-free; 0 keeps the
-// plain [lane][pair] order (2-way conflicts on both).  0: the swizzle cut
-// wta_hv's bank-conflict cycles 20.9 M -> 1.6 M and its LDS-active cycles
-// 42.0 M -> 22.6 M per 1080p D=256 launch, but the kernel is VALU-bound and
-// the two lane bases cost registers (190 -> 197 VGPRs): wta_hv 0.5097 ->
-// 0.5223 ms at 1080p D=256, 2.065 -> 2.108 ms at 4K D=256; D=128 / 192
-// unchanged (profiles/r04_v3/ab_vswizzle.log.txt, pmc_vswizzle.txt).
-constexpr int kWtahvVSwizzle = 0;
 
 // ---- batched frames (sva_disparity_sgm_batch_d) ----------
 // Frames per sgm_paths / wta_hv launch, and the workspace those frames may
@@ -344,14 +226,6 @@ constexpr int kCostStoreNT = 1;
 // 0.0918, D=192 0.127 -> 0.1247, D=256 0.1418 -> 0.1376, 4K D=256 0.5376 ->
 // 0.5213, D=64 unchanged.
 constexpr int kCensusCostSlotOrder = 1;
-// census_cost with the census and the multiply on different waves
-// (census_cost_ws_kernel: 512 threads, two operand buffers, one barrier per
-// row), D <= 192.  Bit-exact (290 census / SGM / any-D / config tests with it
-// on) and slower, census_cost ms on / off (profiles/r06_v14/): 1080p D=128
-// 0.0947 / 0.0874, D=64 0.0733 / 0.0639, D=192 0.1489 / 0.1233, 640x480 D=64
-// 0.0186 / 0.0166, 4K D=128 0.381 / 0.346 -- half the waves idle in each
-// phase cost more than the second barrier and the serialised phases.  Off.
-constexpr int kCensusCostWS = 0;
 // census_cost2.hip (2-D array steps): adjacent lattice lines per workgroup,
 // which share one staged image patch.
 constexpr int kCensusCost2Lines = 8;

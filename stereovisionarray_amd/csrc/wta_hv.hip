@@ -14,7 +14,7 @@
 //            goes to LDS (u16 pairs).
 //   phase H  row-slot s runs one TY-pixel row segment (16 / TY per tile row):
 //            left-to-right from the checkpoint left of it (L_0 kept in
-//            registers, u8-packed), then right-to-left from the one right of
+//            registers, u16 pairs), then right-to-left from the one right of
 //            it; at each pixel S = L_1 + L_0 + V + the four diagonal volumes,
 //            and the first-minimum WTA (+ parabola) picks d*.
 // Every recurrence restarts from the exact state the path kernel had, so L,
@@ -72,12 +72,7 @@ __global__ __launch_bounds__(TB, tune::kWtahvMinWaves) void wta_hv_kernel(const 
     constexpr int NW = DPL / 4, NP = DPL / 2;
     constexpr int TY = 1 << TYL;        // tile rows = checkpoint segment (rows and columns)
     constexpr int kPfVol = pf_vol<DPL, PAIR>();
-    // bit 0: phase V keeps L_2 as u16, bit 1: phase H keeps L_0 as u16
-    constexpr int KEEPM = DPL <= 8 ? tune::kWtahvKeepU16 : tune::kWtahvKeepU16Wide;
-    constexpr bool KEEP16 = (KEEPM & 1) != 0, KEEP16H = (KEEPM & 2) != 0;
     constexpr bool PIN = tune::kWtahvPinRowMin != 0;     // row_min_u32<PIN>
-    // cost words expanded once per phase (tune::kWtahvUnpackOnce)
-    constexpr bool UNPACK1 = ((tune::kWtahvUnpackOnce >> (DPL / 4 - 1)) & 1) != 0;
 
     constexpr int SPR = TW / TY;        // phase H: row segments per tile row
     static_assert(TY <= TW && TW % TY == 0, "tile rows must divide 16");
@@ -86,16 +81,12 @@ __global__ __launch_bounds__(TB, tune::kWtahvMinWaves) void wta_hv_kernel(const 
     const unsigned tb = blockIdx.x - f * (unsigned)g.tiles;
     const int tx = (int)(tb % (unsigned)g.ntx);
     const int ty = (int)(tb / (unsigned)g.ntx);
-    // diagonals recomputed per tile (§4.11): the down pair (4, 6), the up pair (5, 7)
-    constexpr bool DOWN = diag_ckpt_down(DPL), UP = diag_ckpt_up(DPL);
-    constexpr int ND = (DOWN ? 2 : 0) + (UP ? 2 : 0);   // recomputed diagonals
-    constexpr int NV = PAIR ? 2 : 4 - ND;               // diagonal volumes read
-    static_assert(!PAIR || ND == 0, "the pair route replaces all four diagonal volumes");
-    static_assert(!MN || (TY == kMinimaSeg && ND == 0), "path minima: 8-pixel segments, no phase D");
+    constexpr int NV = PAIR ? 2 : 4;                    // diagonal volumes read
+    static_assert(!MN || TY == kMinimaSeg, "path minima: 8-pixel segments");
     C += (size_t)f * g.vol;
     L4 += (size_t)f * NV * g.vol;
     CK += (size_t)f * 2 * g.hck;
-    CKV += (size_t)f * (2 + ND) * g.vck;
+    CKV += (size_t)f * 2 * g.vck;
     disp += (size_t)f * (size_t)g.W * (size_t)g.H;
     if (sub) sub += (size_t)f * (size_t)g.W * (size_t)g.H;
     const int slot = (int)(threadIdx.x >> 4);
@@ -117,14 +108,11 @@ __global__ __launch_bounds__(TB, tune::kWtahvMinWaves) void wta_hv_kernel(const 
     }
 
     // V = L_2 + L_3 per tile pixel, [pixel = r * TW + c][lane k][NP pairs]:
-    // each 16-lane row reads / writes 16 consecutive NP-dword chunks.  At
-    // NP = 8 a lane's two 16-byte chunks trade places when ((k >> 2) ^
-    // (k >> 3)) & 1 (tune::kWtahvVSwizzle): bank-conflict-free b128 reads and
-    // writes.  vw(p) = the word of pair p inside a pixel block.
+    // each 16-lane row reads / writes 16 consecutive NP-dword chunks.
+    // vw(p) = the word of pair p inside a pixel block: word p % 4 of the
+    // lane's first or second 16-byte chunk (one b128 access each).
     __shared__ unsigned vsum[TY * TW * 16 * NP];
-    constexpr bool VSW = NP == 8 && tune::kWtahvVSwizzle != 0;
-    auto vsw_of = [](int kk) -> int { return VSW ? (((kk >> 2) ^ (kk >> 3)) & 1) * 4 : 0; };
-    const int vb0 = k * NP + vsw_of(k), vb1 = k * NP + (4 ^ vsw_of(k));
+    const int vb0 = k * NP, vb1 = k * NP + 4;
     auto vw = [&](int p) -> int { return (p < 4 ? vb0 : vb1) + (p & 3); };
 
     // phase V: column x0 + slot; phase H: row hr, columns [hx, hx + TY)
@@ -135,9 +123,9 @@ __global__ __launch_bounds__(TB, tune::kWtahvMinWaves) void wta_hv_kernel(const 
     const bool hrow = hr < ny && nh > 0;
     const unsigned xv = (unsigned)(x0 + slot), yh = (unsigned)(y0 + hr);
 
-    // Both phases' cost words are loaded up front (tune::kWtahvRowCFirst): the
-    // tile's column slice for phase V and its row slice for phase H (the same
-    // bytes, L2-hot the second time).
+    // Both phases' cost words are loaded up front: the tile's column slice for
+    // phase V and its row slice for phase H (the same bytes, L2-hot the second
+    // time).
     Words<NW> cv[TY], ch[TY];
 #pragma unroll
     for (int r = 0; r < TY; r++)
@@ -147,7 +135,7 @@ __global__ __launch_bounds__(TB, tune::kWtahvMinWaves) void wta_hv_kernel(const 
         for (int j = 0; j < TY; j++)
             ch[j] = bload<NW>(rC, (yh * uW + (unsigned)(hx + j)) * uD + lane_d);
     };
-    if constexpr (tune::kWtahvRowCFirst != 0) load_row();
+    load_row();
     // the slot's entering minima: phase V's column segment (directions 2, 3)
     // and phase H's row segment (0, 1), 8 bytes each, the same in all 16 lanes
     Words<2> mv[2] = {}, mh[2] = {};
@@ -175,10 +163,7 @@ __global__ __launch_bounds__(TB, tune::kWtahvMinWaves) void wta_hv_kernel(const 
     };
     unsigned Aa[NP], Ab[NP], ma, mb;
     Edges ea, eb;
-    // ---- phase V: down (direction 2) and up (direction 3) ------------------
-    // tune::kWtahvInterleaveV: one after the other (0), or interleaved, step i
-    // of one next to step TY-1-i of the other (1: two independent dependency
-    // chains per wave).
+    // ---- phase V: down (direction 2), then up (direction 3) ----------------
     if (vcol) {
         if (ty > 0)
             load_state<DPL, PAD, PIN, MN>(make_rsrc(CKV, g.vck), ((unsigned)(ty - 1) * uW + xv) * uD + lane_d,
@@ -190,24 +175,17 @@ __global__ __launch_bounds__(TB, tune::kWtahvMinWaves) void wta_hv_kernel(const 
                                  ((unsigned)(ty + 1) * uW + xv) * uD + lane_d, Ab, mb, padm);
         else
             zero_state(Ab, mb);
-        // The down pass keeps each pixel's L_2 (KEEP16, tune::kWtahvKeepU16: as the
-        // step's u16 pairs, so V = L_2 + L_3 is NP packed adds; else u8-packed,
-        // re-expanded here with two v_perm per word).
-        constexpr int NK = KEEP16 ? NP : NW;
-        auto keep = [&](unsigned (&dst)[NK], const unsigned (&A)[NP], const unsigned (&ow)[NW]) {
+        // The down pass keeps each pixel's L_2 as the step's u16 pairs, so
+        // V = L_2 + L_3 is NP packed adds.
+        auto keep = [&](unsigned (&dst)[NP], const unsigned (&A)[NP]) {
 #pragma unroll
-            for (int q = 0; q < NK; q++) dst[q] = KEEP16 ? A[q] : ow[q];
+            for (int q = 0; q < NP; q++) dst[q] = A[q];
         };
-        auto put_v = [&](int r, const unsigned (&ld)[NK], const unsigned (&Au)[NP],
-                         const unsigned (&lu)[NW], const unsigned (&cw)[NW]) {
+        auto put_v = [&](int r, const unsigned (&ld)[NP], const unsigned (&Au)[NP],
+                         const unsigned (&cw)[NW]) {
             unsigned V[NP];
-            if constexpr (KEEP16) {
 #pragma unroll
-                for (int p = 0; p < NP; p++) V[p] = ld[p] + Au[p];   // L_2 + L_3 (<= 510 per half)
-            } else {
-                words_to_pairs<DPL>(ld, V);
-                unpack_add<NW>(lu, V);
-            }
+            for (int p = 0; p < NP; p++) V[p] = ld[p] + Au[p];   // L_2 + L_3 (<= 510 per half)
             if constexpr (PAIR) {
                 // + 4C, what the two pair sums leave out (<= 1020 per half: no carry)
                 unsigned c4[NP];
@@ -219,164 +197,35 @@ __global__ __launch_bounds__(TB, tune::kWtahvMinWaves) void wta_hv_kernel(const 
 #pragma unroll
             for (int p = 0; p < NP; p++) dst[vw(p)] = V[p];
         };
-        unsigned LD[TY][NK];
-        if constexpr (tune::kWtahvInterleaveV != 0) {
-            unsigned LU[TY][NK];
-            for_seq<TY>([&](auto I) {
-                constexpr int i = decltype(I)::value, ru = TY - 1 - i;
-                unsigned ow[NW];
-                if (i < ny) {
-                    given_m(ma, mv[0], i);
-                    sgm_step<DPL, PIN, MN>(cv[i].w, Aa, ma, ow, P1, P2, ea);
-                    keep(LD[i], Aa, ow);
-                }
-                if (ru < ny) {
-                    given_m(mb, mv[1], i);
-                    sgm_step<DPL, PIN, MN>(cv[ru].w, Ab, mb, ow, P1, P2, eb);
-                    keep(LU[ru], Ab, ow);
-                }
-            });
-            for_seq<TY>([&](auto R) {
-                constexpr int r = decltype(R)::value;
-                if (r < ny) {
-                    if constexpr (KEEP16) {
-                        const unsigned none[NW] = {};
-                        put_v(r, LD[r], LU[r], none, cv[r].w);
-                    } else {
-                        unsigned V[NP] = {};
-                        put_v(r, LD[r], V, LU[r], cv[r].w);
-                    }
-                }
-            });
-        } else {
-            unsigned cvp[UNPACK1 ? TY : 1][NP];           // row r's cost pairs (UNPACK1)
-            for_seq<TY>([&](auto I) {
-                constexpr int i = decltype(I)::value;
-                unsigned ow[NW];
-                if (i < ny) {
-                    given_m(ma, mv[0], i);
-                    if constexpr (UNPACK1) {
-                        words_to_pairs<DPL>(cv[i].w, cvp[i]);
-                        sgm_step_c<DPL, PIN, MN>(cvp[i], Aa, ma, ow, P1, P2, ea);
-                    } else {
-                        sgm_step<DPL, PIN, MN>(cv[i].w, Aa, ma, ow, P1, P2, ea);
-                    }
-                    keep(LD[i], Aa, ow);
-                }
-            });
-            for_seq<TY>([&](auto Q) {
-                constexpr int r = TY - 1 - decltype(Q)::value;
-                if (r < ny) {
-                    unsigned lu[NW];
-                    given_m(mb, mv[1], TY - 1 - r);
-                    if constexpr (UNPACK1) sgm_step_c<DPL, PIN, MN>(cvp[UNPACK1 ? r : 0], Ab, mb, lu, P1, P2, eb);
-                    else sgm_step<DPL, PIN, MN>(cv[r].w, Ab, mb, lu, P1, P2, eb);
-                    put_v(r, LD[r], Ab, lu, cv[r].w);
-                }
-            });
-        }
-    }
-    if constexpr (ND > 0) {
-        // ---- phase D: diagonals recomputed per tile ------
-        // Direction 4 (+x) and 6 (-x) come down from the row checkpoint at
-        // y0 - 1, 5 (-x) and 7 (+x) up from the one at y0 + TY (zero state at
-        // the image's top / bottom edge).  Each has NL = 16 + TY - 1 lines
-        // crossing the tile; a line's first TY - 1 pixels can lie in the halo
-        // beside it.  In-tile pixels add L into V with LDS atomics (packed u16
-        // pairs: V + four diagonals <= 1530 per half, no carry), so every
-        // direction's runs share the slots in any order.  A line off the
-        // image restarts (zero state) like the path kernel's wrapped lines.
-        __syncthreads();                              // V stored before the adds
-        constexpr int NL = TW + TY - 1;
-        constexpr int NRUN = (ND * NL + 15) / 16;     // runs per slot
-        const rsrc_t rCKD = make_rsrc(CKV + 2 * (size_t)g.vck, (unsigned)ND * g.vck);
-        // run i of this slot: line q = slot + 16 i of the ND * NL
-        struct Run {
-            int c, rx, yck;   // column at the checkpoint row, x step, checkpoint segment
-            unsigned plane;   // its plane in rCKD
-            bool up, ok;
-        };
-        auto run_of = [&](int i) __attribute__((always_inline)) -> Run {
-            Run u;
-            const int q = slot + 16 * i;
-            const int dd = q / NL, li = q - dd * NL;
-            u.ok = q < ND * NL;
-            u.up = !DOWN || dd >= 2;
-            const int e = u.up && DOWN ? dd - 2 : dd;     // 0 or 1 within its pair
-            // down: 4 (+x), 6 (-x); up: 5 (-x), 7 (+x)
-            u.rx = u.up ? (e ? 1 : -1) : (e ? -1 : 1);
-            u.c = u.rx > 0 ? x0 - TY + li : x0 + 1 + li;
-            u.plane = (unsigned)dd;
-            u.yck = u.up ? (y0 + TY < H ? ty + 1 : -1) : ty - 1;   // -1: no checkpoint
-            return u;
-        };
-        auto issue_d = [&](int i, Words<NW>& ck, Words<NW> (&cd)[TY]) __attribute__((always_inline)) {
-            const Run u = run_of(i);
-            const bool ckin = u.yck >= 0 && (unsigned)u.c < (unsigned)W;
-            ck = bload<NW>(rCKD, ckin ? u.plane * g.vck + ((unsigned)u.yck * uW + (unsigned)u.c) * uD +
-                                            lane_d
-                                      : 0u);
-#pragma unroll
-            for (int s = 0; s < TY; s++) {
-                const int x = u.c + u.rx * (s + 1);
-                const int y = u.up ? y0 + TY - 1 - s : y0 + s;
-                cd[s] = bload<NW>(rC, (unsigned)x < (unsigned)W && y < H
-                                          ? ((unsigned)y * uW + (unsigned)x) * uD + lane_d
-                                          : 0u);
+        unsigned LD[TY][NP];
+        for_seq<TY>([&](auto I) {
+            constexpr int i = decltype(I)::value;
+            unsigned ow[NW];
+            if (i < ny) {
+                given_m(ma, mv[0], i);
+                sgm_step<DPL, PIN, MN>(cv[i].w, Aa, ma, ow, P1, P2, ea);
+                keep(LD[i], Aa);
             }
-        };
-        auto run_d = [&](int i, const Words<NW>& ck, const Words<NW> (&cd)[TY]) __attribute__((always_inline)) {
-            const Run u = run_of(i);
-            if (!u.ok) return;                        // uniform per 16-lane row
-            unsigned A[NP], m;
-            if (u.yck >= 0 && (unsigned)u.c < (unsigned)W) state_from_words<DPL, PAD, PIN>(ck, A, m, padm);
-            else zero_state(A, m);
-            for_seq<TY>([&](auto R) {
-                constexpr int s = decltype(R)::value;
-                const int x = u.c + u.rx * (s + 1);
-                const int r = u.up ? TY - 1 - s : s;      // tile row
-                if ((unsigned)x < (unsigned)W && r < ny) {
-                    unsigned ow[NW];
-                    sgm_step<DPL, PIN>(cd[s].w, A, m, ow, P1, P2, eb);
-                    if (x >= x0 && x < x0 + nx) {
-                        unsigned* dst = &vsum[(r * TW + (x - x0)) * 16 * NP];
-#pragma unroll
-                        for (int p = 0; p < NP; p++) atomicAdd(&dst[vw(p)], A[p]);
-                    }
-                } else {
-                    zero_state(A, m);                   // off the image: restart
-                }
-            });
-        };
-        if constexpr (DPL <= 8) {
-            // the next run's loads go out before this run's recurrence
-            Words<NW> ck[2], cd[2][TY];
-            issue_d(0, ck[0], cd[0]);
-            for_seq<NRUN>([&](auto I) {
-                constexpr int i = decltype(I)::value;
-                if constexpr (i + 1 < NRUN) issue_d(i + 1, ck[(i + 1) & 1], cd[(i + 1) & 1]);
-                run_d(i, ck[i & 1], cd[i & 1]);
-            });
-        } else {
-            Words<NW> ck, cd[TY];
-            for_seq<NRUN>([&](auto I) {
-                constexpr int i = decltype(I)::value;
-                issue_d(i, ck, cd);
-                run_d(i, ck, cd);
-            });
-        }
+        });
+        for_seq<TY>([&](auto Q) {
+            constexpr int r = TY - 1 - decltype(Q)::value;
+            if (r < ny) {
+                unsigned lu[NW];
+                given_m(mb, mv[1], TY - 1 - r);
+                sgm_step<DPL, PIN, MN>(cv[r].w, Ab, mb, lu, P1, P2, eb);
+                put_v(r, LD[r], Ab, cv[r].w);
+            }
+        });
     }
-    if constexpr (tune::kWtahvRowCFirst == 0) load_row();
     // phase H's first global loads (checkpoints, diagonal volumes) go out
-    // before the barrier (tune::kWtahvEarlyLoads)
+    // before the barrier
     const int hs = hx >> TYL;                          // the row segment's index
     const unsigned ckrow = yh * (unsigned)g.nsx;
     Words<NW> ckw[2];
-    constexpr int NVA = NV > 0 ? NV : 1;               // (array extent; NV may be 0)
-    rsrc_t rV[NVA];
+    rsrc_t rV[NV];
 #pragma unroll
     for (int r = 0; r < NV; r++) rV[r] = make_rsrc(L4 + (size_t)r * g.vol, g.vol);
-    Words<NW> rv[kPfVol][NVA];
+    Words<NW> rv[kPfVol][NV];
     auto issue = [&](int s, int j) {
         const unsigned off = (yh * uW + (unsigned)(hx + j)) * uD + lane_d;
 #pragma unroll
@@ -390,116 +239,65 @@ __global__ __launch_bounds__(TB, tune::kWtahvMinWaves) void wta_hv_kernel(const 
 #pragma unroll
         for (int q = 0; q < kPfVol && q < TY; q++) issue(q, TY - 1 - q);
     };
-    if constexpr (tune::kWtahvEarlyLoads != 0) {
-        if (hrow) issue_first();
-    }
+    if (hrow) issue_first();
     __syncthreads();
 
     // ---- phase H: left-to-right (direction 0), then right-to-left (1) with
     // the sum and the WTA per pixel
     if (!hrow) return;                                 // whole 16-lane row leaves together
-    if constexpr (tune::kWtahvEarlyLoads == 0) issue_first();
     if (hs > 0) state_from_words<DPL, PAD, PIN, MN>(ckw[0], Aa, ma, padm);
     else zero_state(Aa, ma);
-    // L_0 of the segment's pixels, kept like phase V's L_2 (KEEP16H)
-    constexpr int NKH = KEEP16H ? NP : NW;
-    unsigned LF[TY][NKH];
-    unsigned chp[UNPACK1 ? TY : 1][NP];                // pixel i's cost pairs (UNPACK1)
+    // L_0 of the segment's pixels, kept like phase V's L_2 (u16 pairs)
+    unsigned LF[TY][NP];
     for_seq<TY>([&](auto I) {
         constexpr int i = decltype(I)::value;
         unsigned ow[NW];
         if (i < nh) {
             given_m(ma, mh[0], i);
-            if constexpr (UNPACK1) {
-                words_to_pairs<DPL>(ch[i].w, chp[i]);
-                sgm_step_c<DPL, PIN, MN>(chp[i], Aa, ma, ow, P1, P2, ea);
-            } else {
-                sgm_step<DPL, PIN, MN>(ch[i].w, Aa, ma, ow, P1, P2, ea);
-            }
+            sgm_step<DPL, PIN, MN>(ch[i].w, Aa, ma, ow, P1, P2, ea);
 #pragma unroll
-            for (int q = 0; q < NKH; q++) LF[i][q] = KEEP16H ? Aa[q] : ow[q];
+            for (int q = 0; q < NP; q++) LF[i][q] = Aa[q];
         }
     });
     if (hx + TY < W) state_from_words<DPL, PAD, PIN, MN>(ckw[1], Aa, ma, padm);
     else zero_state(Aa, ma);
     unsigned dres = 0u, sm = 0u, s0 = 0u;
     const bool want_sub = sub != nullptr;
-    unsigned dpair[NP];                                // each pair's two d (kWtahvKeyPerm)
+    unsigned dpair[NP];                                // each pair's two d, for wta_pick_key_perm
 #pragma unroll
     for (int j = 0; j < NP; j++)
         dpair[j] = (lane_d + (unsigned)pair_d<DPL>(j, 0)) | ((lane_d + (unsigned)pair_d<DPL>(j, 1)) << 16);
-    constexpr bool DEFER = tune::kWtahvSubLds != 0 && tune::kWtahvSubDeferred != 0;
     unsigned* const vrow = &vsum[(hr * TW + hseg * TY) * 16 * NP];   // the segment's V blocks
     for_seq<TY>([&](auto Q) {
         constexpr int q = decltype(Q)::value, j = TY - 1 - q, s = q % kPfVol;
         if (j < nh) {
             unsigned ow[NW];
             given_m(ma, mh[1], q);
-            if constexpr (UNPACK1) sgm_step_c<DPL, PIN, MN>(chp[UNPACK1 ? j : 0], Aa, ma, ow, P1, P2, ea);
-            else sgm_step<DPL, PIN, MN>(ch[j].w, Aa, ma, ow, P1, P2, ea);
+            sgm_step<DPL, PIN, MN>(ch[j].w, Aa, ma, ow, P1, P2, ea);
             unsigned* const vpix = vrow + j * 16 * NP;                     // this pixel's V
             unsigned S[NP];
 #pragma unroll
             for (int p = 0; p < NP; p++) S[p] = vpix[vw(p)] + Aa[p];   // V + L_1
-            if constexpr (KEEP16H) {
 #pragma unroll
-                for (int p = 0; p < NP; p++) S[p] += LF[j][p];     // + L_0
-            } else {
-                unpack_add<NW>(LF[j], S);
-            }
+            for (int p = 0; p < NP; p++) S[p] += LF[j][p];     // + L_0
 #pragma unroll
             for (int r = 0; r < NV; r++) unpack_add<NW>(rv[s][r].w, S);
             if constexpr (PAD) {
 #pragma unroll
                 for (int p = 0; p < NP; p++) S[p] |= padm[p];
             }
-            unsigned spm, sb;
-            if constexpr (tune::kWtahvSubLds != 0) {
-                // S(d*-1) and S(d*+1) through LDS: every lane writes its S
-                // pairs over the pixel's V block, which nothing reads again;
-                // as u16 the block is S indexed by d (up to the swizzle).  The owning lane reads
-                // the two neighbours (same wave, behind a wave barrier).
-                const unsigned best = tune::kWtahvKeyPerm
-                                          ? wta_pick_key_perm<DPL, PIN && tune::kWtahvPinWta>(S, dpair)
-                                          : wta_pick_key<DPL, PIN && tune::kWtahvPinWta, tune::kSplitPairs != 0>(S, k);
-                const int ds = (int)(best & 0xffffu);
-                if (want_sub) {
+            // S(d*-1) and S(d*+1) go through LDS: every lane writes its S
+            // pairs over the pixel's V block, which nothing reads again; as
+            // u16 the block is S in the state's pair layout.  The owning lane
+            // reads the two neighbours once after the row segment (below).
+            const unsigned best = wta_pick_key_perm<DPL, PIN && tune::kWtahvPinWta>(S, dpair);
+            const int ds = (int)(best & 0xffffu);
+            if (want_sub) {
 #pragma unroll
-                    for (int p = 0; p < NP; p++) vpix[vw(p)] = S[p];
-                    if constexpr (!DEFER) {
-                        // the owning lane reads what other lanes of this wave just
-                        // wrote: state the ordering (a wave's LDS operations
-                        // execute in issue order, so this costs no instruction)
-                        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                        __builtin_amdgcn_wave_barrier();
-                        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-                    }
-                }
-                if constexpr (DEFER) {
-                    dres = k == j ? (unsigned)ds : dres;
-                    s0 = k == j ? best >> 16 : s0;
-                } else if (k == j) {
-                    dres = (unsigned)ds;
-                    s0 = best >> 16;
-                    if (want_sub) {
-                        const uint16_t* s16 = reinterpret_cast<const uint16_t*>(vpix);
-                        const int dm = ds > 0 ? ds - 1 : 0, dp = ds + 1 < 16 * DPL ? ds + 1 : ds;
-                        // u16 of disparity d: pair (d / 2) % NP of lane d / DPL
-                        auto at = [&](int d) {
-                            const int kk = d / DPL, pp = pair_of<DPL>(d % DPL), hh = half_of<DPL>(d % DPL);
-                            return (unsigned)s16[2 * (kk * NP + (pp ^ vsw_of(kk))) + hh];
-                        };
-                        sm = at(dm) | (at(dp) << 16);
-                    }
-                }
-            } else {
-                const int ds = wta_pick_raw<DPL, PIN && tune::kWtahvPinWta, tune::kSplitPairs != 0>(S, k, want_sub, &spm, &sb);
-                if (k == j) {
-                    dres = (unsigned)ds;
-                    sm = spm;
-                    s0 = sb;
-                }
+                for (int p = 0; p < NP; p++) vpix[vw(p)] = S[p];
             }
+            dres = k == j ? (unsigned)ds : dres;
+            s0 = k == j ? best >> 16 : s0;
         }
         if constexpr (q + kPfVol < TY) {
             __builtin_amdgcn_sched_barrier(0);
@@ -507,23 +305,22 @@ __global__ __launch_bounds__(TB, tune::kWtahvMinWaves) void wta_hv_kernel(const 
             __builtin_amdgcn_sched_barrier(0);
         }
     });
-    if constexpr (DEFER) {
-        // S(d*-1), S(d*+1) of lane k's pixel (j = k) from the S its row wrote
-        // over the pixel's V block (same wave: order, no barrier instruction)
-        if (want_sub) {
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            if (k < nh) {
-                const uint16_t* s16 = reinterpret_cast<const uint16_t*>(vrow + k * 16 * NP);
-                const int ds = (int)dres;
-                const int dm = ds > 0 ? ds - 1 : 0, dp = ds + 1 < 16 * DPL ? ds + 1 : ds;
-                auto at = [&](int d) {
-                    const int kk = d / DPL, pp = pair_of<DPL>(d % DPL), hh = half_of<DPL>(d % DPL);
-                    return (unsigned)s16[2 * (kk * NP + (pp ^ vsw_of(kk))) + hh];
-                };
-                sm = at(dm) | (at(dp) << 16);
-            }
+    // S(d*-1), S(d*+1) of lane k's pixel (j = k) from the S its row wrote
+    // over the pixel's V block (same wave: order, no barrier instruction)
+    if (want_sub) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        if (k < nh) {
+            const uint16_t* s16 = reinterpret_cast<const uint16_t*>(vrow + k * 16 * NP);
+            const int ds = (int)dres;
+            const int dm = ds > 0 ? ds - 1 : 0, dp = ds + 1 < 16 * DPL ? ds + 1 : ds;
+            // u16 of disparity d: half half_of(d % DPL) of pair pair_of(d % DPL) of lane d / DPL
+            auto at = [&](int d) {
+                const int kk = d / DPL, pp = pair_of<DPL>(d % DPL), hh = half_of<DPL>(d % DPL);
+                return (unsigned)s16[2 * (kk * NP + pp) + hh];
+            };
+            sm = at(dm) | (at(dp) << 16);
         }
     }
     if (k < nh) {
@@ -570,10 +367,6 @@ hipError_t launch_wta_hv(Ctx& c, const uint8_t* C, const uint8_t* L4, const uint
                          const uint8_t* CKV, int W, int H, int D, int P1, int P2, int dmin,
                          uint16_t* disp, float* sub, int dreal, int npair, bool pair,
                          const uint8_t* MN) {
-    // D <= 128 on the strip route: all eight directions recomputed per tile
-    // from checkpoints, no diagonal volume (wta_strip.hip)
-    if (tune::kStripRoute != 0 && wta_strip_supported(D))
-        return launch_wta_strip(c, C, CK, CKV, W, H, D, P1, P2, dmin, disp, sub, dreal, npair);
     DispatchTimer t(c, "wta_hv");
     if (!wta_hv_supported(D)) return hipErrorInvalidValue;
     const TileGeom tg = tile_geom(W, H, D);
@@ -607,9 +400,8 @@ hipError_t launch_wta_hv(Ctx& c, const uint8_t* C, const uint8_t* L4, const uint
     }
     constexpr int TYL = tune::kWtahvTileLog2, TYLW = tune::kWtahvTileLog2Wide;
     if (tg.seg_log2 != (D <= 128 ? TYL : TYLW)) return hipErrorInvalidValue;
-    if (pair && (npair != 1 || !diag_pair_ok(D, P2) || tg.nvol != 4)) return hipErrorInvalidValue;
-    if (MN && (npair != 1 || !path_minima_enabled(D) || (1 << tg.seg_log2) != sgm::kMinimaSeg ||
-               tg.nvol != 4))
+    if (pair && (npair != 1 || !diag_pair_ok(D, P2))) return hipErrorInvalidValue;
+    if (MN && (npair != 1 || !path_minima_enabled(D) || (1 << tg.seg_log2) != sgm::kMinimaSeg))
         return hipErrorInvalidValue;
     switch (D) {
         case 64: SVA_WTAHV_P(4, TYL, tune::kDiagPair4, tune::kPathMinima4); break;

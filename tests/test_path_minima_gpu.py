@@ -124,10 +124,9 @@ def stage_maps(ctx, sva, torch_dev, L, R, p):
     dR = torch.from_numpy(R.copy()).to(torch_dev)
     C = torch.zeros((H, W, D), dtype=torch.uint8, device=torch_dev)
     ctx.census_cost_d(dL.data_ptr(), dR.data_ptr(), W, H, W, p, C.data_ptr())
-    nvol = lay.diag_volumes
-    diag = torch.full((nvol, H, W, D), 0xAB, dtype=torch.uint8, device=torch_dev)
+    diag = torch.full((4, H, W, D), 0xAB, dtype=torch.uint8, device=torch_dev)
     hck = torch.full((2, H, lay.nsx, D), 0xCD, dtype=torch.uint8, device=torch_dev)
-    vck = torch.full((6 - nvol, lay.nsy, W, D), 0xEF, dtype=torch.uint8, device=torch_dev)
+    vck = torch.full((2, lay.nsy, W, D), 0xEF, dtype=torch.uint8, device=torch_dev)
     assert diag.numel() == lay.diag_bytes and hck.numel() == lay.hckpt_bytes
     assert vck.numel() == lay.vckpt_bytes and C.numel() == lay.cost_bytes
     ctx.paths_tile_d(C.data_ptr(), C.numel(), W, H, p, diag.data_ptr(), diag.numel(),

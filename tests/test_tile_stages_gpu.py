@@ -1,12 +1,11 @@
-"""The frame route's two stages (the tile pipeline)
-through their ABI v6 entry points, against the CPU oracle, bit-exact:
-sva_paths_tile_d writes the diagonal volumes and the checkpoints (the
+"""The frame route's two stages (the tile pipeline) through
+their ABI v6 entry points, against the CPU oracle, bit-exact:
+sva_paths_tile_d writes the four diagonal volumes and the checkpoints (the
 oracle's L_0 / L_1 at the checkpoint columns, L_2 / L_3 at the checkpoint
-rows, and in a build that recomputes the down diagonals per tile their L_4 /
-L_6 rows too); sva_wta_hv_d recomputes the checkpointed directions per tile
-and picks d* (sub-pixel within 1e-5 px, observed 0).  The volume / plane
-layout is read from sva_tile_layout_of, so the same checks cover the product
-build (diag_volumes 4) and the §4.11 experiment build (2).
+rows); sva_wta_hv_d recomputes the four checkpointed directions per tile and
+picks d* (sub-pixel within 1e-5 px, observed 0).  The plane sizes are read
+from sva_tile_layout_of, which reports four diagonal volumes and two row
+checkpoint planes.
 Ragged widths and heights around the 16 x seg tile, every native D, five
 penalty pairs.  Every entry refuses an undersized buffer with
 SVA_ERR_INVALID_ARG before launching.
@@ -30,10 +29,10 @@ def run_tiles(ctx, sva, torch_dev, C, p):
     H, W, D = C.shape
     lay = sva.tile_layout(W, H, D)
     d_C = dev(C, torch_dev)
-    nvol = lay.diag_volumes
-    diag = torch.full((nvol, H, W, D), 0xAB, dtype=torch.uint8, device=torch_dev)
+    assert lay.diag_volumes == 4
+    diag = torch.full((4, H, W, D), 0xAB, dtype=torch.uint8, device=torch_dev)
     hck = torch.full((2, H, lay.nsx, D), 0xCD, dtype=torch.uint8, device=torch_dev)
-    vck = torch.full((6 - nvol, lay.nsy, W, D), 0xEF, dtype=torch.uint8, device=torch_dev)
+    vck = torch.full((2, lay.nsy, W, D), 0xEF, dtype=torch.uint8, device=torch_dev)
     assert diag.numel() == lay.diag_bytes and hck.numel() == lay.hckpt_bytes
     assert vck.numel() == lay.vckpt_bytes and d_C.numel() == lay.cost_bytes
     ctx.paths_tile_d(d_C.data_ptr(), d_C.numel(), W, H, p, diag.data_ptr(), diag.numel(),
@@ -58,10 +57,7 @@ def check_stages(oracle, C, dmin, res, P1=10, P2=120):
     diag, hck, vck, disp, sub, lay = res
     seg = lay.seg
     vols = [oracle.path(C, r, P1, P2) for r in range(8)]
-    # volumes: all four diagonals (the wta_hv route, D >= 192), none (the
-    # strip route, D <= 128: all eight directions recomputed per tile,
-    # DESIGN.md §4.12), or the up diagonals 5, 7 in the §4.11 experiment build
-    vol_dirs = {4: [4, 5, 6, 7], 2: [5, 7], 0: []}[lay.diag_volumes]
+    vol_dirs = [4, 5, 6, 7]            # the four diagonal volumes, in direction order
     for slot, r in enumerate(vol_dirs):
         assert np.array_equal(diag[slot], vols[r]), f"direction {r}"
     for s in range(lay.nsx):
@@ -74,12 +70,6 @@ def check_stages(oracle, C, dmin, res, P1=10, P2=120):
             assert np.array_equal(vck[0, s], vols[2][s * seg + seg - 1]), ("v0", s)
         if s > 0:                      # L_3 at the segment's first row
             assert np.array_equal(vck[1, s], vols[3][s * seg]), ("v1", s)
-        if lay.diag_volumes <= 2 and s * seg + seg < H:   # L_4, L_6 at the last row
-            assert np.array_equal(vck[2, s], vols[4][s * seg + seg - 1]), ("d4", s)
-            assert np.array_equal(vck[3, s], vols[6][s * seg + seg - 1]), ("d6", s)
-        if lay.diag_volumes == 0 and s > 0:                # L_5, L_7 at the first row
-            assert np.array_equal(vck[4, s], vols[5][s * seg]), ("d5", s)
-            assert np.array_equal(vck[5, s], vols[7][s * seg]), ("d7", s)
     S = np.zeros(C.shape, np.uint16)
     for v in vols:
         S += v
@@ -136,8 +126,6 @@ def test_undersized_buffers_refused(ctx, sva, torch_dev):
     p = sva.default_params(D=D)
     full = [lay.cost_bytes, lay.diag_bytes, lay.hckpt_bytes, lay.vckpt_bytes]
     for i in range(4):
-        if full[i] == 0:            # no diagonal volume on the strip route (D <= 128)
-            continue
         sizes = list(full)
         sizes[i] -= 1
         with pytest.raises(sva.SvaError) as e:

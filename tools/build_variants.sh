@@ -1,6 +1,6 @@
 #!/bin/bash
 # Build experiment variants of libsva.so for in-process A/B (tools/ab_paths.py):
-#   tools/build_variants.sh name1 "kPfH8=28 kPfV8=8" name2 "kWtahPfBwd=6" ...
+#   tools/build_variants.sh name1 "kPfH8=28 kPfV8=8" name2 "kWtahvPfVol=4" ...
 # Each variant is built from a scratch copy of stereovisionarray_amd/csrc
 # (build/var_<name>/src) whose sva_tuning.h has the named constexpr constants
 # rewritten; product translation units carry no experiment switches.  A value
