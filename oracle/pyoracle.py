@@ -2,7 +2,8 @@
 
 Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg import
 this module, and only as the checker or the timed CPU baseline.  Parity status:
-"parity unpinned" (see sva_oracle.h and DESIGN.md §5).
+Mode R and the refinement / 3-D routines are pinned by tests/golden/ref_*,
+Mode S is not (see sva_oracle.h and DESIGN.md §5).
 """
 from __future__ import annotations
 

@@ -1,7 +1,7 @@
 /*
  * refpath_oracle.c -- CPU ORACLE, Mode R ("reference parity" path).
- * TEST INFRASTRUCTURE ONLY (see sva_oracle.h).  Parity unpinned: the
- * reference is unbuildable here (needs OpenCV); see DESIGN.md §5.
+ * TEST INFRASTRUCTURE ONLY (see sva_oracle.h).  Pinned by fixtures that the
+ * reference's own compiled code produced (tests/golden/ref_*).
  *
  * Each function restates one reference function.  Floating-point expressions
  * keep the reference's operand order; this file is compiled with

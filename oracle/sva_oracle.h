@@ -6,17 +6,21 @@
  * or the timed CPU baseline.  The product library (libsva.so) never links,
  * loads or calls anything in this directory.
  *
- * PARITY STATUS: "parity unpinned".
+ * PARITY STATUS:
  *   - The reference (Nahuel-M/StereoVisionArray) ships no tests, no golden
- *     vectors and no fixtures.
- *   - The reference's hot-path translation units (src/Camera.cpp,
- *     src/functions.cpp) need OpenCV 4.2 headers/libraries that are absent from
- *     this image; building them would require writing stand-in headers, which
- *     this project does not do.  The reference is therefore unbuildable here and
- *     there is no oracle/_ref.
- *   - Mode S (Census / Hamming / 8-path SGM / WTA) does not exist in the
- *     reference at all; its spec is frozen in DESIGN.md §2.
- *   What pins this oracle instead: hand-derived known-answer tests in
+ *     vectors and no fixtures, and needs OpenCV 4.2, which is
+ *     absent.  `make ref` compiles its src/Camera.cpp, src/functions.cpp and
+ *     src/CameraStereoVision.cpp unmodified against the stand-in headers in
+ *     cvstandin/, with refgen.cpp as driver, into _ref/refgen; what that
+ *     program outputs is committed as tests/golden/ref_*.
+ *   - Pinned by those fixtures (tests/test_reference_fixtures.py, exact):
+ *     Mode R's loop as the unmodified main() runs it, Bresenham, the cameras,
+ *     the pair tables, and the refinement / 3-D routines.
+ *   - Not pinned: real OpenCV's resize, imread, YAML and mean (the stand-in
+ *     restates them), so ingestion and evaluation; and Mode S (Census /
+ *     Hamming / 8-path SGM / WTA), which does not exist in the reference at
+ *     all and whose spec is frozen in DESIGN.md §2.
+ *   Also pinning this oracle: hand-derived known-answer tests in
  *   tests/test_oracle_kat.py (hand-expanded Bresenham traces of
  *   functions.cpp:253-321, hand-computed Camera.cpp:15-34 projections, census
  *   words, 1-D SGM recurrences, shifted-texture disparities).

@@ -1,6 +1,9 @@
 // C++ host-mirror tests (include/sva.hpp).  Built by tests/test_host_cpp.py.
 //   ./test_host cpu   -- CPU-only checks (pair tables, bresenham, camera)
 //   ./test_host gpu   -- computeDisparity / computeDisparitySGM through the C-ABI
+//   ./test_host dump F -- pair tables and bresenham lists as JSON, for the
+//                         comparison with the reference's own output
+//                         (tests/golden/ref_pairs.json, ref_bresenham.npz)
 #include <cstdio>
 #include <cstring>
 #include <fstream>
@@ -287,7 +290,58 @@ static void gpu_tests() {
     CHECK(calculateAverageError(eng, img, 2, 2) == 2.5);
 }
 
+static void print_pairs(const std::vector<std::array<int, 2>>& v) {
+    std::printf("[");
+    for (size_t i = 0; i < v.size(); i++) std::printf("%s[%d, %d]", i ? ", " : "", v[i][0], v[i][1]);
+    std::printf("]");
+}
+
+// One JSON object on stdout: the pair tables in the layout of
+// tests/golden/ref_pairs.json, once with reference_quirks = true ("pairs") and
+// once with false ("pairs_fixed"), and the bresenham point list of every
+// "x0 y0 x1 y1" line of the given file ("bresenham").
+static void dump(const char* endpoints_file) {
+    auto cams = rig(640);
+    for (int quirks = 1; quirks >= 0; quirks--) {
+        std::printf("%s\"%s\": [\n", quirks ? "{" : ",\n", quirks ? "pairs" : "pairs_fixed");
+        for (int t = ORTHOGONAL; t <= MID_TOP; t++) {
+            std::printf(" {\"call\": \"getCameraPairs\", \"pairType\": %d, \"pairs\": ", t);
+            print_pairs(getCameraPairs(cams, (pairType)t));
+            std::printf("},\n");
+        }
+        for (int t = ORTHOGONAL; t <= MID_TOP; t++)
+            for (int n = 0; n < 25; n++) {
+                std::printf(" {\"call\": \"getCameraPairs\", \"pairType\": %d, \"cameraNum\": %d, \"pairs\": ", t, n);
+                print_pairs(getCameraPairs(cams, (pairType)t, n, quirks != 0));
+                std::printf("},\n");
+            }
+        std::printf(" {\"call\": \"getGroups\", \"groupType\": \"CHESS\", \"groups\": [");
+        auto groups = getGroups(cams, "CHESS", quirks != 0);
+        for (size_t i = 0; i < groups.size(); i++) {
+            std::printf("%s", i ? ", " : "");
+            print_pairs(groups[i]);
+        }
+        std::printf("]}\n]");
+    }
+    std::printf(",\n\"bresenham\": [");
+    std::ifstream f(endpoints_file);
+    int x0, y0, x1, y1;
+    bool first = true;
+    while (f >> x0 >> y0 >> x1 >> y1) {
+        std::printf("%s[", first ? "\n " : ",\n ");
+        first = false;
+        auto pts = bresenham({x0, y0}, {x1, y1});
+        for (size_t i = 0; i < pts.size(); i++) std::printf("%s[%d, %d]", i ? ", " : "", pts[i].x, pts[i].y);
+        std::printf("]");
+    }
+    std::printf("\n]}\n");
+}
+
 int main(int argc, char** argv) {
+    if (argc > 2 && std::strcmp(argv[1], "dump") == 0) {
+        dump(argv[2]);
+        return 0;
+    }
     const bool gpu = argc > 1 && std::strcmp(argv[1], "gpu") == 0;
     if (gpu) gpu_tests();
     else cpu_tests();

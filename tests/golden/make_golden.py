@@ -1,11 +1,12 @@
 #!/usr/bin/env python3
 """Generate the frozen regression fixtures in tests/golden/ from the CPU oracle.
 
-STATUS: these are NOT reference-generated golden vectors.  The reference
-(Nahuel-M/StereoVisionArray) ships no tests or fixtures, and its hot-path
-sources need OpenCV, which this image lacks, so it cannot be run here
-("parity unpinned").  The oracle they come from is pinned by
-the hand-derived KATs in tests/test_oracle_kat.py.  The fixtures freeze the
+STATUS: these are NOT reference-generated golden vectors; those are the
+ref_* files beside them, made by make_ref_golden.py from the reference's own
+compiled code.  The oracle these come from is pinned by the
+ref_* fixtures for Mode R and by the hand-derived KATs in
+tests/test_oracle_kat.py; for Mode S, which the reference
+(Nahuel-M/StereoVisionArray) does not have, by the KATs alone.  The fixtures freeze the
 oracle's outputs on small seeded inputs so that any later change to the
 oracle or to the kernels is caught (tests/test_golden.py checks both).
 

@@ -1,8 +1,8 @@
 """Known-answer tests that pin the CPU oracle (no GPU needed).
 
-The reference ships no tests or golden vectors and cannot be built here
-(OpenCV absent), so the oracle is "parity unpinned" with respect to the
-reference binary.  These KATs are hand-derived from the reference source
+The reference ships no tests or golden vectors.  Its own compiled code now
+pins Mode R (tests/test_reference_fixtures.py); these KATs came
+first, stay, and are all that pins Mode S.  They are hand-derived from the reference source
 (functions.cpp:253-321, Camera.cpp:15-34, CameraStereoVision.cpp:85-89) and
 from the Mode S spec; each expected value below was traced by
 hand, not produced by the code under test.

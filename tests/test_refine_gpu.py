@@ -6,8 +6,8 @@ DepthMapToPoints3D, functions.cpp:74-146).
 Bars: u8 maps bit-exact; f64 depth maps and 3-D points bit-exact (same
 operand order, no contraction, IEEE div/sqrt on both sides); scatter
 collisions resolve to the reference's loop order; untouched pixels keep the
-caller's buffer.  Parity vs the reference itself is unpinned (no fixtures,
-OpenCV absent)."""
+caller's buffer.  The oracle's parity with the reference itself is checked by
+tests/test_reference_fixtures.py (fixtures tests/golden/ref_*)."""
 import numpy as np
 import pytest
 import torch

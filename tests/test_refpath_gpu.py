@@ -1,9 +1,9 @@
 """Mode R parity: the reference's own path (CameraStereoVision.cpp:44-95) on
 the GPU vs the CPU restatement (oracle/refpath_oracle.c), bit-exact.
 
-Parity of the restatement against the reference binary is unpinned (the
-reference needs OpenCV, absent here); tests/test_oracle_kat.py pins the
-restatement by hand-derived known answers instead.
+The restatement itself is held to the reference's own compiled code by
+tests/test_reference_fixtures.py (fixtures tests/golden/ref_*)
+and to hand-derived known answers by tests/test_oracle_kat.py.
 """
 import numpy as np
 import pytest
