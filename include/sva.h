@@ -195,6 +195,25 @@ int sva_disparity_sgm_d(void* ctx, const uint8_t* left, const uint8_t* right, in
                         int height, size_t pitch, const sva_sgm_params* p, uint16_t* disp,
                         float* subpix);
 
+/* The same frame with the WTA's confidence.  cost_min: W*H
+ * u16, S(d*), the 8-path sum at the winning disparity; cost_second: W*H u16,
+ * the smallest S(d) over the caller's disparities with |d - d*| > 1, 0xFFFF
+ * when there is none (D <= 3).  Either plane may be NULL.  uniqueness = u in
+ * 0..100 (SVA_ERR_INVALID_ARG outside), 0 = off: a pixel with a cost_second
+ * and cost_second * (100 - u) < cost_min * 100 gets disp = p->invalid and
+ * subpix = NaN (the marks of lr_check); the cost planes keep their values.
+ * With lr_check the reference map is filtered first and a pixel is invalid if
+ * either test rejects it; the planes come from the reference pass.  With
+ * uniqueness = 0 the disp / subpix output equals sva_disparity_sgm*'s. */
+int sva_disparity_sgm_conf(void* ctx, const uint8_t* left, const uint8_t* right, int width,
+                           int height, size_t pitch, const sva_sgm_params* p, int uniqueness,
+                           uint16_t* disp, float* subpix, uint16_t* cost_min,
+                           uint16_t* cost_second);
+int sva_disparity_sgm_conf_d(void* ctx, const uint8_t* left, const uint8_t* right, int width,
+                             int height, size_t pitch, const sva_sgm_params* p, int uniqueness,
+                             uint16_t* disp, float* subpix, uint16_t* cost_min,
+                             uint16_t* cost_second);
+
 /* A batch of device-resident frames of one shape on this context's stream:
  * pair j matches jobs[j].left against jobs[j].right along its own step
  * (params.dir, params.dir_y), and every frame's cost volume then goes through
@@ -268,6 +287,11 @@ int sva_wta_hv_d(void* ctx, const uint8_t* C, size_t C_bytes, const uint8_t* dia
                  const sva_sgm_params* p, uint16_t* disp, float* subpix);
 int sva_wta_d(void* ctx, const uint16_t* S, int width, int height, const sva_sgm_params* p,
               uint16_t* disp, float* subpix);
+/* sva_wta_d with the confidence planes and the uniqueness filter of
+ * sva_disparity_sgm_conf_d (cost_min, cost_second nullable). */
+int sva_wta_conf_d(void* ctx, const uint16_t* S, int width, int height, const sva_sgm_params* p,
+                   int uniqueness, uint16_t* disp, float* subpix, uint16_t* cost_min,
+                   uint16_t* cost_second);
 
 /* -------------------------------------------- Mode R (reference parity) --- */
 /* The reference's own path, bit-exact: per pixel the t_near/t_far ray ends
@@ -402,6 +426,27 @@ int sva_fuse_depth_d(void* ctx, const uint16_t* disps, int n_maps, int width, in
 int sva_fuse_depth(void* ctx, const uint16_t* disps, int n_maps, int width, int height,
                    const double* baselines, double f, double pixel_size, uint16_t invalid,
                    double* depth, uint8_t* n_valid);
+
+/* Cost-aware fusion (SURVEY.md §8e "or min-cost"): per pixel
+ * the depth baseline_i * f / (disp_i * pixel_size) of ONE map, chosen among
+ * the maps valid there (disp_i != invalid, disp_i > 0) by the confidence
+ * planes of sva_disparity_sgm_conf*: SVA_FUSE_MIN_COST the smallest cost_min,
+ * SVA_FUSE_MAX_MARGIN the largest cost_second - cost_min (unsigned 32-bit,
+ * 0xFFFF as is); ties go to the lowest map index; 0 if no map is valid.
+ * disps, cost_min, cost_second: [n_maps][H][W] u16 (cost_second may be NULL
+ * for SVA_FUSE_MIN_COST); n_maps <= 32; n_valid, winner (the chosen map's
+ * index, 0xFF if none) nullable.  A NULL cost_second with MAX_MARGIN, another
+ * mode or n_maps outside 1..32 return SVA_ERR_INVALID_ARG. */
+#define SVA_FUSE_MIN_COST 0
+#define SVA_FUSE_MAX_MARGIN 1
+int sva_fuse_depth_conf_d(void* ctx, const uint16_t* disps, const uint16_t* cost_min,
+                          const uint16_t* cost_second, int n_maps, int width, int height,
+                          const double* baselines, double f, double pixel_size, uint16_t invalid,
+                          int mode, double* depth, uint8_t* n_valid, uint8_t* winner);
+int sva_fuse_depth_conf(void* ctx, const uint16_t* disps, const uint16_t* cost_min,
+                        const uint16_t* cost_second, int n_maps, int width, int height,
+                        const double* baselines, double f, double pixel_size, uint16_t invalid,
+                        int mode, double* depth, uint8_t* n_valid, uint8_t* winner);
 
 /* Disparity -> depth, CameraStereoVision.cpp:47,98-100 (f64; 0 where disp 0). */
 int sva_disparity_to_depth_d(void* ctx, const uint8_t* disp, int n, double cam_distance,

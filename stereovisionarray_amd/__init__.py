@@ -63,8 +63,11 @@ EXPORTED = [
     "sva_tile_check", "sva_paths_tile_d", "sva_wta_hv_d", "sva_multi_create", "sva_multi_destroy",
     "sva_multi_synchronize", "sva_multi_last_error", "sva_multi_plan", "sva_multi_context",
     "sva_batch_sgm_d", "sva_array_depth", "sva_disparity_sgm_batch_d", "sva_set_debug",
-    "sva_get_debug",
+    "sva_get_debug", "sva_disparity_sgm_conf", "sva_disparity_sgm_conf_d", "sva_wta_conf_d",
+    "sva_fuse_depth_conf", "sva_fuse_depth_conf_d",
 ]
+SVA_FUSE_MIN_COST = 0
+SVA_FUSE_MAX_MARGIN = 1
 SVA_MULTI_GATHER_RCCL = 0
 SVA_MULTI_GATHER_PEER = 1
 SVA_MULTI_GATHER_ALL = 2
@@ -169,6 +172,15 @@ def _load() -> ct.CDLL:
         "sva_get_debug": (i32, [vp, i32, P(ct.c_int64)]),
         "sva_disparity_sgm": (i32, [vp, vp, vp, i32, i32, sz, P(SgmParams), vp, vp]),
         "sva_disparity_sgm_d": (i32, [vp, vp, vp, i32, i32, sz, P(SgmParams), vp, vp]),
+        "sva_disparity_sgm_conf": (i32, [vp, vp, vp, i32, i32, sz, P(SgmParams), i32, vp, vp, vp,
+                                         vp]),
+        "sva_disparity_sgm_conf_d": (i32, [vp, vp, vp, i32, i32, sz, P(SgmParams), i32, vp, vp,
+                                           vp, vp]),
+        "sva_wta_conf_d": (i32, [vp, vp, i32, i32, P(SgmParams), i32, vp, vp, vp, vp]),
+        "sva_fuse_depth_conf_d": (i32, [vp, vp, vp, vp, i32, i32, i32, P(dbl), dbl, dbl,
+                                        ct.c_uint16, i32, vp, vp, vp]),
+        "sva_fuse_depth_conf": (i32, [vp, vp, vp, vp, i32, i32, i32, P(dbl), dbl, dbl,
+                                      ct.c_uint16, i32, vp, vp, vp]),
         "sva_census_d": (i32, [vp, vp, i32, i32, sz, vp]),
         "sva_cost_d": (i32, [vp, vp, vp, i32, i32, P(SgmParams), vp]),
         "sva_paths_d": (i32, [vp, vp, i32, i32, P(SgmParams), vp]),
@@ -375,6 +387,37 @@ class Context:
         self._chk(lib.sva_disparity_sgm_d(self.h, _ptr(left), _ptr(right), W, H, pitch,
                                           ct.byref(params), _ptr(disp), _ptr(sub)))
 
+    # -- Mode S with the WTA's confidence planes and the uniqueness filter
+    def disparity_sgm_conf(self, left: np.ndarray, right: np.ndarray, params: SgmParams,
+                           uniqueness: int = 0):
+        """(disp, sub, cost_min, cost_second): sva_disparity_sgm_conf.  cost_min =
+        S(d*), cost_second = min S(d) over |d - d*| > 1 (0xFFFF if none);
+        uniqueness = u in 0..100 rejects pixels with cost_second * (100 - u) <
+        cost_min * 100 (disp = params.invalid, sub = NaN)."""
+        assert left.dtype == np.uint8 and right.dtype == np.uint8 and left.shape == right.shape
+        left = np.ascontiguousarray(left)
+        right = np.ascontiguousarray(right)
+        H, W = left.shape
+        disp = np.zeros((H, W), np.uint16)
+        sub = np.zeros((H, W), np.float32) if params.subpixel else None
+        cmin = np.zeros((H, W), np.uint16)
+        csec = np.zeros((H, W), np.uint16)
+        self._chk(lib.sva_disparity_sgm_conf(self.h, _ptr(left), _ptr(right), W, H, W,
+                                             ct.byref(params), int(uniqueness), _ptr(disp),
+                                             _ptr(sub), _ptr(cmin), _ptr(csec)))
+        return disp, sub, cmin, csec
+
+    def disparity_sgm_conf_d(self, left, right, W, H, pitch, params, uniqueness, disp, sub=None,
+                             cost_min=None, cost_second=None):
+        self._chk(lib.sva_disparity_sgm_conf_d(self.h, _ptr(left), _ptr(right), W, H, pitch,
+                                               ct.byref(params), int(uniqueness), _ptr(disp),
+                                               _ptr(sub), _ptr(cost_min), _ptr(cost_second)))
+
+    def wta_conf_d(self, S, W, H, params, uniqueness, disp, sub=None, cost_min=None,
+                   cost_second=None):
+        self._chk(lib.sva_wta_conf_d(self.h, _ptr(S), W, H, ct.byref(params), int(uniqueness),
+                                     _ptr(disp), _ptr(sub), _ptr(cost_min), _ptr(cost_second)))
+
     def disparity_sgm_batch_d(self, pairs, W, H, pitch, maps, sub=None):
         """pairs: list of (left_ptr, right_ptr, SgmParams) on this context's device;
         maps: [n][H][W] u16 device, sub: [n][H][W] f32 device or None."""
@@ -580,6 +623,33 @@ class Context:
         b = (ct.c_double * n_maps)(*[float(v) for v in baselines])
         self._chk(lib.sva_fuse_depth_d(self.h, _ptr(disps), n_maps, W, H, b, f, pixel_size,
                                        invalid, _ptr(depth), _ptr(n_valid)))
+
+    def fuse_depth_conf(self, disps: np.ndarray, cost_min: np.ndarray, cost_second, baselines,
+                        f, pixel_size, invalid=0xFFFF, mode=SVA_FUSE_MIN_COST):
+        """(depth, n_valid, winner): sva_fuse_depth_conf, the depth of the valid
+        map with the smallest cost_min (SVA_FUSE_MIN_COST; cost_second may be
+        None) or the largest cost_second - cost_min (SVA_FUSE_MAX_MARGIN)."""
+        d = np.ascontiguousarray(disps, dtype=np.uint16)
+        cm = np.ascontiguousarray(cost_min, dtype=np.uint16)
+        cs = None if cost_second is None else np.ascontiguousarray(cost_second, dtype=np.uint16)
+        N, H, W = d.shape
+        assert cm.shape == d.shape and (cs is None or cs.shape == d.shape)
+        b = (ct.c_double * max(1, N))(*[float(v) for v in baselines])
+        out = np.zeros((H, W), np.float64)
+        nv = np.zeros((H, W), np.uint8)
+        win = np.zeros((H, W), np.uint8)
+        self._chk(lib.sva_fuse_depth_conf(self.h, _ptr(d), _ptr(cm), _ptr(cs), N, W, H, b, f,
+                                          pixel_size, invalid, int(mode), _ptr(out), _ptr(nv),
+                                          _ptr(win)))
+        return out, nv, win
+
+    def fuse_depth_conf_d(self, disps, cost_min, cost_second, n_maps, W, H, baselines, f,
+                          pixel_size, invalid, mode, depth, n_valid=None, winner=None):
+        b = (ct.c_double * max(1, n_maps))(*[float(v) for v in baselines])
+        self._chk(lib.sva_fuse_depth_conf_d(self.h, _ptr(disps), _ptr(cost_min),
+                                            _ptr(cost_second), n_maps, W, H, b, f, pixel_size,
+                                            invalid, int(mode), _ptr(depth), _ptr(n_valid),
+                                            _ptr(winner)))
 
     def disparity_to_depth(self, disp: np.ndarray, cam_distance, f, pixel_size):
         d = np.ascontiguousarray(disp, dtype=np.uint8)

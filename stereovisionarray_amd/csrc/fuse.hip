@@ -9,6 +9,8 @@
 // spills to scratch.  Invalid entries are +inf and rank after every valid one.
 // HBM bytes per pixel: 2 * n_maps read + 9 written.  f64 without contraction,
 // IEEE division: the same bits as the oracle's insertion sort + mean.
+// fuse_depth_conf_kernel (§2.6b) picks one map per pixel by the WTA's
+// confidence planes instead: min-cost or max-margin.
 #include "sva_internal.h"
 
 #pragma clang fp contract(off)
@@ -52,7 +54,73 @@ __global__ __launch_bounds__(256) void fuse_depth_kernel(const uint16_t* __restr
     if (n_valid) n_valid[p] = (uint8_t)n;
 }
 
+// Cost-aware fusion: the depth of ONE map per pixel, the
+// valid map (§2.6's rule) with the smallest cost_min (MARGIN = false) or the
+// largest cost_second - cost_min in u32 (MARGIN = true); ties go to the lowest
+// map index (the scan is ascending and only a strictly better map replaces the
+// winner).  The winner's disparity, numerator and index move through selects,
+// so nothing is indexed by data.  Bytes per pixel: 4 or 6 * n_maps read, 10
+// written.  The same f64 expression as the median kernel, no contraction.
+template <int NM, bool MARGIN>
+__global__ __launch_bounds__(256) void fuse_depth_conf_kernel(
+    const uint16_t* __restrict__ disps, const uint16_t* __restrict__ cost_min,
+    const uint16_t* __restrict__ cost_second, int n_maps, size_t np, FuseNum num,
+    double pixel_size, uint16_t invalid, double* __restrict__ depth,
+    uint8_t* __restrict__ n_valid, uint8_t* __restrict__ winner) {
+    const size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= np) return;
+    int n = 0, wi = 0xff;
+    unsigned wd = 0u, wscore = 0u;
+    double wnum = 0.0;
+#pragma unroll
+    for (int i = 0; i < NM; i++) {
+        const bool in = i < n_maps;
+        const unsigned d = in ? disps[(size_t)i * np + p] : invalid;
+        const bool ok = d != invalid && d != 0;
+        unsigned score = in ? cost_min[(size_t)i * np + p] : 0u;
+        if constexpr (MARGIN) score = (in ? (unsigned)cost_second[(size_t)i * np + p] : 0u) - score;
+        const bool take = ok && (n == 0 || (MARGIN ? score > wscore : score < wscore));
+        wd = take ? d : wd;
+        wscore = take ? score : wscore;
+        wnum = take ? num.v[i] : wnum;
+        wi = take ? i : wi;
+        n += ok;
+    }
+    depth[p] = n == 0 ? 0.0 : wnum / ((double)wd * pixel_size);
+    if (n_valid) n_valid[p] = (uint8_t)n;
+    if (winner) winner[p] = (uint8_t)wi;
+}
+
 }  // namespace
+
+hipError_t launch_fuse_depth_conf(Ctx& c, const uint16_t* disps, const uint16_t* cost_min,
+                                  const uint16_t* cost_second, int n_maps, size_t np,
+                                  const double* num, double pixel_size, uint16_t invalid, int mode,
+                                  double* depth, uint8_t* n_valid, uint8_t* winner) {
+    if (n_maps < 1 || n_maps > 32) return hipErrorInvalidValue;
+    if (mode != SVA_FUSE_MIN_COST && mode != SVA_FUSE_MAX_MARGIN) return hipErrorInvalidValue;
+    if (mode == SVA_FUSE_MAX_MARGIN && !cost_second) return hipErrorInvalidValue;
+    ScopedKernelTimer t(c, "fuse_depth_conf");
+    FuseNum k{};
+    for (int i = 0; i < n_maps; i++) k.v[i] = num[i];
+    const dim3 grid((unsigned)((np + 255) / 256));
+#define SVA_FUSE_C(NM, MG)                                                                       \
+    hipLaunchKernelGGL((fuse_depth_conf_kernel<NM, MG>), grid, dim3(256), 0, c.stream, disps,    \
+                       cost_min, cost_second, n_maps, np, k, pixel_size, invalid, depth, n_valid, \
+                       winner)
+#define SVA_FUSE_N(MG)                    \
+    do {                                  \
+        if (n_maps <= 4) SVA_FUSE_C(4, MG);        \
+        else if (n_maps <= 8) SVA_FUSE_C(8, MG);   \
+        else if (n_maps <= 16) SVA_FUSE_C(16, MG); \
+        else SVA_FUSE_C(32, MG);                   \
+    } while (0)
+    if (mode == SVA_FUSE_MAX_MARGIN) SVA_FUSE_N(true);
+    else SVA_FUSE_N(false);
+#undef SVA_FUSE_N
+#undef SVA_FUSE_C
+    return hipGetLastError();
+}
 
 hipError_t launch_fuse_depth(Ctx& c, const uint16_t* disps, int n_maps, size_t np,
                              const double* num, double pixel_size, uint16_t invalid,

@@ -186,8 +186,9 @@ size_t frame_minima_bytes(const TileGeom& tg, int Dp) {
     return path_minima_enabled(Dp) ? tg.hmn_bytes + tg.vmn_bytes : 0;
 }
 
+// cf set: wta_hv's confidence instance instead of the plain one.
 int paths_wta(Ctx* c, const uint8_t* C, int W, int H, const sva_sgm_params* p, int Dp,
-              uint16_t* disp, float* sub) {
+              uint16_t* disp, float* sub, const ConfOut* cf = nullptr) {
     if (!wta_hv_supported(Dp)) return fail(c, SVA_ERR_UNSUPPORTED, "no tile pipeline for this D");
     const size_t nv = (size_t)W * H * (size_t)Dp;
     const TileGeom tg = tile_geom(W, H, Dp);
@@ -209,7 +210,7 @@ int paths_wta(Ctx* c, const uint8_t* C, int W, int H, const sva_sgm_params* p, i
     SVA_HIP(c, launch_paths(*c, C, W, H, Dp, p->P1, p->P2, L4, CK, CKV, 1, pair, p->D, MN),
             "paths launch");
     SVA_HIP(c, launch_wta_hv(*c, C, L4, CK, CKV, W, H, Dp, p->P1, p->P2, p->dmin, disp, sub, p->D, 1,
-                             pair, MN),
+                             pair, MN, cf),
             "wta launch");
     c->last_diag_route = pair ? 1 : 0;
     return SVA_OK;
@@ -253,8 +254,13 @@ int check_tile_buffers(Ctx* c, int W, int H, int D, const void* C, size_t C_byte
 // Mode S on device buffers: census -> cost -> 8 paths -> WTA (-> L/R check).
 // Any D in 1..256 runs at the native width Dp = padded_D(D): the cost kernels
 // write 255 at d >= D and the WTA ignores those disparities.
+// cf set (sva_disparity_sgm_conf*): the reference pass runs the confidence
+// instance, which writes the cost planes and applies the uniqueness filter;
+// the right-referenced pass of the L/R check stays the plain instance, and
+// lr_check_kernel keeps the pixels the filter already marked invalid.
 int run_sgm_device(Ctx* c, const uint8_t* left, const uint8_t* right, int W, int H, size_t pitch,
-                   const sva_sgm_params* p, uint16_t* disp, float* sub) {
+                   const sva_sgm_params* p, uint16_t* disp, float* sub,
+                   const ConfOut* cf = nullptr) {
     const int Dp = padded_D(p->D);
     const size_t np = (size_t)W * H, nv = np * (size_t)Dp;
     int s;
@@ -270,7 +276,7 @@ int run_sgm_device(Ctx* c, const uint8_t* left, const uint8_t* right, int W, int
         // once per matching role when the L/R check runs.
         SVA_HIP(c, launch_census_cost(*c, left, right, W, H, pitch, Dp, p->dmin, p->dir, C, p->D),
                 "cost launch");
-        if ((s = paths_wta(c, C, W, H, p, Dp, disp, sub))) return s;
+        if ((s = paths_wta(c, C, W, H, p, Dp, disp, sub, cf))) return s;
         if (p->lr_check) {
             // right image as reference: the images swap roles, the step flips
             SVA_HIP(c, launch_census_cost(*c, right, left, W, H, pitch, Dp, p->dmin, -p->dir, C,
@@ -290,7 +296,7 @@ int run_sgm_device(Ctx* c, const uint8_t* left, const uint8_t* right, int W, int
         SVA_HIP(c, launch_census_cost2(*c, left, right, W, H, pitch, Dp, p->dmin, p->dir,
                                        p->dir_y, C, p->D),
                 "cost launch");
-        if ((s = paths_wta(c, C, W, H, p, Dp, disp, sub))) return s;
+        if ((s = paths_wta(c, C, W, H, p, Dp, disp, sub, cf))) return s;
         if (p->lr_check) {
             SVA_HIP(c, launch_census_cost2(*c, right, left, W, H, pitch, Dp, p->dmin, -p->dir,
                                            -p->dir_y, C, p->D),
@@ -309,7 +315,7 @@ int run_sgm_device(Ctx* c, const uint8_t* left, const uint8_t* right, int W, int
     SVA_HIP(c, launch_census_pair(*c, left, right, W, H, pitch, cl, cr), "census launch");
     SVA_HIP(c, launch_cost2(*c, cl, cr, W, H, Dp, p->dmin, p->dir, p->dir_y, C, p->D),
             "cost launch");
-    if ((s = paths_wta(c, C, W, H, p, Dp, disp, sub))) return s;
+    if ((s = paths_wta(c, C, W, H, p, Dp, disp, sub, cf))) return s;
     if (p->lr_check) {
         // right image as reference: roles of the census maps swap, the step flips
         SVA_HIP(c, launch_cost2(*c, cr, cl, W, H, Dp, p->dmin, -p->dir, -p->dir_y, C, p->D),
@@ -937,6 +943,81 @@ int sva_disparity_sgm(void* ctx, const uint8_t* left, const uint8_t* right, int 
     return SVA_OK;
 }
 
+// Mode S with the WTA's confidence planes and the uniqueness filter (DESIGN.md
+// §2.4b): the frame route with wta_hv's confidence instance.
+namespace {
+int check_uniqueness(Ctx* c, int uniqueness) {
+    if (uniqueness < 0 || uniqueness > 100)
+        return fail(c, SVA_ERR_INVALID_ARG, "uniqueness must be 0..100 (percent, 0 = off)");
+    return SVA_OK;
+}
+}  // namespace
+
+int sva_disparity_sgm_conf_d(void* ctx, const uint8_t* left, const uint8_t* right, int W, int H,
+                             size_t pitch, const sva_sgm_params* p, int uniqueness, uint16_t* disp,
+                             float* sub, uint16_t* cost_min, uint16_t* cost_second) {
+    Ctx* c = as_ctx(ctx);
+    SVA_CHECK_CTX(c);
+    int s;
+    if ((s = check_image(c, left, W, H, pitch)) || (s = check_image(c, right, W, H, pitch)) ||
+        (s = check_sgm(c, p, W, H)) || (s = check_uniqueness(c, uniqueness)))
+        return s;
+    if (!disp) return fail(c, SVA_ERR_INVALID_ARG, "null disparity output");
+    ConfOut cf;
+    cf.cost_min = cost_min;
+    cf.cost_second = cost_second;
+    cf.uniqueness = uniqueness;
+    cf.invalid = p->invalid;
+    return run_sgm_device(c, left, right, W, H, pitch, p, disp, p->subpixel ? sub : nullptr, &cf);
+}
+
+int sva_disparity_sgm_conf(void* ctx, const uint8_t* left, const uint8_t* right, int W, int H,
+                           size_t pitch, const sva_sgm_params* p, int uniqueness, uint16_t* disp,
+                           float* sub, uint16_t* cost_min, uint16_t* cost_second) {
+    Ctx* c = as_ctx(ctx);
+    SVA_CHECK_CTX(c);
+    int s;
+    if ((s = check_image(c, left, W, H, pitch)) || (s = check_image(c, right, W, H, pitch)) ||
+        (s = check_sgm(c, p, W, H)) || (s = check_uniqueness(c, uniqueness)))
+        return s;
+    if (!disp) return fail(c, SVA_ERR_INVALID_ARG, "null disparity output");
+    const bool want_sub = p->subpixel && sub;
+    const size_t np = (size_t)W * H;
+    SVA_HIP(c, c->in_a.ensure(np), "staging");
+    SVA_HIP(c, c->in_b.ensure(np), "staging");
+    SVA_HIP(c, c->out_a.ensure(np * 2), "staging");
+    if (want_sub) SVA_HIP(c, c->out_b.ensure(np * 4), "staging");
+    // the two cost planes share one staging buffer
+    if (cost_min || cost_second) SVA_HIP(c, c->out_c.ensure(np * 4), "staging");
+    ConfOut cf;
+    cf.cost_min = cost_min ? (uint16_t*)c->out_c.ptr : nullptr;
+    cf.cost_second = cost_second ? (uint16_t*)c->out_c.ptr + np : nullptr;
+    cf.uniqueness = uniqueness;
+    cf.invalid = p->invalid;
+    SVA_HIP(c, hipMemcpy2DAsync(c->in_a.ptr, W, left, pitch, W, H, hipMemcpyHostToDevice, c->stream),
+            "upload");
+    SVA_HIP(c, hipMemcpy2DAsync(c->in_b.ptr, W, right, pitch, W, H, hipMemcpyHostToDevice, c->stream),
+            "upload");
+    if ((s = run_sgm_device(c, (uint8_t*)c->in_a.ptr, (uint8_t*)c->in_b.ptr, W, H, W, p,
+                            (uint16_t*)c->out_a.ptr, want_sub ? (float*)c->out_b.ptr : nullptr,
+                            &cf)))
+        return s;
+    SVA_HIP(c, hipMemcpyAsync(disp, c->out_a.ptr, np * 2, hipMemcpyDeviceToHost, c->stream),
+            "download");
+    if (want_sub)
+        SVA_HIP(c, hipMemcpyAsync(sub, c->out_b.ptr, np * 4, hipMemcpyDeviceToHost, c->stream),
+                "download");
+    if (cost_min)
+        SVA_HIP(c, hipMemcpyAsync(cost_min, cf.cost_min, np * 2, hipMemcpyDeviceToHost, c->stream),
+                "download");
+    if (cost_second)
+        SVA_HIP(c, hipMemcpyAsync(cost_second, cf.cost_second, np * 2, hipMemcpyDeviceToHost,
+                                  c->stream),
+                "download");
+    SVA_HIP(c, hipStreamSynchronize(c->stream), "sync");
+    return SVA_OK;
+}
+
 int sva_census_d(void* ctx, const uint8_t* img, int W, int H, size_t pitch, uint64_t* census) {
     Ctx* c = as_ctx(ctx);
     SVA_CHECK_CTX(c);
@@ -1060,6 +1141,25 @@ int sva_wta_d(void* ctx, const uint16_t* S, int W, int H, const sva_sgm_params* 
     if ((s = check_sgm(c, p, W, H, true))) return s;
     if (!S || !disp || W <= 0 || H <= 0) return fail(c, SVA_ERR_INVALID_ARG, "bad argument");
     SVA_HIP(c, launch_wta_from_sum(*c, S, W, H, p->D, p->dmin, disp, p->subpixel ? sub : nullptr),
+            "wta launch");
+    return SVA_OK;
+}
+
+int sva_wta_conf_d(void* ctx, const uint16_t* S, int W, int H, const sva_sgm_params* p,
+                   int uniqueness, uint16_t* disp, float* sub, uint16_t* cost_min,
+                   uint16_t* cost_second) {
+    Ctx* c = as_ctx(ctx);
+    SVA_CHECK_CTX(c);
+    int s;
+    if ((s = check_sgm(c, p, W, H, true)) || (s = check_uniqueness(c, uniqueness))) return s;
+    if (!S || !disp || W <= 0 || H <= 0) return fail(c, SVA_ERR_INVALID_ARG, "bad argument");
+    ConfOut cf;
+    cf.cost_min = cost_min;
+    cf.cost_second = cost_second;
+    cf.uniqueness = uniqueness;
+    cf.invalid = p->invalid;
+    SVA_HIP(c, launch_wta_from_sum(*c, S, W, H, p->D, p->dmin, disp, p->subpixel ? sub : nullptr,
+                                   &cf),
             "wta launch");
     return SVA_OK;
 }
@@ -1206,6 +1306,81 @@ int sva_fuse_depth(void* ctx, const uint16_t* disps, int n_maps, int W, int H,
             "download");
     if (n_valid)
         SVA_HIP(c, hipMemcpyAsync(n_valid, c->out_b.ptr, np, hipMemcpyDeviceToHost, c->stream),
+                "download");
+    SVA_HIP(c, hipStreamSynchronize(c->stream), "sync");
+    return SVA_OK;
+}
+
+// Cost-aware fusion.
+static int check_fuse_conf(Ctx* c, const uint16_t* disps, const uint16_t* cost_min,
+                    const uint16_t* cost_second, int n_maps, int W, int H, const double* b,
+                    int mode, const double* depth) {
+    if (!disps || !cost_min || !b || !depth) return fail(c, SVA_ERR_INVALID_ARG, "null pointer");
+    if (mode != SVA_FUSE_MIN_COST && mode != SVA_FUSE_MAX_MARGIN)
+        return fail(c, SVA_ERR_INVALID_ARG, "mode must be SVA_FUSE_MIN_COST or SVA_FUSE_MAX_MARGIN");
+    if (mode == SVA_FUSE_MAX_MARGIN && !cost_second)
+        return fail(c, SVA_ERR_INVALID_ARG, "SVA_FUSE_MAX_MARGIN needs the cost_second planes");
+    if (n_maps < 1 || n_maps > 32) return fail(c, SVA_ERR_INVALID_ARG, "n_maps must be 1..32");
+    if (W <= 0 || H <= 0) return fail(c, SVA_ERR_INVALID_ARG, "image size must be positive");
+    return SVA_OK;
+}
+
+int sva_fuse_depth_conf_d(void* ctx, const uint16_t* disps, const uint16_t* cost_min,
+                          const uint16_t* cost_second, int n_maps, int W, int H,
+                          const double* baselines, double f, double pixel_size, uint16_t invalid,
+                          int mode, double* depth, uint8_t* n_valid, uint8_t* winner) {
+    Ctx* c = as_ctx(ctx);
+    SVA_CHECK_CTX(c);
+    int s;
+    if ((s = check_fuse_conf(c, disps, cost_min, cost_second, n_maps, W, H, baselines, mode, depth)))
+        return s;
+    double num[32];
+    for (int i = 0; i < n_maps; i++) num[i] = baselines[i] * f;
+    SVA_HIP(c, launch_fuse_depth_conf(*c, disps, cost_min, cost_second, n_maps, (size_t)W * H, num,
+                                      pixel_size, invalid, mode, depth, n_valid, winner),
+            "fuse launch");
+    return SVA_OK;
+}
+
+int sva_fuse_depth_conf(void* ctx, const uint16_t* disps, const uint16_t* cost_min,
+                        const uint16_t* cost_second, int n_maps, int W, int H,
+                        const double* baselines, double f, double pixel_size, uint16_t invalid,
+                        int mode, double* depth, uint8_t* n_valid, uint8_t* winner) {
+    Ctx* c = as_ctx(ctx);
+    SVA_CHECK_CTX(c);
+    int s;
+    if ((s = check_fuse_conf(c, disps, cost_min, cost_second, n_maps, W, H, baselines, mode, depth)))
+        return s;
+    const size_t np = (size_t)W * H, in_bytes = np * 2 * (size_t)n_maps;
+    double num[32];
+    for (int i = 0; i < n_maps; i++) num[i] = baselines[i] * f;
+    SVA_HIP(c, c->in_a.ensure(in_bytes), "staging");
+    SVA_HIP(c, c->in_b.ensure(in_bytes), "staging");
+    if (cost_second) SVA_HIP(c, c->in_c.ensure(in_bytes), "staging");
+    SVA_HIP(c, c->out_a.ensure(np * 8), "staging");
+    SVA_HIP(c, c->out_b.ensure(np), "staging");
+    SVA_HIP(c, c->out_c.ensure(np), "staging");
+    SVA_HIP(c, hipMemcpyAsync(c->in_a.ptr, disps, in_bytes, hipMemcpyHostToDevice, c->stream),
+            "upload");
+    SVA_HIP(c, hipMemcpyAsync(c->in_b.ptr, cost_min, in_bytes, hipMemcpyHostToDevice, c->stream),
+            "upload");
+    if (cost_second)
+        SVA_HIP(c, hipMemcpyAsync(c->in_c.ptr, cost_second, in_bytes, hipMemcpyHostToDevice,
+                                  c->stream),
+                "upload");
+    SVA_HIP(c, launch_fuse_depth_conf(*c, (const uint16_t*)c->in_a.ptr,
+                                      (const uint16_t*)c->in_b.ptr,
+                                      cost_second ? (const uint16_t*)c->in_c.ptr : nullptr, n_maps,
+                                      np, num, pixel_size, invalid, mode, (double*)c->out_a.ptr,
+                                      (uint8_t*)c->out_b.ptr, (uint8_t*)c->out_c.ptr),
+            "fuse launch");
+    SVA_HIP(c, hipMemcpyAsync(depth, c->out_a.ptr, np * 8, hipMemcpyDeviceToHost, c->stream),
+            "download");
+    if (n_valid)
+        SVA_HIP(c, hipMemcpyAsync(n_valid, c->out_b.ptr, np, hipMemcpyDeviceToHost, c->stream),
+                "download");
+    if (winner)
+        SVA_HIP(c, hipMemcpyAsync(winner, c->out_c.ptr, np, hipMemcpyDeviceToHost, c->stream),
                 "download");
     SVA_HIP(c, hipStreamSynchronize(c->stream), "sync");
     return SVA_OK;

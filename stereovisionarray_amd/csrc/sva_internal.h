@@ -219,17 +219,28 @@ inline int padded_D(int D) {
 // four diagonal volumes L4, WTA.  dreal < D: a padded frame (DESIGN.md
 // §4.7), WTA over d < dreal only.
 bool wta_hv_supported(int D);
+// The WTA's confidence outputs, a kernel argument of the
+// confidence instances: W*H u16 planes (each nullable), the uniqueness
+// percentage 0..100 (0 = no filter) and the disparity a rejected pixel gets.
+struct ConfOut {
+    uint16_t* cost_min = nullptr;
+    uint16_t* cost_second = nullptr;
+    int uniqueness = 0;
+    unsigned invalid = 0xffffu;
+};
 // pair: L4 holds the pair route's two pair-sum volumes (one frame).
 // MN: the minima planes of launch_paths(.., MN) for the same frame; the
 // recurrences read each step's m there (one frame, path_minima_enabled).
+// cf set (one frame): the confidence instance of the same kernel.
 hipError_t launch_wta_hv(Ctx& c, const uint8_t* C, const uint8_t* L4, const uint8_t* CK,
                          const uint8_t* CKV, int W, int H, int D, int P1, int P2, int dmin,
                          uint16_t* disp, float* sub, int dreal = 0, int npair = 1,
-                         bool pair = false, const uint8_t* MN = nullptr);
+                         bool pair = false, const uint8_t* MN = nullptr,
+                         const ConfOut* cf = nullptr);
 // wta.hip
 hipError_t launch_sum(Ctx& c, const uint8_t* L8, int W, int H, int D, uint16_t* S);
 hipError_t launch_wta_from_sum(Ctx& c, const uint16_t* S, int W, int H, int D, int dmin,
-                               uint16_t* disp, float* sub);
+                               uint16_t* disp, float* sub, const ConfOut* cf = nullptr);
 hipError_t launch_lr_check(Ctx& c, uint16_t* disp_l, const uint16_t* disp_r, float* sub, int W, int H,
                            int sx, int sy, int max_diff, uint16_t invalid);
 // 2-D matching step (sy != 0); sy == 0 forwards to launch_cost(dir = sx).
@@ -240,6 +251,14 @@ hipError_t launch_cost2(Ctx& c, const uint64_t* cl, const uint64_t* cr, int W, i
 hipError_t launch_fuse_depth(Ctx& c, const uint16_t* disps, int n_maps, size_t np,
                              const double* num, double pixel_size, uint16_t invalid,
                              double* depth, uint8_t* n_valid);
+// Cost-aware fusion: per pixel the depth of the valid map
+// with the smallest cost_min (mode SVA_FUSE_MIN_COST; cost_second nullable)
+// or the largest cost_second - cost_min (SVA_FUSE_MAX_MARGIN); winner
+// (nullable) gets its index, 0xFF if none.
+hipError_t launch_fuse_depth_conf(Ctx& c, const uint16_t* disps, const uint16_t* cost_min,
+                                  const uint16_t* cost_second, int n_maps, size_t np,
+                                  const double* num, double pixel_size, uint16_t invalid, int mode,
+                                  double* depth, uint8_t* n_valid, uint8_t* winner);
 // refpath.hip
 hipError_t launch_ref_endpoints(Ctx& c, int W, int H, const sva_camera& cref,
                                 const sva_camera& coth, int k, double t_near, double t_far,

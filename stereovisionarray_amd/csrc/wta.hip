@@ -5,8 +5,8 @@
 // holds disparities [k*DPL, k*DPL+DPL).  S = sum of the 8 u8 path volumes is
 // formed in packed u16 (no carry: S <= 8*255 < 2^16); the pick is
 // wta_common.h's.  These kernels serve the stage API (sva_wta_d,
-// sva_aggregate_d); the frame pipeline uses wta_hv.hip, which also recomputes
-// the horizontal paths.
+// sva_wta_conf_d, sva_aggregate_d); the frame pipeline uses wta_hv.hip, which
+// also recomputes the horizontal paths.
 #include "sva_device.h"
 #include "sva_internal.h"
 #include "wta_common.h"
@@ -111,6 +111,35 @@ __global__ __launch_bounds__(BLOCK) void wta_sum_kernel(const uint16_t* __restri
     wta_finish<DPL>(S, k, D, dmin, pix, disp, sub);
 }
 
+// The confidence form of the S-volume stage: the same pick,
+// then cost_second over the same keys, the two planes (each nullable) and the
+// uniqueness filter on the values lane 0 writes.
+template <int DPL>
+__global__ __launch_bounds__(BLOCK) void wta_sum_conf_kernel(const uint16_t* __restrict__ Sin,
+                                                             int npix, int D, int dmin,
+                                                             uint16_t* __restrict__ disp,
+                                                             float* __restrict__ sub, ConfOut cf) {
+    const size_t pix = (size_t)blockIdx.x * PIX_PER_BLOCK + (threadIdx.x >> 4);
+    const int k = threadIdx.x & 15;
+    if (pix >= (size_t)npix) return;
+    unsigned S[DPL / 2];
+    const unsigned* s = (const unsigned*)(Sin + pix * D + k * DPL);
+#pragma unroll
+    for (int j = 0; j < DPL / 2; j++) S[j] = s[j];
+    unsigned spm = 0, s0 = 0;
+    const int ds = wta_pick_raw<DPL>(S, k, true, &spm, &s0);
+    const unsigned s2 = wta_second_raw<DPL>(S, k, ds);
+    if (k == 0) {
+        if (cf.cost_min) cf.cost_min[pix] = (uint16_t)s0;
+        if (cf.cost_second) cf.cost_second[pix] = (uint16_t)s2;
+        const bool rej = conf_reject(s0, s2, cf.uniqueness);
+        disp[pix] = rej ? (uint16_t)cf.invalid : (uint16_t)(dmin + ds);
+        if (sub)
+            sub[pix] = rej ? __builtin_nanf("")
+                           : subpixel(dmin, ds, D, spm & 0xffffu, s0, spm >> 16);
+    }
+}
+
 // DESIGN.md §2.5.  The sub-pixel map (nullable) follows the check: NaN
 // wherever the disparity is `invalid` afterwards (oracle svo_lr_sub).
 __global__ void lr_check_kernel(uint16_t* __restrict__ dl, const uint16_t* __restrict__ dr,
@@ -157,10 +186,15 @@ hipError_t launch_sum(Ctx& c, const uint8_t* L8, int W, int H, int D, uint16_t* 
 }
 
 hipError_t launch_wta_from_sum(Ctx& c, const uint16_t* S, int W, int H, int D, int dmin,
-                               uint16_t* disp, float* sub) {
+                               uint16_t* disp, float* sub, const ConfOut* cf) {
     ScopedKernelTimer t(c, "wta_sum");
     const int npix = W * H;
     dim3 grid((npix + PIX_PER_BLOCK - 1) / PIX_PER_BLOCK);
+    if (cf) {
+        if (cf->uniqueness < 0 || cf->uniqueness > 100) return hipErrorInvalidValue;
+        SVA_DISPATCH_D(D, wta_sum_conf_kernel, grid, S, npix, D, dmin, disp, sub, *cf);
+        return hipGetLastError();
+    }
     SVA_DISPATCH_D(D, wta_sum_kernel, grid, S, npix, D, dmin, disp, sub);
     return hipGetLastError();
 }

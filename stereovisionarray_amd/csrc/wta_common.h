@@ -94,6 +94,62 @@ __device__ __forceinline__ unsigned wta_pick_key_perm(const unsigned (&S)[DPL / 
     return row_min_u32<PIN>(best);
 }
 
+// ---- confidence ------------------------------------------
+// cost_second = min { S(d) : |d - d*| > 1 }: a second first-minimum reduction
+// over the same keys with the keys of d*-1 .. d*+1 forced to all-ones, so the
+// row minimum >> 16 is 0xFFFF when no disparity is left (and for padded
+// disparities, whose S is 0xFFFF already).  u = d* - 1 - (the lane's first
+// disparity), in unsigned arithmetic: the lane's local disparity e is one of
+// the three iff e - u <= 2 (u wraps for a d* - 1 before the lane).
+__device__ __forceinline__ unsigned conf_mask_key(unsigned key, unsigned e, unsigned u) {
+    return e - u <= 2u ? 0xffffffffu : key;
+}
+
+// wta_hv.hip's pair layout: the keys of wta_pick_key_perm.
+template <int DPL, bool PIN = false>
+__device__ __forceinline__ unsigned wta_second_key_perm(const unsigned (&S)[DPL / 2],
+                                                        const unsigned (&dpair)[DPL / 2],
+                                                        unsigned ds, unsigned lane_d) {
+    constexpr int NP = DPL / 2;
+    const unsigned u = ds - 1u - lane_d;
+    unsigned best = 0xffffffffu;
+#pragma unroll
+    for (int j = 0; j < NP; j++) {
+        const unsigned lo = __builtin_amdgcn_perm(S[j], dpair[j], 0x05040100u);
+        const unsigned hi = __builtin_amdgcn_perm(S[j], dpair[j], 0x07060302u);
+        const unsigned a = conf_mask_key(lo, (unsigned)j, u);
+        const unsigned b = conf_mask_key(hi, (unsigned)(j + NP), u);
+        best = best < a ? best : a;
+        best = best < b ? best : b;
+    }
+    return row_min_u32<PIN>(best) >> 16;
+}
+
+// wta.hip's adjacent pairs: the keys of wta_pick_raw.
+template <int DPL>
+__device__ __forceinline__ unsigned wta_second_raw(const unsigned (&S)[DPL / 2], int k, int ds) {
+    constexpr int NP = DPL / 2;
+    const unsigned d0 = (unsigned)(k * DPL);
+    const unsigned u = (unsigned)ds - 1u - d0;
+    unsigned best = 0xffffffffu;
+#pragma unroll
+    for (int j = 0; j < NP; j++) {
+        const unsigned lo = ((S[j] & 0xffffu) << 16) | (d0 + 2u * j);
+        const unsigned hi = (S[j] & 0xffff0000u) | (d0 + 2u * j + 1u);
+        const unsigned a = conf_mask_key(lo, 2u * j, u);
+        const unsigned b = conf_mask_key(hi, 2u * j + 1u, u);
+        best = best < a ? best : a;
+        best = best < b ? best : b;
+    }
+    return row_min_u32(best) >> 16;
+}
+
+// The uniqueness filter: reject iff a second cost exists and
+// cost_second * (100 - u) < cost_min * 100 (integers, every product < 2^20).
+__device__ __forceinline__ bool conf_reject(unsigned cmin, unsigned csec, int uniq) {
+    return csec != 0xffffu && csec * (unsigned)(100 - uniq) < cmin * 100u;
+}
+
 // Returns d* (0-based, the same in all 16 lanes of the row) and, when
 // want_sub, the f32 sub-pixel disparity dmin + d* (+ parabola offset) in *v.
 template <int DPL>
