@@ -168,7 +168,16 @@ int sva_kernel_time(void* ctx, const char* name, double* total_ms, int64_t* coun
  *                            takes the pair route; -1 restores the built-in
  *                            threshold (small frames are faster on four
  *                            volumes), 0 lets the parity tests run the pair
- *                            route at every size. */
+ *                            route at every size.
+ *   SVA_DEBUG_REFINE_ROUTE   set / get: 0 = sva_improve_with_disparity* picks
+ *                            its kernel by k (below), 1 = the box-sum route
+ *                            for every k >= 1, so the parity tests can run it
+ *                            where the two small-window kernels are witnesses.
+ *   SVA_DEBUG_REFINE_LAST_ROUTE  get: the kernel of the last refinement launch:
+ *                            0 = refine_box_kernel (k 1..16), 1 =
+ *                            refine_kernel (k 0; k 1..16 on planes of 2^31
+ *                            bytes or more), 2 = the box-sum route
+ *                            (k >= 17), -1 = none yet. */
 #define SVA_DEBUG_PLANE_SPLIT 1
 #define SVA_DEBUG_FAIL_COST_AT 2
 #define SVA_DEBUG_SIDE_IDLE 3
@@ -177,6 +186,8 @@ int sva_kernel_time(void* ctx, const char* name, double* total_ms, int64_t* coun
 #define SVA_DEBUG_PLACEMENT_WORST_NS 6
 #define SVA_DEBUG_DIAG_ROUTE 7
 #define SVA_DEBUG_DIAG_PAIR_MIN_PIXELS 8
+#define SVA_DEBUG_REFINE_ROUTE 9
+#define SVA_DEBUG_REFINE_LAST_ROUTE 10
 int sva_set_debug(void* ctx, int key, int64_t value);
 int sva_get_debug(void* ctx, int key, int64_t* value);
 
@@ -341,7 +352,16 @@ int sva_shift_perspective(void* ctx, const sva_camera* in_cam, const sva_camera*
 /* improveWithDisparity (functions.cpp:11-52): for each pair i (cam_pairs[2i],
  * cam_pairs[2i+1], paired image images[i]) shift the image by the disparity,
  * then re-search 11 candidates along the 0/1 direction with 2k x 2k SADs,
- * k = (window_size-1)/2 <= 32; the last pair wins.  mask nullable (= the
+ * k = (window_size-1)/2, any window_size >= 1; the last pair wins.  k >= 17
+ * runs on summed-area tables of the 11 absolute-difference planes, whose work
+ * per pixel does not depend on k.  They live in a context workspace that
+ * grows on demand and is freed by sva_destroy:
+ *   e = 4 for k <= 2052 (32-bit sums are exact), else 8;
+ *   table = e * (width + 1) * (height + 1) bytes per candidate;
+ *   G = min(11, max(1, floor(512 MiB / table))) tables at a time;
+ *   workspace = 256 + G * table (+ up to 7 of alignment)
+ *               + (G < 11 ? 9 * width * height : 0) bytes;
+ * none of it when no window fits the image.  mask nullable (= the
  * reference's getFaceMask, :13).  strict: fail with SVA_ERR_INVALID_ARG if a
  * masked pixel's window leaves the image (the reference's ROI throws);
  * otherwise such pixels are skipped.  _d: images is a HOST array of device

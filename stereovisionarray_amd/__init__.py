@@ -42,6 +42,8 @@ SVA_DEBUG_PLACEMENT_NS = 5
 SVA_DEBUG_PLACEMENT_WORST_NS = 6
 SVA_DEBUG_DIAG_ROUTE = 7
 SVA_DEBUG_DIAG_PAIR_MIN_PIXELS = 8
+SVA_DEBUG_REFINE_ROUTE = 9
+SVA_DEBUG_REFINE_LAST_ROUTE = 10
 # The ABI this binding is written against (include/sva.h SVA_ABI_VERSION).
 ABI_VERSION = 6
 
@@ -356,7 +358,8 @@ class Context:
 
     def set_debug(self, key: int, value: int):
         """sva_set_debug: SVA_DEBUG_PLANE_SPLIT / SVA_DEBUG_FAIL_COST_AT (tests),
-        SVA_DEBUG_PLACEMENT_TRIALS (sva_reserve's placement check)."""
+        SVA_DEBUG_PLACEMENT_TRIALS (sva_reserve's placement check),
+        SVA_DEBUG_REFINE_ROUTE (1 = the refinement's box-sum route at every k >= 1)."""
         self._chk(lib.sva_set_debug(self.h, key, int(value)))
 
     def get_debug(self, key: int) -> int:

@@ -490,8 +490,7 @@ int check_planes(Ctx* c, int W, int H, size_t pitch) {
 }
 
 int check_window(Ctx* c, int window_size) {
-    if (window_size < 1 || (window_size - 1) / 2 > 32)
-        return fail(c, SVA_ERR_UNSUPPORTED, "window_size must give kernelSize (w-1)/2 in 0..32");
+    if (window_size < 1) return fail(c, SVA_ERR_UNSUPPORTED, "window_size must be >= 1");
     return SVA_OK;
 }
 
@@ -607,7 +606,7 @@ int sva_destroy(void* ctx) {
     c->census_side.release();
     for (DevBuf* b : {&c->census_l, &c->census_r, &c->cost, &c->paths, &c->ckpt, &c->scratch_u16,
                       &c->disp_r, &c->in_a, &c->in_b, &c->in_mask, &c->out_a, &c->out_b,
-                      &c->out_c, &c->in_c, &c->shifted, &c->keys, &c->counts, &c->total, &c->ref_keys})
+                      &c->out_c, &c->in_c, &c->shifted, &c->keys, &c->counts, &c->total, &c->ref_keys, &c->refine_ws})
         b->release();
     c->timer.release_all();
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
@@ -816,6 +815,10 @@ int sva_set_debug(void* ctx, int key, int64_t value) {
             if (value < -1) return fail(c, SVA_ERR_INVALID_ARG, "pair route threshold must be >= -1");
             c->dbg_pair_min_pixels = value;
             return SVA_OK;
+        case SVA_DEBUG_REFINE_ROUTE:
+            if (value < 0 || value > 1) return fail(c, SVA_ERR_INVALID_ARG, "refine route must be 0 or 1");
+            c->dbg_refine_route = (int)value;
+            return SVA_OK;
         default:
             return fail(c, SVA_ERR_INVALID_ARG, "unknown or read-only debug key");
     }
@@ -835,6 +838,8 @@ int sva_get_debug(void* ctx, int key, int64_t* value) {
         case SVA_DEBUG_DIAG_PAIR_MIN_PIXELS:
             *value = c->dbg_pair_min_pixels >= 0 ? c->dbg_pair_min_pixels : (int64_t)tune::kDiagPairMinPixels;
             return SVA_OK;
+        case SVA_DEBUG_REFINE_ROUTE: *value = c->dbg_refine_route; return SVA_OK;
+        case SVA_DEBUG_REFINE_LAST_ROUTE: *value = c->last_refine_route; return SVA_OK;
         case SVA_DEBUG_SIDE_IDLE: {
             bool idle = true;
             for (hipStream_t s : c->side) {

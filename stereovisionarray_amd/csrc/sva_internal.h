@@ -64,6 +64,13 @@ struct Ctx {
     DevBuf in_a, in_b, in_mask, out_a, out_b, out_c;
     // refinement / 3-D workspace (refine.hip)
     DevBuf in_c, shifted, keys, counts, total;
+    // the box-sum refinement route's tables (refine.hip sat_plan; sva.h gives the size)
+    DevBuf refine_ws;
+    // SVA_DEBUG_REFINE_ROUTE (0 = automatic, 1 = box-sum route for every k >= 1)
+    // and SVA_DEBUG_REFINE_LAST_ROUTE (0 = refine_box_kernel, 1 =
+    // refine_kernel<ND>, 2 = box-sum route, -1 = no refine launch yet)
+    int dbg_refine_route = 0;
+    int last_refine_route = -1;
     // Mode R's split plane loop: one first-minimum key per pixel (refpath.hip).
     // ref_finalize_kernel puts every key it reads back to all-ones, so after
     // the first call only a grown buffer needs the memset: ref_keys_clean =

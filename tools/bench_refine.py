@@ -5,7 +5,9 @@ kernel times; one JSON line per routine:
   improveWithDisparity (4 CROSS pairs of camera 12, 20x20 windows, a centred
   face-sized mask, and without a mask), shiftPerspective2,
   DepthMapToPoints3D, Points3DToDepthMap, the ingestion resize, and the
-  evaluation error map / masked mean."""
+  evaluation error map / masked mean.
+--window-sweep: the refinement's kernel time over the window size instead
+(window_sweep below)."""
 import json
 import os
 import sys
@@ -18,7 +20,81 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "oracle"))
 
 
+def window_sweep():
+    """improveWithDisparity's `refine` kernel time per launch over the window
+    size at 1920x1080 (4 CROSS pairs of camera 12, planes resident in HBM,
+    SVA_TIMING_ALL), with the 600x600 face mask and without a mask:
+      windows 21, 35, 49, 65 on the automatic route and forced onto the
+        box-sum route (SVA_DEBUG_REFINE_ROUTE), the two alternating call by
+        call on one warm context, outputs compared byte for byte (from
+        window 35 the automatic route is the box-sum route: both arms agree);
+      windows 67, 129, 257, 513 on the automatic route.
+    One JSON line per (window, mask, route): median, min and max over the
+    calls of the mean time of the call's four launches."""
+    import torch
+    import stereovisionarray_amd as sva
+    from stereovisionarray_amd import synth
+
+    W, H, reps = 1920, 1080, 15
+    ctx = sva.Context(0)
+    s = torch.cuda.Stream()
+    torch.cuda.set_stream(s)
+    ctx.set_stream(s.cuda_stream)
+    dev = torch.device("cuda", 0)
+    cam = [sva.Camera.make(*c) for c in synth.reference_array(0.036 / W)]
+    pairs = [(cam[12], cam[b]) for b in (7, 17, 11, 13)]
+    rng = np.random.default_rng(0)
+    mask = np.zeros((H, W), np.uint8)
+    mask[240:840, 660:1260] = 1
+    d_disp = torch.from_numpy(rng.integers(100, 160, size=(H, W)).astype(np.uint8)).to(dev)
+    d_center = torch.from_numpy(synth.texture(H, W, 12)).to(dev)
+    d_mask = torch.from_numpy(mask).to(dev)
+    d_others = [torch.from_numpy(synth.texture(H, W, 40 + i)).to(dev) for i in range(4)]
+    outs = [torch.zeros((H, W), dtype=torch.uint8, device=dev) for _ in range(2)]
+    names = {0: "refine_box_kernel", 1: "refine_kernel", 2: "box_sum"}
+    ctx.set_timing(True)
+
+    def call(window, m, forced, out):
+        ctx.set_debug(sva.SVA_DEBUG_REFINE_ROUTE, int(forced))
+        ctx.reset_timing()
+        ctx.improve_with_disparity_d(d_disp.data_ptr(), d_center.data_ptr(),
+                                     [o.data_ptr() for o in d_others], pairs, W, H, W,
+                                     d_mask.data_ptr() if m else None, window, False,
+                                     out.data_ptr())
+        torch.cuda.synchronize()
+        ms, n = ctx.kernel_time("refine")
+        ctx.set_debug(sva.SVA_DEBUG_REFINE_ROUTE, 0)
+        return ms / n, ctx.get_debug(sva.SVA_DEBUG_REFINE_LAST_ROUTE)
+
+    for window in (21, 35, 49, 65, 67, 129, 257, 513):
+        for m in (True, False):
+            arms = (False, True) if window <= 65 else (False,)
+            t = {f: [] for f in arms}
+            route = {}
+            for o in outs:
+                o.zero_()
+            for f in arms:                       # warm both arms (workspace, code objects)
+                call(window, m, f, outs[int(f)])
+            for _ in range(reps):
+                for f in arms:
+                    ms, route[f] = call(window, m, f, outs[int(f)])
+                    t[f].append(ms)
+            same = bool(torch.equal(outs[0], outs[1])) if len(arms) == 2 else None
+            for f in arms:
+                v = sorted(t[f])
+                print(json.dumps({"routine": "refine_window_sweep", "size": f"{W}x{H}",
+                                  "window": window, "k": (window - 1) // 2,
+                                  "mask": "600x600" if m else "none", "forced": f,
+                                  "route": names[route[f]], "launches_per_call": 4, "calls": reps,
+                                  "refine_ms_median": round(v[len(v) // 2], 4),
+                                  "refine_ms_min": round(v[0], 4), "refine_ms_max": round(v[-1], 4),
+                                  "outputs_equal": same}), flush=True)
+    ctx.close()
+
+
 def main():
+    if "--window-sweep" in sys.argv[1:]:
+        return window_sweep()
     import torch
     import stereovisionarray_amd as sva
     from stereovisionarray_amd import synth
