@@ -146,10 +146,12 @@ int sva_kernel_time(void* ctx, const char* name, double* total_ms, int64_t* coun
  *                            shares (0 = the automatic count, refpath.hip
  *                            plane_shares), so the parity tests cover every
  *                            share count at every size.
- *   SVA_DEBUG_FAIL_COST_AT   set: the next sva_disparity_sgm_batch_d call fails
- *                            its n-th cost launch (1-based) with
- *                            SVA_ERR_DEVICE, without launching it; the switch
- *                            then resets to 0 (fault injection for the
+ *   SVA_DEBUG_FAIL_COST_AT   set: the next sva_disparity_sgm_batch_d or
+ *                            sva_disparity_sgm_batch_conf_d call fails its
+ *                            n-th cost launch (1-based) with SVA_ERR_DEVICE,
+ *                            without launching it.  That call resets the
+ *                            switch to 0 whatever its outcome, also when it
+ *                            refuses its arguments (fault injection for the
  *                            side-stream join test).
  *   SVA_DEBUG_SIDE_IDLE      get: 1 if every side stream of the batch route
  *                            has finished its queued work (hipStreamQuery),
@@ -238,6 +240,18 @@ int sva_disparity_sgm_conf_d(void* ctx, const uint8_t* left, const uint8_t* righ
 struct sva_pair_d;
 int sva_disparity_sgm_batch_d(void* ctx, const struct sva_pair_d* jobs, int n_jobs, int width,
                               int height, size_t pitch, uint16_t* maps, float* subpix);
+/* The same batch through wta_hv's confidence instance (DESIGN.md §2.4b,
+ * §4.10): frame j's maps / subpix / cost_min / cost_second planes equal
+ * sva_disparity_sgm_conf_d's for that pair byte for byte.  cost_min,
+ * cost_second: [n][H][W] u16 device, each may be NULL.  The rules of
+ * sva_disparity_sgm_batch_d hold (lr_check: SVA_ERR_UNSUPPORTED); the jobs
+ * must also share params.invalid, and uniqueness must lie in 0..100
+ * (SVA_ERR_INVALID_ARG).  With uniqueness = 0, maps / subpix equal
+ * sva_disparity_sgm_batch_d's. */
+int sva_disparity_sgm_batch_conf_d(void* ctx, const struct sva_pair_d* jobs, int n_jobs,
+                                   int width, int height, size_t pitch, int uniqueness,
+                                   uint16_t* maps, float* subpix, uint16_t* cost_min,
+                                   uint16_t* cost_second);
 
 /* Stage entry points (device buffers).  Layouts: census W*H u64; C, L
  * [y][x][d] u8; S [y][x][d] u16; L volumes [8][y][x][d] (direction table in
@@ -531,6 +545,17 @@ typedef struct sva_pair_d {
  * ordered before the next call writes maps / subpix. */
 int sva_batch_sgm_d(void* multi, const sva_pair_d* jobs, int n_jobs, int width, int height,
                     size_t pitch, uint16_t* maps, float* subpix);
+/* sva_batch_sgm_d with every pair through sva_disparity_sgm_conf_d on its
+ * context (so per-job invalid, lr_check and subpixel work as they do there) and
+ * the confidence planes gathered with the maps: cost_min, cost_second are
+ * [n_jobs][H][W] u16 on devices[0], each may be NULL.  Only the planes passed
+ * non-NULL are computed into the remote jobs' slots and shipped (2 bytes per
+ * pixel and pair each, next to the map's 2 and a sub-pixel job's 4).
+ * uniqueness outside 0..100: SVA_ERR_INVALID_ARG.  Ordering as above, for all
+ * four outputs. */
+int sva_batch_sgm_conf_d(void* multi, const sva_pair_d* jobs, int n_jobs, int width, int height,
+                         size_t pitch, int uniqueness, uint16_t* maps, float* subpix,
+                         uint16_t* cost_min, uint16_t* cost_second);
 
 /* A camera-array frame from HOST images: pair j matches images[pairs[j].ref]
  * against images[pairs[j].other] with its own params (the 2-D step of its
@@ -552,6 +577,26 @@ int sva_array_depth(void* multi, const uint8_t* const* images, int n_images, int
                     int height, size_t pitch, const sva_array_pair* pairs, int n_pairs,
                     const int32_t* group_start, int n_groups, double f, double pixel_size,
                     double* depth, uint8_t* n_valid, uint16_t* maps);
+/* sva_array_depth with confidence (SURVEY.md §8e "the per-pixel median or
+ * min-cost"): every pair is matched with the uniqueness filter (uniqueness in
+ * 0..100, 0 = off; sva_disparity_sgm_conf_d), and each group is fused by
+ * `mode`: SVA_FUSE_MIN_COST / SVA_FUSE_MAX_MARGIN through
+ * sva_fuse_depth_conf_d, SVA_FUSE_MEDIAN through sva_fuse_depth_d on the
+ * filtered maps.  The gather ships, next to the maps, only the planes the mode
+ * reads (MEDIAN none, MIN_COST cost_min, MAX_MARGIN both) and those the caller
+ * asks to receive.  winner (nullable): host [n_groups][H][W] u8, the chosen
+ * pair's index within its group, 0xFF if none; it must be NULL with
+ * SVA_FUSE_MEDIAN.  cost_min, cost_second (nullable): host [n_pairs][H][W] u16,
+ * like maps.  Another mode, uniqueness outside 0..100 or a winner with MEDIAN
+ * return SVA_ERR_INVALID_ARG; everything else is as for sva_array_depth, whose
+ * result MEDIAN with uniqueness = 0 equals bit for bit. */
+#define SVA_FUSE_MEDIAN 2   /* sva_array_depth_conf only; sva_fuse_depth_conf* keep refusing it */
+int sva_array_depth_conf(void* multi, const uint8_t* const* images, int n_images, int width,
+                         int height, size_t pitch, const sva_array_pair* pairs, int n_pairs,
+                         const int32_t* group_start, int n_groups, double f, double pixel_size,
+                         int uniqueness, int mode, double* depth, uint8_t* n_valid,
+                         uint8_t* winner, uint16_t* maps, uint16_t* cost_min,
+                         uint16_t* cost_second);
 
 #ifdef __cplusplus
 }

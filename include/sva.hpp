@@ -433,6 +433,74 @@ private:
     void* m_ = nullptr;
 };
 
+namespace detail {
+// The C-ABI form of one camera-array frame, shared by computeArrayDepth and
+// computeArrayDepthConf: the pairs grouped by reference camera (stable: the
+// order reference cameras first appear in `pairs`), each with its grid step.
+struct ArrayFrame {
+    int W = 0, H = 0;
+    size_t pitch = 0;
+    std::vector<int> refs;                // reference camera of each group
+    std::vector<sva_array_pair> ap;
+    std::vector<int32_t> group_start;
+    std::vector<size_t> order;            // ap index -> index in pairs
+    std::vector<const uint8_t*> ptrs;
+
+    // every pair's plane of `all` ([ap][H][W]) back in `pairs` order
+    template <typename T>
+    void scatter(const std::vector<T>& all, size_t n_pairs, std::vector<std::vector<T>>* out) const {
+        const size_t np = (size_t)W * H;
+        out->assign(n_pairs, {});
+        for (size_t i = 0; i < ap.size(); i++)
+            (*out)[order[i]].assign(all.begin() + i * np, all.begin() + (i + 1) * np);
+    }
+    template <typename T>
+    std::vector<std::vector<T>> split(const std::vector<T>& planes) const {
+        const size_t np = (size_t)W * H;
+        std::vector<std::vector<T>> out(refs.size());
+        for (size_t g = 0; g < refs.size(); g++)
+            out[g].assign(planes.begin() + g * np, planes.begin() + (g + 1) * np);
+        return out;
+    }
+};
+
+inline ArrayFrame arrayFrame(const std::vector<ImageView>& images, const std::vector<Camera>& cameras,
+                             const std::vector<std::array<int, 2>>& pairs, const sva_sgm_params& p,
+                             double pitch, const char* who) {
+    if (pairs.empty()) throw Error(SVA_ERR_INVALID_ARG, std::string(who) + ": no camera pairs");
+    const ImageView& first = images.at(pairs[0][0]);
+    ArrayFrame fr;
+    fr.W = first.width;
+    fr.H = first.height;
+    fr.pitch = first.pitch;
+    for (const auto& im : images)
+        if (im.width != fr.W || im.height != fr.H || im.pitch != first.pitch)
+            throw Error(SVA_ERR_INVALID_ARG, std::string(who) + ": images differ in size");
+    for (const auto& pr : pairs)
+        if (std::find(fr.refs.begin(), fr.refs.end(), pr[0]) == fr.refs.end())
+            fr.refs.push_back(pr[0]);
+    for (int r : fr.refs) {
+        fr.group_start.push_back((int32_t)fr.ap.size());
+        for (size_t j = 0; j < pairs.size(); j++) {
+            if (pairs[j][0] != r) continue;
+            const PairStep st = pairStep(cameras.at(pairs[j][0]), cameras.at(pairs[j][1]), pitch);
+            sva_array_pair a;
+            a.ref = pairs[j][0];
+            a.other = pairs[j][1];
+            a.params = p;
+            a.params.dir = st.dir;
+            a.params.dir_y = st.dir_y;
+            a.baseline = st.baseline;
+            fr.ap.push_back(a);
+            fr.order.push_back(j);
+        }
+    }
+    fr.group_start.push_back((int32_t)fr.ap.size());
+    for (const auto& im : images) fr.ptrs.push_back(im.data);
+    return fr;
+}
+}  // namespace detail
+
 // One camera-array frame over a MultiEngine: replaces the pair loop of
 // CameraStereoVision.cpp:55 for Mode S.  Every pair (getCameraPairs,
 // functions.cpp:148-213) is matched along its own grid step (pairStep) with
@@ -445,54 +513,48 @@ inline std::vector<std::vector<double>> computeArrayDepth(
     MultiEngine& m, const std::vector<ImageView>& images, const std::vector<Camera>& cameras,
     const std::vector<std::array<int, 2>>& pairs, const sva_sgm_params& p, double pitch = 0.05,
     std::vector<std::vector<uint16_t>>* maps = nullptr) {
-    if (pairs.empty()) throw Error(SVA_ERR_INVALID_ARG, "computeArrayDepth: no camera pairs");
-    const ImageView& first = images.at(pairs[0][0]);
-    const int W = first.width, H = first.height;
-    for (const auto& im : images)
-        if (im.width != W || im.height != H || im.pitch != first.pitch)
-            throw Error(SVA_ERR_INVALID_ARG, "computeArrayDepth: images differ in size");
-    // group the pairs by reference camera (stable: first appearance order)
-    std::vector<int> refs;
-    for (const auto& pr : pairs)
-        if (std::find(refs.begin(), refs.end(), pr[0]) == refs.end()) refs.push_back(pr[0]);
-    std::vector<sva_array_pair> ap;
-    std::vector<int32_t> group_start;
-    std::vector<size_t> order;   // ap index -> index in pairs
-    for (int r : refs) {
-        group_start.push_back((int32_t)ap.size());
-        for (size_t j = 0; j < pairs.size(); j++) {
-            if (pairs[j][0] != r) continue;
-            const PairStep st = pairStep(cameras.at(pairs[j][0]), cameras.at(pairs[j][1]), pitch);
-            sva_array_pair a;
-            a.ref = pairs[j][0];
-            a.other = pairs[j][1];
-            a.params = p;
-            a.params.dir = st.dir;
-            a.params.dir_y = st.dir_y;
-            a.baseline = st.baseline;
-            ap.push_back(a);
-            order.push_back(j);
-        }
-    }
-    group_start.push_back((int32_t)ap.size());
-    std::vector<const uint8_t*> ptrs;
-    for (const auto& im : images) ptrs.push_back(im.data);
-    const size_t np = (size_t)W * H;
-    const int ng = (int)refs.size();
+    const detail::ArrayFrame fr = detail::arrayFrame(images, cameras, pairs, p, pitch,
+                                                     "computeArrayDepth");
+    const size_t np = (size_t)fr.W * fr.H;
+    const int ng = (int)fr.refs.size();
     std::vector<double> depth(np * ng);
-    std::vector<uint16_t> all(maps ? np * ap.size() : 0);
-    const Camera& c0 = cameras.at(refs[0]);
-    m.check(sva_array_depth(m.handle(), ptrs.data(), (int)ptrs.size(), W, H, first.pitch, ap.data(),
-                            (int)ap.size(), group_start.data(), ng, c0.f, c0.pixel_size,
-                            depth.data(), nullptr, maps ? all.data() : nullptr));
-    if (maps) {
-        maps->assign(pairs.size(), {});
-        for (size_t i = 0; i < ap.size(); i++)
-            (*maps)[order[i]].assign(all.begin() + i * np, all.begin() + (i + 1) * np);
-    }
-    std::vector<std::vector<double>> out(ng);
-    for (int g = 0; g < ng; g++) out[g].assign(depth.begin() + g * np, depth.begin() + (g + 1) * np);
-    return out;
+    std::vector<uint16_t> all(maps ? np * fr.ap.size() : 0);
+    const Camera& c0 = cameras.at(fr.refs[0]);
+    m.check(sva_array_depth(m.handle(), fr.ptrs.data(), (int)fr.ptrs.size(), fr.W, fr.H, fr.pitch,
+                            fr.ap.data(), (int)fr.ap.size(), fr.group_start.data(), ng, c0.f,
+                            c0.pixel_size, depth.data(), nullptr, maps ? all.data() : nullptr));
+    if (maps) fr.scatter(all, pairs.size(), maps);
+    return fr.split(depth);
+}
+
+// computeArrayDepth with confidence (sva_array_depth_conf): the same grouping,
+// every pair matched with the uniqueness filter (0..100, 0 = off), and each
+// reference camera's maps fused by `mode`: SVA_FUSE_MIN_COST, SVA_FUSE_MAX_MARGIN
+//  or SVA_FUSE_MEDIAN on the filtered maps.  winner (nullable;
+// not with SVA_FUSE_MEDIAN) receives per group the chosen pair's index within
+// the group, 0xFF where no map is valid.
+inline std::vector<std::vector<double>> computeArrayDepthConf(
+    MultiEngine& m, const std::vector<ImageView>& images, const std::vector<Camera>& cameras,
+    const std::vector<std::array<int, 2>>& pairs, const sva_sgm_params& p, int uniqueness,
+    int mode = SVA_FUSE_MIN_COST, double pitch = 0.05,
+    std::vector<std::vector<uint16_t>>* maps = nullptr,
+    std::vector<std::vector<uint8_t>>* winner = nullptr) {
+    const detail::ArrayFrame fr = detail::arrayFrame(images, cameras, pairs, p, pitch,
+                                                     "computeArrayDepthConf");
+    const size_t np = (size_t)fr.W * fr.H;
+    const int ng = (int)fr.refs.size();
+    std::vector<double> depth(np * ng);
+    std::vector<uint16_t> all(maps ? np * fr.ap.size() : 0);
+    std::vector<uint8_t> win(winner ? np * ng : 0);
+    const Camera& c0 = cameras.at(fr.refs[0]);
+    m.check(sva_array_depth_conf(m.handle(), fr.ptrs.data(), (int)fr.ptrs.size(), fr.W, fr.H,
+                                 fr.pitch, fr.ap.data(), (int)fr.ap.size(), fr.group_start.data(),
+                                 ng, c0.f, c0.pixel_size, uniqueness, mode, depth.data(), nullptr,
+                                 winner ? win.data() : nullptr, maps ? all.data() : nullptr,
+                                 nullptr, nullptr));
+    if (maps) fr.scatter(all, pairs.size(), maps);
+    if (winner) *winner = fr.split(win);
+    return fr.split(depth);
 }
 
 // ---- refinement and 3-D output ----

@@ -66,10 +66,12 @@ EXPORTED = [
     "sva_multi_synchronize", "sva_multi_last_error", "sva_multi_plan", "sva_multi_context",
     "sva_batch_sgm_d", "sva_array_depth", "sva_disparity_sgm_batch_d", "sva_set_debug",
     "sva_get_debug", "sva_disparity_sgm_conf", "sva_disparity_sgm_conf_d", "sva_wta_conf_d",
-    "sva_fuse_depth_conf", "sva_fuse_depth_conf_d",
+    "sva_fuse_depth_conf", "sva_fuse_depth_conf_d", "sva_disparity_sgm_batch_conf_d",
+    "sva_batch_sgm_conf_d", "sva_array_depth_conf",
 ]
 SVA_FUSE_MIN_COST = 0
 SVA_FUSE_MAX_MARGIN = 1
+SVA_FUSE_MEDIAN = 2      # sva_array_depth_conf only
 SVA_MULTI_GATHER_RCCL = 0
 SVA_MULTI_GATHER_PEER = 1
 SVA_MULTI_GATHER_ALL = 2
@@ -229,6 +231,11 @@ def _load() -> ct.CDLL:
         "sva_disparity_sgm_batch_d": (i32, [vp, P(PairD), i32, i32, i32, sz, vp, vp]),
         "sva_array_depth": (i32, [vp, P(vp), i32, i32, i32, sz, P(ArrayPair), i32, P(i32), i32,
                                   dbl, dbl, vp, vp, vp]),
+        "sva_disparity_sgm_batch_conf_d": (i32, [vp, P(PairD), i32, i32, i32, sz, i32, vp, vp, vp,
+                                                 vp]),
+        "sva_batch_sgm_conf_d": (i32, [vp, P(PairD), i32, i32, i32, sz, i32, vp, vp, vp, vp]),
+        "sva_array_depth_conf": (i32, [vp, P(vp), i32, i32, i32, sz, P(ArrayPair), i32, P(i32),
+                                       i32, dbl, dbl, i32, i32, vp, vp, vp, vp, vp, vp]),
         "sva_resize_linear_f64_d": (i32, [vp, vp, i32, i32, vp, i32, i32]),
         "sva_resize_linear_f64": (i32, [vp, vp, i32, i32, vp, i32, i32]),
         "sva_ref_error_d": (i32, [vp, vp, i32, i32, vp, i32, i32, ct.c_double, vp]),
@@ -429,6 +436,18 @@ class Context:
             jobs[i] = PairD(_ptr(l), _ptr(r), p)
         self._chk(lib.sva_disparity_sgm_batch_d(self.h, jobs, len(pairs), W, H, pitch,
                                                 _ptr(maps), _ptr(sub)))
+
+    def disparity_sgm_batch_conf_d(self, pairs, W, H, pitch, uniqueness, maps, sub=None,
+                                   cost_min=None, cost_second=None):
+        """disparity_sgm_batch_d through the confidence instance: cost_min /
+        cost_second are [n][H][W] u16 device planes or None; the pairs also
+        share params.invalid."""
+        jobs = (PairD * len(pairs))()
+        for i, (l, r, p) in enumerate(pairs):
+            jobs[i] = PairD(_ptr(l), _ptr(r), p)
+        self._chk(lib.sva_disparity_sgm_batch_conf_d(self.h, jobs, len(pairs), W, H, pitch,
+                                                     int(uniqueness), _ptr(maps), _ptr(sub),
+                                                     _ptr(cost_min), _ptr(cost_second)))
 
     def census_d(self, img, W, H, pitch, out):
         self._chk(lib.sva_census_d(self.h, _ptr(img), W, H, pitch, _ptr(out)))
@@ -756,6 +775,44 @@ class Multi:
             jobs[i] = PairD(_ptr(l), _ptr(r), p)
         self._chk(lib.sva_batch_sgm_d(self.h, jobs, len(pairs), W, H, pitch, _ptr(maps),
                                       _ptr(sub)))
+
+    def batch_sgm_conf_d(self, pairs, W, H, pitch, uniqueness, maps, sub=None, cost_min=None,
+                         cost_second=None):
+        """batch_sgm_d with every pair through sva_disparity_sgm_conf_d; cost_min /
+        cost_second: [n][H][W] u16 on devices[0] or None (only those given are
+        gathered)."""
+        jobs = (PairD * len(pairs))()
+        for i, (l, r, p) in enumerate(pairs):
+            jobs[i] = PairD(_ptr(l), _ptr(r), p)
+        self._chk(lib.sva_batch_sgm_conf_d(self.h, jobs, len(pairs), W, H, pitch, int(uniqueness),
+                                           _ptr(maps), _ptr(sub), _ptr(cost_min),
+                                           _ptr(cost_second)))
+
+    def array_depth_conf(self, images, pairs, group_start, f, pixel_size, uniqueness=0,
+                         mode=SVA_FUSE_MIN_COST, want_maps=False, want_costs=False):
+        """array_depth with the uniqueness filter on every pair and the fusion
+        picked by mode (SVA_FUSE_MIN_COST, SVA_FUSE_MAX_MARGIN, SVA_FUSE_MEDIAN).
+        Returns (depth, n_valid, winner [G,H,W] u8 or None with MEDIAN, maps,
+        cost_min, cost_second), the last three [P,H,W] u16 or None."""
+        imgs = [np.ascontiguousarray(a, dtype=np.uint8) for a in images]
+        H, W = imgs[0].shape
+        ptrs = (ct.c_void_p * len(imgs))(*[_ptr(a) for a in imgs])
+        jp = (ArrayPair * len(pairs))()
+        for i, (a, b, p, base) in enumerate(pairs):
+            jp[i] = ArrayPair(a, b, p, base)
+        gs = (ct.c_int32 * len(group_start))(*group_start)
+        G = len(group_start) - 1
+        depth = np.zeros((G, H, W), np.float64)
+        nv = np.zeros((G, H, W), np.uint8)
+        win = np.zeros((G, H, W), np.uint8) if mode != SVA_FUSE_MEDIAN else None
+        maps = np.zeros((len(pairs), H, W), np.uint16) if want_maps else None
+        cmin = np.zeros((len(pairs), H, W), np.uint16) if want_costs else None
+        csec = np.zeros((len(pairs), H, W), np.uint16) if want_costs else None
+        self._chk(lib.sva_array_depth_conf(self.h, ptrs, len(imgs), W, H, W, jp, len(pairs), gs,
+                                           G, f, pixel_size, int(uniqueness), int(mode),
+                                           _ptr(depth), _ptr(nv), _ptr(win), _ptr(maps),
+                                           _ptr(cmin), _ptr(csec)))
+        return depth, nv, win, maps, cmin, csec
 
     def array_depth(self, images, pairs, group_start, f, pixel_size, want_maps=False):
         """images: list of HxW u8 numpy views; pairs: list of (ref, other,

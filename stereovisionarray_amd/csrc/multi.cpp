@@ -10,7 +10,9 @@
 // at sva_multi_create, so libsva.so itself has no RCCL link dependency), or
 // peer copies over xGMI (SVA_MULTI_GATHER_PEER).  Every compute step goes
 // through the public per-context entry points (sva_disparity_sgm_d,
-// sva_fuse_depth_d); there is no CPU path.
+// sva_fuse_depth_d, and sva_disparity_sgm_conf_d / sva_fuse_depth_conf_d for
+// the confidence forms, whose cost planes are gathered like the maps); there
+// is no CPU path.
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
@@ -107,6 +109,7 @@ struct Multi {
     std::vector<DevBuf> slots;         // per context: local maps of gathered jobs
     std::vector<DevBuf> images;        // per device: uploaded views (sva_array_depth)
     DevBuf maps0, depth0, nvalid0;     // device 0 (sva_array_depth)
+    DevBuf conf0, winner0;             // device 0: cost planes, winners (sva_array_depth_conf)
     PinnedBuf stage_in, stage_out;
     Rccl rccl;
     std::vector<ncclComm_t> comms;
@@ -231,21 +234,36 @@ int gather(Multi* m, const Plan& P, const std::vector<char>& remote,
     return SVA_OK;
 }
 
-// The shared part of sva_batch_sgm_d / sva_array_depth: run every pair on its
-// context, gather to devices[0].  left/right: per-job device pointers;
-// maps/sub on devices[0] ([n][H][W]); sub may be null.
+// The confidence form of run_pairs: every pair runs
+// sva_disparity_sgm_conf_d with this uniqueness, and the planes given here
+// (devices[0], [n][H][W] u16, each nullable) are gathered like the maps.  A
+// null plane is neither computed into a slot nor shipped.
+struct ConfPlanes {
+    int uniqueness = 0;
+    uint16_t* cost_min = nullptr;
+    uint16_t* cost_second = nullptr;
+};
+
+// The shared part of sva_batch_sgm_d / sva_array_depth and their confidence
+// forms: run every pair on its context, gather to devices[0].  left/right:
+// per-job device pointers; maps/sub on devices[0] ([n][H][W]); sub may be
+// null; cp null = the plain route (sva_disparity_sgm_d).
 int run_pairs(Multi* m, const Plan& P, const std::vector<const uint8_t*>& left,
               const std::vector<const uint8_t*>& right, const std::vector<sva_sgm_params>& prm,
               const std::vector<std::vector<hipEvent_t>>& wait_for, int W, int H, size_t pitch,
-              uint16_t* maps, float* sub) {
+              uint16_t* maps, float* sub, const ConfPlanes* cp = nullptr) {
     const int n = (int)P.dev.size();
     const size_t np = (size_t)W * H;
-    // 0. maps / sub are the caller's buffers on devices[0]: results of the
-    // previous call are complete on st(0, 0), and the caller may still be
-    // reading them there.  Every stream that writes into maps / sub -- device
-    // 0's other context streams (local jobs) and, with peer copies, each source
-    // device's st(d, 0) -- starts after what is queued on st(0, 0) now.  (The
-    // RCCL receives run on st(0, 0) itself.)
+    uint16_t* const cmin = cp ? cp->cost_min : nullptr;
+    uint16_t* const csec = cp ? cp->cost_second : nullptr;
+    // 0. maps / sub (and the two cost planes) are the caller's buffers on
+    // devices[0]: results of the previous call are complete on st(0, 0), and
+    // the caller may still be reading them there.  Every stream that writes
+    // into them -- device 0's other context streams (local jobs) and, with
+    // peer copies, each source device's st(d, 0) -- starts after what is queued
+    // on st(0, 0) now.  (The RCCL receives run on st(0, 0) itself.)  The cost
+    // planes are written by exactly the streams that write maps (the same
+    // job's kernel, the same gather), so these waits order them too.
     {
         hipEvent_t e0;
         MHIP(m, ev_on(m, 0, &e0), "event");
@@ -261,7 +279,10 @@ int run_pairs(Multi* m, const Plan& P, const std::vector<const uint8_t*>& left,
     // 1. slot workspace per context; a context starts after its device's last gather
     std::vector<char> remote(n, 0);
     for (int j = 0; j < n; j++) remote[j] = P.dev[j] != 0 || m->gather_all;
-    const size_t per = np * 2 + (sub ? np * 4 : 0);
+    // a slot: the map, then the sub-pixel map, cost_min and cost_second where asked for
+    const size_t off_sub = np * 2, off_min = off_sub + (sub ? np * 4 : 0);
+    const size_t off_sec = off_min + (cmin ? np * 2 : 0);
+    const size_t per = off_sec + (csec ? np * 2 : 0);
     for (int d = 0; d < m->nd(); d++) {
         MHIP(m, hipSetDevice(m->devices[d]), "hipSetDevice");
         for (int s = 0; s < m->spd; s++) {
@@ -273,26 +294,36 @@ int run_pairs(Multi* m, const Plan& P, const std::vector<const uint8_t*>& left,
         }
     }
     // 2. compute
-    std::vector<const uint8_t*> src_map(n, nullptr), src_sub(n, nullptr);
+    std::vector<const uint8_t*> src_map(n, nullptr), src_sub(n, nullptr), src_min(n, nullptr),
+        src_sec(n, nullptr);
     for (int j = 0; j < n; j++) {
         const int d = P.dev[j], s = P.cx[j];
         const size_t ci = (size_t)d * m->spd + s;
         uint16_t* od;
         float* os = nullptr;
+        uint16_t *omin = nullptr, *osec = nullptr;
         if (remote[j]) {
             uint8_t* base = (uint8_t*)m->slots[ci].ptr + (size_t)P.slot[j] * per;
             od = (uint16_t*)base;
-            if (sub) os = (float*)(base + np * 2);
+            if (sub) os = (float*)(base + off_sub);
+            if (cmin) omin = (uint16_t*)(base + off_min);
+            if (csec) osec = (uint16_t*)(base + off_sec);
             src_map[j] = base;
-            src_sub[j] = base + np * 2;
+            src_sub[j] = base + off_sub;
+            src_min[j] = base + off_min;
+            src_sec[j] = base + off_sec;
         } else {
             od = maps + (size_t)j * np;
             if (sub) os = sub + (size_t)j * np;
+            if (cmin) omin = cmin + (size_t)j * np;
+            if (csec) osec = csec + (size_t)j * np;
         }
         MHIP(m, hipSetDevice(m->devices[d]), "hipSetDevice");
         for (hipEvent_t e : wait_for[j]) MHIP(m, hipStreamWaitEvent(m->st(d, s), e, 0), "wait");
-        const int st = sva_disparity_sgm_d(m->ctx[ci], left[j], right[j], W, H, pitch, &prm[j], od,
-                                           os);
+        const int st = cp ? sva_disparity_sgm_conf_d(m->ctx[ci], left[j], right[j], W, H, pitch,
+                                                     &prm[j], cp->uniqueness, od, os, omin, osec)
+                          : sva_disparity_sgm_d(m->ctx[ci], left[j], right[j], W, H, pitch, &prm[j],
+                                                od, os);
         if (st != SVA_OK) return m->ctx_fail(st, m->ctx[ci], "pair");
     }
     // 3. join each device's streams into its stream 0
@@ -302,7 +333,7 @@ int run_pairs(Multi* m, const Plan& P, const std::vector<const uint8_t*>& left,
             int st = stream_after(m, d, m->st(d, s), m->st(d, 0));
             if (st) return st;
         }
-    // 4. gather (maps, then sub-pixel maps)
+    // 4. gather (maps, then sub-pixel maps, then the cost planes asked for)
     int st = gather(m, P, remote, src_map, (uint8_t*)maps, np * 2);
     if (st) return st;
     if (sub) {
@@ -312,6 +343,8 @@ int run_pairs(Multi* m, const Plan& P, const std::vector<const uint8_t*>& left,
         for (int j = 0; j < n; j++) remote_sub[j] = remote[j] && prm[j].subpixel != 0;
         if ((st = gather(m, P, remote_sub, src_sub, (uint8_t*)sub, np * 4))) return st;
     }
+    if (cmin && (st = gather(m, P, remote, src_min, (uint8_t*)cmin, np * 2))) return st;
+    if (csec && (st = gather(m, P, remote, src_sec, (uint8_t*)csec, np * 2))) return st;
     for (int d = 0; d < m->nd(); d++) {
         MHIP(m, hipSetDevice(m->devices[d]), "hipSetDevice");
         MHIP(m, hipEventRecord(m->gathered[d], m->st(d, 0)), "event record");
@@ -580,6 +613,8 @@ int sva_multi_destroy(void* mp) {
         m->maps0.release();
         m->depth0.release();
         m->nvalid0.release();
+        m->conf0.release();
+        m->winner0.release();
     }
     m->stage_in.release();
     m->stage_out.release();
@@ -623,10 +658,16 @@ int sva_multi_context(void* mp, int d, int s, void** out) {
     return SVA_OK;
 }
 
-int sva_batch_sgm_d(void* mp, const sva_pair_d* jobs, int n_jobs, int W, int H, size_t pitch,
-                    uint16_t* maps, float* sub) {
+}  // extern "C"
+
+namespace {
+// sva_batch_sgm_d (cp null) and sva_batch_sgm_conf_d
+int batch_sgm_d(void* mp, const sva_pair_d* jobs, int n_jobs, int W, int H, size_t pitch,
+                uint16_t* maps, float* sub, const ConfPlanes* cp) {
     Multi* m = as_multi(mp);
     if (!m) return SVA_ERR_INVALID_ARG;
+    if (cp && (cp->uniqueness < 0 || cp->uniqueness > 100))
+        return m->fail(SVA_ERR_INVALID_ARG, "uniqueness must be 0..100");
     if (n_jobs < 0 || (n_jobs > 0 && (!jobs || !maps)) || W <= 0 || H <= 0 || pitch < (size_t)W)
         return m->fail(SVA_ERR_INVALID_ARG, "bad batch arguments");
     if (n_jobs == 0) return SVA_OK;
@@ -647,15 +688,27 @@ int sva_batch_sgm_d(void* mp, const sva_pair_d* jobs, int n_jobs, int W, int H, 
         r[j] = jobs[j].right;
         prm[j] = jobs[j].params;
     }
-    return run_pairs(m, P, l, r, prm, none, W, H, pitch, maps, any_sub ? sub : nullptr);
+    return run_pairs(m, P, l, r, prm, none, W, H, pitch, maps, any_sub ? sub : nullptr, cp);
 }
 
-int sva_array_depth(void* mp, const uint8_t* const* images, int n_images, int W, int H,
-                    size_t pitch, const sva_array_pair* pairs, int n_pairs,
-                    const int32_t* group_start, int n_groups, double f, double pixel_size,
-                    double* depth, uint8_t* n_valid, uint16_t* maps) {
+// sva_array_depth (conf false: plain matching, median fusion) and
+// sva_array_depth_conf (every pair through the uniqueness filter; `mode` picks
+// the fusion; winner, cost_min, cost_second: nullable host outputs).
+int array_depth(void* mp, const uint8_t* const* images, int n_images, int W, int H, size_t pitch,
+                const sva_array_pair* pairs, int n_pairs, const int32_t* group_start,
+                int n_groups, double f, double pixel_size, bool conf, int uniqueness, int mode,
+                double* depth, uint8_t* n_valid, uint8_t* winner, uint16_t* maps,
+                uint16_t* cost_min, uint16_t* cost_second) {
     Multi* m = as_multi(mp);
     if (!m) return SVA_ERR_INVALID_ARG;
+    if (conf) {
+        if (mode != SVA_FUSE_MIN_COST && mode != SVA_FUSE_MAX_MARGIN && mode != SVA_FUSE_MEDIAN)
+            return m->fail(SVA_ERR_INVALID_ARG, "unknown fusion mode");
+        if (uniqueness < 0 || uniqueness > 100)
+            return m->fail(SVA_ERR_INVALID_ARG, "uniqueness must be 0..100");
+        if (winner && mode == SVA_FUSE_MEDIAN)
+            return m->fail(SVA_ERR_INVALID_ARG, "the median has no winner map");
+    }
     if (!images || n_images <= 0 || !pairs || n_pairs <= 0 || !group_start || n_groups <= 0 ||
         !depth || W <= 0 || H <= 0 || pitch < (size_t)W)
         return m->fail(SVA_ERR_INVALID_ARG, "bad array arguments");
@@ -739,6 +792,16 @@ int sva_array_depth(void* mp, const uint8_t* const* images, int n_images, int W,
     MHIP(m, m->maps0.ensure(np * 2 * n_pairs), "map workspace");
     MHIP(m, m->depth0.ensure(np * 8 * n_groups), "depth workspace");
     MHIP(m, m->nvalid0.ensure(np * n_groups), "depth workspace");
+    // the cost planes the fusion mode reads, and those the caller asked for
+    const bool want_min = conf && (mode != SVA_FUSE_MEDIAN || cost_min);
+    const bool want_sec = conf && (mode == SVA_FUSE_MAX_MARGIN || cost_second);
+    const size_t plane = np * 2 * n_pairs;
+    if (want_min || want_sec)
+        MHIP(m, m->conf0.ensure(plane * ((want_min ? 1 : 0) + (want_sec ? 1 : 0))), "cost planes");
+    if (winner) MHIP(m, m->winner0.ensure(np * n_groups), "winner workspace");
+    uint16_t* cmin0 = want_min ? (uint16_t*)m->conf0.ptr : nullptr;
+    uint16_t* csec0 = want_sec ? (uint16_t*)m->conf0.ptr + (want_min ? np * n_pairs : 0) : nullptr;
+    uint8_t* win0 = winner ? (uint8_t*)m->winner0.ptr : nullptr;
     std::vector<const uint8_t*> l(n_pairs), r(n_pairs);
     std::vector<sva_sgm_params> prm(n_pairs);
     std::vector<std::vector<hipEvent_t>> waits(n_pairs);
@@ -752,13 +815,19 @@ int sva_array_depth(void* mp, const uint8_t* const* images, int n_images, int W,
         waits[j] = {up_ev[d][pairs[j].ref], up_ev[d][pairs[j].other]};
     }
     uint16_t* maps0 = (uint16_t*)m->maps0.ptr;
-    int st = run_pairs(m, P, l, r, prm, waits, W, H, W, maps0, nullptr);
+    ConfPlanes cp;
+    cp.uniqueness = uniqueness;
+    cp.cost_min = cmin0;
+    cp.cost_second = csec0;
+    int st = run_pairs(m, P, l, r, prm, waits, W, H, W, maps0, nullptr, conf ? &cp : nullptr);
     if (st) return st;
     // 4. fusion per group on device 0, each group's download as soon as it is fused
     MHIP(m, hipSetDevice(m->devices[0]), "hipSetDevice");
-    MHIP(m, m->stage_out.ensure(np * (8 + (n_valid ? 1 : 0)) * n_groups +
-                                (maps ? np * 2 * n_pairs : 0)),
-         "pinned staging");
+    // pinned staging: depth, n_valid, winner per group, then the per-pair planes
+    const size_t o_nv = np * 8 * n_groups, o_win = o_nv + (n_valid ? np * n_groups : 0);
+    const size_t o_maps = o_win + (winner ? np * n_groups : 0);
+    const size_t o_min = o_maps + (maps ? plane : 0), o_sec = o_min + (cost_min ? plane : 0);
+    MHIP(m, m->stage_out.ensure(o_sec + (cost_second ? plane : 0)), "pinned staging");
     uint8_t* pout = (uint8_t*)m->stage_out.ptr;
     double* depth0 = (double*)m->depth0.ptr;
     uint8_t* nv0 = (uint8_t*)m->nvalid0.ptr;
@@ -766,28 +835,85 @@ int sva_array_depth(void* mp, const uint8_t* const* images, int n_images, int W,
     for (int j = 0; j < n_pairs; j++) bases[j] = pairs[j].baseline;
     for (int g = 0; g < n_groups; g++) {
         const int j0 = group_start[g], n = group_start[g + 1] - j0;
-        st = sva_fuse_depth_d(m->ctx[0], maps0 + (size_t)j0 * np, n, W, H, &bases[j0], f,
-                              pixel_size, pairs[j0].params.invalid, depth0 + (size_t)g * np,
-                              nv0 + (size_t)g * np);
+        if (conf && mode != SVA_FUSE_MEDIAN)
+            st = sva_fuse_depth_conf_d(m->ctx[0], maps0 + (size_t)j0 * np, cmin0 + (size_t)j0 * np,
+                                       csec0 ? csec0 + (size_t)j0 * np : nullptr, n, W, H,
+                                       &bases[j0], f, pixel_size, pairs[j0].params.invalid, mode,
+                                       depth0 + (size_t)g * np, nv0 + (size_t)g * np,
+                                       win0 ? win0 + (size_t)g * np : nullptr);
+        else
+            st = sva_fuse_depth_d(m->ctx[0], maps0 + (size_t)j0 * np, n, W, H, &bases[j0], f,
+                                  pixel_size, pairs[j0].params.invalid, depth0 + (size_t)g * np,
+                                  nv0 + (size_t)g * np);
         if (st) return m->ctx_fail(st, m->ctx[0], "fuse");
         if ((st = stream_after(m, 0, m->st(0, 0), m->down[0]))) return st;
         MHIP(m, hipMemcpyAsync(pout + (size_t)g * np * 8, depth0 + (size_t)g * np, np * 8,
                                hipMemcpyDeviceToHost, m->down[0]),
              "download");
         if (n_valid)
-            MHIP(m, hipMemcpyAsync(pout + (size_t)n_groups * np * 8 + (size_t)g * np,
-                                   nv0 + (size_t)g * np, np, hipMemcpyDeviceToHost, m->down[0]),
+            MHIP(m, hipMemcpyAsync(pout + o_nv + (size_t)g * np, nv0 + (size_t)g * np, np,
+                                   hipMemcpyDeviceToHost, m->down[0]),
+                 "download");
+        if (winner)
+            MHIP(m, hipMemcpyAsync(pout + o_win + (size_t)g * np, win0 + (size_t)g * np, np,
+                                   hipMemcpyDeviceToHost, m->down[0]),
                  "download");
     }
     if (maps)
-        MHIP(m, hipMemcpyAsync(pout + np * (8 + (n_valid ? 1 : 0)) * n_groups, maps0,
-                               np * 2 * n_pairs, hipMemcpyDeviceToHost, m->down[0]),
+        MHIP(m, hipMemcpyAsync(pout + o_maps, maps0, plane, hipMemcpyDeviceToHost, m->down[0]),
+             "download");
+    if (cost_min)
+        MHIP(m, hipMemcpyAsync(pout + o_min, cmin0, plane, hipMemcpyDeviceToHost, m->down[0]),
+             "download");
+    if (cost_second)
+        MHIP(m, hipMemcpyAsync(pout + o_sec, csec0, plane, hipMemcpyDeviceToHost, m->down[0]),
              "download");
     MHIP(m, hipStreamSynchronize(m->down[0]), "synchronize");
     std::memcpy(depth, pout, np * 8 * n_groups);
-    if (n_valid) std::memcpy(n_valid, pout + (size_t)n_groups * np * 8, np * n_groups);
-    if (maps) std::memcpy(maps, pout + np * (8 + (n_valid ? 1 : 0)) * n_groups, np * 2 * n_pairs);
+    if (n_valid) std::memcpy(n_valid, pout + o_nv, np * n_groups);
+    if (winner) std::memcpy(winner, pout + o_win, np * n_groups);
+    if (maps) std::memcpy(maps, pout + o_maps, plane);
+    if (cost_min) std::memcpy(cost_min, pout + o_min, plane);
+    if (cost_second) std::memcpy(cost_second, pout + o_sec, plane);
     return SVA_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int sva_batch_sgm_d(void* mp, const sva_pair_d* jobs, int n_jobs, int W, int H, size_t pitch,
+                    uint16_t* maps, float* sub) {
+    return batch_sgm_d(mp, jobs, n_jobs, W, H, pitch, maps, sub, nullptr);
+}
+
+int sva_batch_sgm_conf_d(void* mp, const sva_pair_d* jobs, int n_jobs, int W, int H, size_t pitch,
+                         int uniqueness, uint16_t* maps, float* sub, uint16_t* cost_min,
+                         uint16_t* cost_second) {
+    ConfPlanes cp;
+    cp.uniqueness = uniqueness;
+    cp.cost_min = cost_min;
+    cp.cost_second = cost_second;
+    return batch_sgm_d(mp, jobs, n_jobs, W, H, pitch, maps, sub, &cp);
+}
+
+int sva_array_depth(void* mp, const uint8_t* const* images, int n_images, int W, int H,
+                    size_t pitch, const sva_array_pair* pairs, int n_pairs,
+                    const int32_t* group_start, int n_groups, double f, double pixel_size,
+                    double* depth, uint8_t* n_valid, uint16_t* maps) {
+    return array_depth(mp, images, n_images, W, H, pitch, pairs, n_pairs, group_start, n_groups, f,
+                       pixel_size, false, 0, SVA_FUSE_MEDIAN, depth, n_valid, nullptr, maps,
+                       nullptr, nullptr);
+}
+
+int sva_array_depth_conf(void* mp, const uint8_t* const* images, int n_images, int W, int H,
+                         size_t pitch, const sva_array_pair* pairs, int n_pairs,
+                         const int32_t* group_start, int n_groups, double f, double pixel_size,
+                         int uniqueness, int mode, double* depth, uint8_t* n_valid,
+                         uint8_t* winner, uint16_t* maps, uint16_t* cost_min,
+                         uint16_t* cost_second) {
+    return array_depth(mp, images, n_images, W, H, pitch, pairs, n_pairs, group_start, n_groups, f,
+                       pixel_size, true, uniqueness, mode, depth, n_valid, winner, maps, cost_min,
+                       cost_second);
 }
 
 }  // extern "C"

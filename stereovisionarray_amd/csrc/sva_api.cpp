@@ -338,8 +338,12 @@ int run_sgm_device(Ctx* c, const uint8_t* left, const uint8_t* right, int W, int
 // next sub-batches' (VALU-bound, small) cost kernels overlap the current
 // (HBM-bound) aggregation.  jobs[0..n) share D, dmin, P1, P2 and subpixel
 // (checked by the entry point); maps / sub hold n planes of W*H.
+// cf set (sva_disparity_sgm_batch_conf_d): wta_hv's confidence instance, its
+// planes n frames like maps; each sub-batch's launch gets them offset here and
+// the kernel offsets them per frame.  fail_at: SVA_DEBUG_FAIL_COST_AT as the
+// entry point read it.
 int run_sgm_batch(Ctx* c, const sva_pair_d* jobs, int n, int W, int H, size_t pitch,
-                  uint16_t* maps, float* sub) {
+                  uint16_t* maps, float* sub, const ConfOut* cf, int fail_at) {
     const sva_sgm_params* p = &jobs[0].params;
     const int Dp = padded_D(p->D);
     const size_t np = (size_t)W * H, nv = np * (size_t)Dp;
@@ -372,9 +376,7 @@ int run_sgm_batch(Ctx* c, const sva_pair_d* jobs, int n, int W, int H, size_t pi
     }
     SVA_HIP(c, c->census_side.ensure(np * 16 * (size_t)std::max(ns, 1)), "census workspace");
     const hipStream_t own = c->stream;
-    // fault injection (SVA_DEBUG_FAIL_COST_AT): this call's n-th cost launch fails
-    const int fail_at = c->dbg_fail_cost_at;
-    c->dbg_fail_cost_at = 0;
+    // fault injection (SVA_DEBUG_FAIL_COST_AT): this call's fail_at-th cost launch fails
     int st = SVA_OK;
     for (int i = 0; i < n && st == SVA_OK; i++) {
         const sva_sgm_params* q = &jobs[i].params;
@@ -425,9 +427,16 @@ int run_sgm_batch(Ctx* c, const sva_pair_d* jobs, int n, int W, int H, size_t pi
             st = hip_fail(c, e, "paths launch");
             break;
         }
+        ConfOut cfj;
+        if (cf) {
+            cfj = *cf;
+            if (cfj.cost_min) cfj.cost_min += (size_t)i0 * np;
+            if (cfj.cost_second) cfj.cost_second += (size_t)i0 * np;
+        }
         if ((e = launch_wta_hv(*c, Cj, L4, CK, CKV, W, H, Dp, p->P1, p->P2, p->dmin,
-                               maps + (size_t)i0 * np, p->subpixel ? sub + (size_t)i0 * np : nullptr,
-                               p->D, m)) != hipSuccess) {
+                               maps + (size_t)i0 * np,
+                               p->subpixel && sub ? sub + (size_t)i0 * np : nullptr, p->D, m, false,
+                               nullptr, cf ? &cfj : nullptr)) != hipSuccess) {
             st = hip_fail(c, e, "wta launch");
             break;
         }
@@ -880,11 +889,20 @@ int sva_disparity_sgm_d(void* ctx, const uint8_t* left, const uint8_t* right, in
     return run_sgm_device(c, left, right, W, H, pitch, p, disp, p->subpixel ? sub : nullptr);
 }
 
-int sva_disparity_sgm_batch_d(void* ctx, const sva_pair_d* jobs, int n, int W, int H,
-                              size_t pitch, uint16_t* maps, float* sub) {
+// The batch entry points: sva_disparity_sgm_batch_d (cf null) and its
+// confidence form.
+namespace {
+int sgm_batch_d(void* ctx, const sva_pair_d* jobs, int n, int W, int H, size_t pitch,
+                uint16_t* maps, float* sub, const ConfOut* cf) {
     Ctx* c = as_ctx(ctx);
     SVA_CHECK_CTX(c);
+    // SVA_DEBUG_FAIL_COST_AT is for "the next call": read and cleared before
+    // validation, so that a call refused below does not leave it armed
+    const int fail_at = c->dbg_fail_cost_at;
+    c->dbg_fail_cost_at = 0;
     if (!jobs || n <= 0 || !maps) return fail(c, SVA_ERR_INVALID_ARG, "bad batch argument");
+    if (cf && (cf->uniqueness < 0 || cf->uniqueness > 100))
+        return fail(c, SVA_ERR_INVALID_ARG, "uniqueness must be 0..100 (percent, 0 = off)");
     int s;
     const sva_sgm_params* p0 = &jobs[0].params;
     for (int i = 0; i < n; i++) {
@@ -896,6 +914,9 @@ int sva_disparity_sgm_batch_d(void* ctx, const sva_pair_d* jobs, int n, int W, i
             q->subpixel != p0->subpixel)
             return fail(c, SVA_ERR_INVALID_ARG,
                         "a batch's pairs must share D, dmin, P1, P2 and subpixel");
+        // the filter writes one `invalid` per launch
+        if (cf && q->invalid != p0->invalid)
+            return fail(c, SVA_ERR_INVALID_ARG, "a confidence batch's pairs must share invalid");
         if (q->lr_check) return fail(c, SVA_ERR_UNSUPPORTED, "the batch route has no L/R check");
     }
     if (!wta_hv_supported(padded_D(p0->D)))
@@ -910,11 +931,25 @@ int sva_disparity_sgm_batch_d(void* ctx, const sva_pair_d* jobs, int n, int W, i
     const size_t np = (size_t)W * H;
     for (int i0 = 0; i0 < n; i0 += chunk) {
         const int m = std::min(chunk, n - i0);
+        ConfOut cfi;
+        if (cf) {
+            cfi = *cf;
+            if (cfi.cost_min) cfi.cost_min += (size_t)i0 * np;
+            if (cfi.cost_second) cfi.cost_second += (size_t)i0 * np;
+        }
+        // (the injected failure counts the first chunk's launches, as before)
         if ((s = run_sgm_batch(c, jobs + i0, m, W, H, pitch, maps + (size_t)i0 * np,
-                               sub ? sub + (size_t)i0 * np : nullptr)))
+                               sub ? sub + (size_t)i0 * np : nullptr, cf ? &cfi : nullptr,
+                               i0 == 0 ? fail_at : 0)))
             return s;
     }
     return SVA_OK;
+}
+}  // namespace
+
+int sva_disparity_sgm_batch_d(void* ctx, const sva_pair_d* jobs, int n, int W, int H,
+                              size_t pitch, uint16_t* maps, float* sub) {
+    return sgm_batch_d(ctx, jobs, n, W, H, pitch, maps, sub, nullptr);
 }
 
 int sva_disparity_sgm(void* ctx, const uint8_t* left, const uint8_t* right, int W, int H,
@@ -974,6 +1009,19 @@ int sva_disparity_sgm_conf_d(void* ctx, const uint8_t* left, const uint8_t* righ
     cf.uniqueness = uniqueness;
     cf.invalid = p->invalid;
     return run_sgm_device(c, left, right, W, H, pitch, p, disp, p->subpixel ? sub : nullptr, &cf);
+}
+
+// The batch route with the confidence instance: frame j's
+// four outputs equal sva_disparity_sgm_conf_d's for that pair.
+int sva_disparity_sgm_batch_conf_d(void* ctx, const sva_pair_d* jobs, int n, int W, int H,
+                                   size_t pitch, int uniqueness, uint16_t* maps, float* sub,
+                                   uint16_t* cost_min, uint16_t* cost_second) {
+    ConfOut cf;
+    cf.cost_min = cost_min;
+    cf.cost_second = cost_second;
+    cf.uniqueness = uniqueness;
+    cf.invalid = jobs && n > 0 ? jobs[0].params.invalid : 0xffffu;
+    return sgm_batch_d(ctx, jobs, n, W, H, pitch, maps, sub, &cf);
 }
 
 int sva_disparity_sgm_conf(void* ctx, const uint8_t* left, const uint8_t* right, int W, int H,

@@ -227,8 +227,10 @@ inline int padded_D(int D) {
 // §4.7), WTA over d < dreal only.
 bool wta_hv_supported(int D);
 // The WTA's confidence outputs, a kernel argument of the
-// confidence instances: W*H u16 planes (each nullable), the uniqueness
-// percentage 0..100 (0 = no filter) and the disparity a rejected pixel gets.
+// confidence instances: W*H u16 planes (each nullable; a batch launch: npair
+// such planes back to back, like disp), the uniqueness percentage 0..100
+// (0 = no filter) and the disparity a rejected pixel gets, both one value per
+// launch.
 struct ConfOut {
     uint16_t* cost_min = nullptr;
     uint16_t* cost_second = nullptr;
@@ -238,7 +240,8 @@ struct ConfOut {
 // pair: L4 holds the pair route's two pair-sum volumes (one frame).
 // MN: the minima planes of launch_paths(.., MN) for the same frame; the
 // recurrences read each step's m there (one frame, path_minima_enabled).
-// cf set (one frame): the confidence instance of the same kernel.
+// cf set: the confidence instance of the same kernel (one frame or a batch,
+// DESIGN.md §4.10).
 hipError_t launch_wta_hv(Ctx& c, const uint8_t* C, const uint8_t* L4, const uint8_t* CK,
                          const uint8_t* CKV, int W, int H, int D, int P1, int P2, int dmin,
                          uint16_t* disp, float* sub, int dreal = 0, int npair = 1,

@@ -135,7 +135,8 @@ hipError_t launch_wta_hv(Ctx& c, const uint8_t* C, const uint8_t* L4, const uint
     g.vck = (unsigned)(tg.vck_bytes / 2);
     const bool pad = g.dreal < D;
     if (npair < 1) return hipErrorInvalidValue;
-    if (cf && (npair != 1 || cf->uniqueness < 0 || cf->uniqueness > 100)) return hipErrorInvalidValue;
+    // (a batch, npair > 1: cf's planes hold npair frames, like disp and sub)
+    if (cf && (cf->uniqueness < 0 || cf->uniqueness > 100)) return hipErrorInvalidValue;
     g.tiles = g.ntx * g.nty;
     const dim3 grid((unsigned)(g.tiles * npair));
 #define SVA_WTAHV(DPL_, TYL_, MN_)                                                            \

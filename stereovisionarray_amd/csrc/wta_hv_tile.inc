@@ -42,6 +42,12 @@ __global__ __launch_bounds__(TB, tune::kWtahvMinWaves) void wta_hv_kernel(const 
     CKV += (size_t)f * 2 * g.vck;
     disp += (size_t)f * (size_t)g.W * (size_t)g.H;
     if (sub) sub += (size_t)f * (size_t)g.W * (size_t)g.H;
+#if SVA_WTAHV_CONF
+    // the cost planes are [frames][H][W] like disp (uniqueness and invalid:
+    // one value per launch)
+    if (cf.cost_min) cf.cost_min += (size_t)f * (size_t)g.W * (size_t)g.H;
+    if (cf.cost_second) cf.cost_second += (size_t)f * (size_t)g.W * (size_t)g.H;
+#endif
     const int slot = (int)(threadIdx.x >> 4);
     const int k = (int)(threadIdx.x & 15);
     const int W = g.W, H = g.H;
@@ -287,8 +293,8 @@ __global__ __launch_bounds__(TB, tune::kWtahvMinWaves) void wta_hv_kernel(const 
     if (k < nh) {
         const size_t at = (size_t)yh * (size_t)W + (size_t)(hx + k);
 #if SVA_WTAHV_CONF
-        // one frame per launch (launch_wta_hv): the planes need no frame offset.
-        // They keep their values where the filter rejects the pixel.
+        // (the planes were advanced to this block's frame above.)  They keep
+        // their values where the filter rejects the pixel.
         if (cf.cost_min) cf.cost_min[at] = (uint16_t)s0;
         if (cf.cost_second) cf.cost_second[at] = (uint16_t)s2;
         const bool rej = conf_reject(s0, s2, cf.uniqueness);
