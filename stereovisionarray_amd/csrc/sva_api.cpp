@@ -251,6 +251,40 @@ int check_tile_buffers(Ctx* c, int W, int H, int D, const void* C, size_t C_byte
     return SVA_OK;
 }
 
+// Which kernels form a frame's cost volume (native width Dp, step (dir, dir_y)):
+// census + cost in one kernel for 1-D steps (census_cost.hip) and
+// for 2-D steps whose primitive form has |dir_y| = 1 and |dir| <= 3 (every rig
+// baseline of getCameraPairs and of BASELINE config 4; census_cost2.hip,
+// §4.2b), else census_pair followed by cost2.
+enum class CostRoute { Fused1D, Fused2D, Split };
+CostRoute cost_route(int Dp, int dir, int dir_y) {
+    if (dir_y == 0 && Dp >= tune::kCensusCostMinD && census_cost_supported(Dp))
+        return CostRoute::Fused1D;
+    return census_cost2_supported(Dp, dir, dir_y) ? CostRoute::Fused2D : CostRoute::Split;
+}
+
+// One matching role's cost volume C on c.stream: `ref` matched against `oth`
+// along (sx, sy).  The split route reads the census maps cen_ref / cen_oth;
+// fill = launch census_pair into them first (*what then names a failing
+// launch).  The fused routes keep the maps on chip and take neither.
+hipError_t form_cost(Ctx& c, CostRoute route, const uint8_t* ref, const uint8_t* oth, int W, int H,
+                     size_t pitch, int Dp, const sva_sgm_params* p, int sx, int sy, uint8_t* C,
+                     uint64_t* cen_ref, uint64_t* cen_oth, bool fill,
+                     const char** what = nullptr) {
+    if (route == CostRoute::Fused1D)
+        return launch_census_cost(c, ref, oth, W, H, pitch, Dp, p->dmin, sx, C, p->D);
+    if (route == CostRoute::Fused2D)
+        return launch_census_cost2(c, ref, oth, W, H, pitch, Dp, p->dmin, sx, sy, C, p->D);
+    if (fill) {
+        const hipError_t e = launch_census_pair(c, ref, oth, W, H, pitch, cen_ref, cen_oth);
+        if (e != hipSuccess) {
+            if (what) *what = "census launch";
+            return e;
+        }
+    }
+    return launch_cost2(c, cen_ref, cen_oth, W, H, Dp, p->dmin, sx, sy, C, p->D);
+}
+
 // Mode S on device buffers: census -> cost -> 8 paths -> WTA (-> L/R check).
 // Any D in 1..256 runs at the native width Dp = padded_D(D): the cost kernels
 // write 255 at d >= D and the WTA ignores those disparities.
@@ -271,54 +305,24 @@ int run_sgm_device(Ctx* c, const uint8_t* left, const uint8_t* right, int W, int
         SVA_HIP(c, c->disp_r.ensure(np * 2), "lr workspace");
         dr = (uint16_t*)c->disp_r.ptr;
     }
-    if (p->dir_y == 0 && Dp >= tune::kCensusCostMinD && census_cost_supported(Dp)) {
-        // census maps stay on chip: one census+cost kernel (census_cost.hip),
-        // once per matching role when the L/R check runs.
-        SVA_HIP(c, launch_census_cost(*c, left, right, W, H, pitch, Dp, p->dmin, p->dir, C, p->D),
-                "cost launch");
-        if ((s = paths_wta(c, C, W, H, p, Dp, disp, sub, cf))) return s;
-        if (p->lr_check) {
-            // right image as reference: the images swap roles, the step flips
-            SVA_HIP(c, launch_census_cost(*c, right, left, W, H, pitch, Dp, p->dmin, -p->dir, C,
-                                          p->D),
-                    "cost launch");
-            if ((s = paths_wta(c, C, W, H, p, Dp, dr, nullptr))) return s;
-            SVA_HIP(c, launch_lr_check(*c, disp, dr, sub, W, H, p->dir, 0, p->lr_max_diff,
-                                       p->invalid),
-                    "lr launch");
-        }
-        return SVA_OK;
+    const CostRoute route = cost_route(Dp, p->dir, p->dir_y);
+    uint64_t *cl = nullptr, *cr = nullptr;
+    if (route == CostRoute::Split) {
+        SVA_HIP(c, c->census_l.ensure(np * 8), "census workspace");
+        SVA_HIP(c, c->census_r.ensure(np * 8), "census workspace");
+        cl = (uint64_t*)c->census_l.ptr;
+        cr = (uint64_t*)c->census_r.ptr;
     }
-    if (census_cost2_supported(Dp, p->dir, p->dir_y)) {
-        // 2-D array steps with |by| = 1 (every rig baseline of getCameraPairs
-        // and of BASELINE config 4): census + cost on the matrix cores in one
-        // kernel (census_cost2.hip)
-        SVA_HIP(c, launch_census_cost2(*c, left, right, W, H, pitch, Dp, p->dmin, p->dir,
-                                       p->dir_y, C, p->D),
-                "cost launch");
-        if ((s = paths_wta(c, C, W, H, p, Dp, disp, sub, cf))) return s;
-        if (p->lr_check) {
-            SVA_HIP(c, launch_census_cost2(*c, right, left, W, H, pitch, Dp, p->dmin, -p->dir,
-                                           -p->dir_y, C, p->D),
-                    "cost launch");
-            if ((s = paths_wta(c, C, W, H, p, Dp, dr, nullptr))) return s;
-            SVA_HIP(c, launch_lr_check(*c, disp, dr, sub, W, H, p->dir, p->dir_y, p->lr_max_diff,
-                                       p->invalid),
-                    "lr launch");
-        }
-        return SVA_OK;
-    }
-    SVA_HIP(c, c->census_l.ensure(np * 8), "census workspace");
-    SVA_HIP(c, c->census_r.ensure(np * 8), "census workspace");
-    uint64_t* cl = (uint64_t*)c->census_l.ptr;
-    uint64_t* cr = (uint64_t*)c->census_r.ptr;
-    SVA_HIP(c, launch_census_pair(*c, left, right, W, H, pitch, cl, cr), "census launch");
-    SVA_HIP(c, launch_cost2(*c, cl, cr, W, H, Dp, p->dmin, p->dir, p->dir_y, C, p->D),
-            "cost launch");
+    const char* what = "cost launch";
+    hipError_t e = form_cost(*c, route, left, right, W, H, pitch, Dp, p, p->dir, p->dir_y, C, cl, cr,
+                             true, &what);
+    if (e != hipSuccess) return hip_fail(c, e, what);
     if ((s = paths_wta(c, C, W, H, p, Dp, disp, sub, cf))) return s;
     if (p->lr_check) {
-        // right image as reference: roles of the census maps swap, the step flips
-        SVA_HIP(c, launch_cost2(*c, cr, cl, W, H, Dp, p->dmin, -p->dir, -p->dir_y, C, p->D),
+        // right image as reference: the images (on the split route their
+        // census maps, no second census) swap roles, the step flips
+        SVA_HIP(c, form_cost(*c, route, right, left, W, H, pitch, Dp, p, -p->dir, -p->dir_y, C, cr,
+                             cl, false),
                 "cost launch");
         if ((s = paths_wta(c, C, W, H, p, Dp, dr, nullptr))) return s;
         SVA_HIP(c, launch_lr_check(*c, disp, dr, sub, W, H, p->dir, p->dir_y, p->lr_max_diff,
@@ -326,6 +330,15 @@ int run_sgm_device(Ctx* c, const uint8_t* left, const uint8_t* right, int W, int
                 "lr launch");
     }
     return SVA_OK;
+}
+
+// cf's planes `off` pixels on: a chunk's or a sub-batch's frames of a batch.
+ConfOut conf_at(const ConfOut* cf, size_t off) {
+    ConfOut r;
+    if (cf) r = *cf;
+    if (r.cost_min) r.cost_min += off;
+    if (r.cost_second) r.cost_second += off;
+    return r;
 }
 
 // A batch of frames of one shape through few launches of each aggregation
@@ -348,7 +361,7 @@ int run_sgm_batch(Ctx* c, const sva_pair_d* jobs, int n, int W, int H, size_t pi
     const int Dp = padded_D(p->D);
     const size_t np = (size_t)W * H, nv = np * (size_t)Dp;
     const TileGeom tg = tile_geom(W, H, Dp);
-    const size_t ckb = tg.hck_bytes + tg.vck_bytes;
+    const size_t ckb = frame_ckpt_bytes(tg, false);
     const int sb = tune::kBatchSubFrames > 0 ? std::min(n, tune::kBatchSubFrames) : n;
     const int nsub = (n + sb - 1) / sb;
     SVA_HIP(c, c->cost.ensure(nv * n), "cost workspace");
@@ -382,22 +395,13 @@ int run_sgm_batch(Ctx* c, const sva_pair_d* jobs, int n, int W, int H, size_t pi
         const sva_sgm_params* q = &jobs[i].params;
         uint8_t* Ci = C + (size_t)i * nv;
         if (ns > 1) c->stream = c->side[i % ns];
-        hipError_t e;
-        if (i + 1 == fail_at) {
-            e = hipErrorLaunchFailure;
-        } else if (q->dir_y == 0 && Dp >= tune::kCensusCostMinD && census_cost_supported(Dp)) {
-            e = launch_census_cost(*c, jobs[i].left, jobs[i].right, W, H, pitch, Dp, q->dmin, q->dir,
-                                   Ci, q->D);
-        } else if (census_cost2_supported(Dp, q->dir, q->dir_y)) {
-            e = launch_census_cost2(*c, jobs[i].left, jobs[i].right, W, H, pitch, Dp, q->dmin,
-                                    q->dir, q->dir_y, Ci, q->D);
-        } else {
-            uint64_t* cl = (uint64_t*)c->census_side.ptr + (size_t)(i % std::max(ns, 1)) * 2 * np;
-            uint64_t* cr = cl + np;
-            e = launch_census_pair(*c, jobs[i].left, jobs[i].right, W, H, pitch, cl, cr);
-            if (e == hipSuccess)
-                e = launch_cost2(*c, cl, cr, W, H, Dp, q->dmin, q->dir, q->dir_y, Ci, q->D);
-        }
+        // (the split route's census maps: this side stream's slot)
+        uint64_t* cl = (uint64_t*)c->census_side.ptr + (size_t)(i % std::max(ns, 1)) * 2 * np;
+        hipError_t e = i + 1 == fail_at
+                           ? hipErrorLaunchFailure
+                           : form_cost(*c, cost_route(Dp, q->dir, q->dir_y), jobs[i].left,
+                                       jobs[i].right, W, H, pitch, Dp, q, q->dir, q->dir_y, Ci, cl,
+                                       cl + np, true);
         // the last frame of a sub-batch on this side stream (or of the batch)
         if (e == hipSuccess && ns > 1 && (i + ns >= n || (i + ns) / sb != i / sb))
             e = hipEventRecord(c->side_done[(size_t)(i / sb) * ns + i % ns], c->stream);
@@ -427,12 +431,7 @@ int run_sgm_batch(Ctx* c, const sva_pair_d* jobs, int n, int W, int H, size_t pi
             st = hip_fail(c, e, "paths launch");
             break;
         }
-        ConfOut cfj;
-        if (cf) {
-            cfj = *cf;
-            if (cfj.cost_min) cfj.cost_min += (size_t)i0 * np;
-            if (cfj.cost_second) cfj.cost_second += (size_t)i0 * np;
-        }
+        const ConfOut cfj = conf_at(cf, (size_t)i0 * np);
         if ((e = launch_wta_hv(*c, Cj, L4, CK, CKV, W, H, Dp, p->P1, p->P2, p->dmin,
                                maps + (size_t)i0 * np,
                                p->subpixel && sub ? sub + (size_t)i0 * np : nullptr, p->D, m, false,
@@ -537,6 +536,55 @@ int run_improve(Ctx* c, const uint8_t* disp, const uint8_t* center, const uint8_
     }
     return SVA_OK;
 }
+
+int check_uniqueness(Ctx* c, int uniqueness) {
+    if (uniqueness < 0 || uniqueness > 100)
+        return fail(c, SVA_ERR_INVALID_ARG, "uniqueness must be 0..100 (percent, 0 = off)");
+    return SVA_OK;
+}
+
+// Staging of the host-pointer entry points over the context's in_* / out_*
+// buffers, everything on c->stream.  A step that fails leaves its status in
+// st and turns the later steps into no-ops: an entry point stages its inputs,
+// returns st if set, runs its _d twin's run function on the staged pointers,
+// downloads and returns sync().
+struct Staging {
+    Ctx* c;
+    int st = SVA_OK;
+    void note(hipError_t e, const char* what) {
+        if (e != hipSuccess) st = hip_fail(c, e, what);
+    }
+    // b grown to `bytes`: an output, or the destination of the uploads below
+    template <class T>
+    T* out(DevBuf& b, size_t bytes) {
+        if (st == SVA_OK) note(b.ensure(bytes), "staging");
+        return (T*)b.ptr;
+    }
+    template <class T>
+    T* up(DevBuf& b, const void* src, size_t bytes) {
+        T* d = out<T>(b, bytes);
+        if (st == SVA_OK)
+            note(hipMemcpyAsync(d, src, bytes, hipMemcpyHostToDevice, c->stream), "upload");
+        return d;
+    }
+    // H rows of W bytes, `pitch` apart at the caller's, packed on the device
+    uint8_t* up2d(DevBuf& b, const uint8_t* src, size_t pitch, int W, int H) {
+        uint8_t* d = out<uint8_t>(b, (size_t)W * H);
+        if (st == SVA_OK)
+            note(hipMemcpy2DAsync(d, W, src, pitch, W, H, hipMemcpyHostToDevice, c->stream),
+                 "upload");
+        return d;
+    }
+    // (an optional output the caller left out, dst null, is skipped)
+    void down(void* dst, const void* src, size_t bytes) {
+        if (st == SVA_OK && dst)
+            note(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream), "download");
+    }
+    int sync() {
+        if (st == SVA_OK) note(hipStreamSynchronize(c->stream), "sync");
+        return st;
+    }
+};
 
 }  // namespace
 
@@ -877,21 +925,50 @@ int sva_kernel_time(void* ctx, const char* name, double* total_ms, int64_t* coun
 }
 
 // ---------------------------------------------------------------- Mode S --
-int sva_disparity_sgm_d(void* ctx, const uint8_t* left, const uint8_t* right, int W, int H,
-                        size_t pitch, const sva_sgm_params* p, uint16_t* disp, float* sub) {
+namespace {
+// Arguments of sva_disparity_sgm[_conf][_d]; the plain forms pass uniqueness 0.
+int check_sgm_frame(Ctx* c, const uint8_t* left, const uint8_t* right, int W, int H, size_t pitch,
+                    const sva_sgm_params* p, int uniqueness, const uint16_t* disp) {
+    int s;
+    if ((s = check_image(c, left, W, H, pitch)) || (s = check_image(c, right, W, H, pitch)) ||
+        (s = check_sgm(c, p, W, H)) || (s = check_uniqueness(c, uniqueness)))
+        return s;
+    if (!disp) return fail(c, SVA_ERR_INVALID_ARG, "null disparity output");
+    return SVA_OK;
+}
+
+// The host-buffer forms of Mode S: sva_disparity_sgm (conf false) and
+// sva_disparity_sgm_conf, which adds the WTA's confidence planes and the
+// uniqueness filter.
+int sgm_host(void* ctx, const uint8_t* left, const uint8_t* right, int W, int H, size_t pitch,
+             const sva_sgm_params* p, bool conf, int uniqueness, uint16_t* disp, float* sub,
+             uint16_t* cost_min, uint16_t* cost_second) {
     Ctx* c = as_ctx(ctx);
     SVA_CHECK_CTX(c);
     int s;
-    if ((s = check_image(c, left, W, H, pitch)) || (s = check_image(c, right, W, H, pitch)) ||
-        (s = check_sgm(c, p, W, H)))
-        return s;
-    if (!disp) return fail(c, SVA_ERR_INVALID_ARG, "null disparity output");
-    return run_sgm_device(c, left, right, W, H, pitch, p, disp, p->subpixel ? sub : nullptr);
+    if ((s = check_sgm_frame(c, left, right, W, H, pitch, p, uniqueness, disp))) return s;
+    const bool want_sub = p->subpixel && sub;
+    const size_t np = (size_t)W * H;
+    Staging g{c};
+    const uint8_t* dl = g.up2d(c->in_a, left, pitch, W, H);
+    const uint8_t* dr = g.up2d(c->in_b, right, pitch, W, H);
+    uint16_t* dd = g.out<uint16_t>(c->out_a, np * 2);
+    float* ds = want_sub ? g.out<float>(c->out_b, np * 4) : nullptr;
+    // the two cost planes share one staging buffer
+    uint16_t* dc = cost_min || cost_second ? g.out<uint16_t>(c->out_c, np * 4) : nullptr;
+    if (g.st) return g.st;
+    const ConfOut cf{cost_min ? dc : nullptr, cost_second ? dc + np : nullptr, uniqueness,
+                     p->invalid};
+    if ((s = run_sgm_device(c, dl, dr, W, H, W, p, dd, ds, conf ? &cf : nullptr))) return s;
+    g.down(disp, dd, np * 2);
+    if (want_sub) g.down(sub, ds, np * 4);
+    g.down(cost_min, cf.cost_min, np * 2);
+    g.down(cost_second, cf.cost_second, np * 2);
+    return g.sync();
 }
 
 // The batch entry points: sva_disparity_sgm_batch_d (cf null) and its
 // confidence form.
-namespace {
 int sgm_batch_d(void* ctx, const sva_pair_d* jobs, int n, int W, int H, size_t pitch,
                 uint16_t* maps, float* sub, const ConfOut* cf) {
     Ctx* c = as_ctx(ctx);
@@ -901,9 +978,8 @@ int sgm_batch_d(void* ctx, const sva_pair_d* jobs, int n, int W, int H, size_t p
     const int fail_at = c->dbg_fail_cost_at;
     c->dbg_fail_cost_at = 0;
     if (!jobs || n <= 0 || !maps) return fail(c, SVA_ERR_INVALID_ARG, "bad batch argument");
-    if (cf && (cf->uniqueness < 0 || cf->uniqueness > 100))
-        return fail(c, SVA_ERR_INVALID_ARG, "uniqueness must be 0..100 (percent, 0 = off)");
     int s;
+    if (cf && (s = check_uniqueness(c, cf->uniqueness))) return s;
     const sva_sgm_params* p0 = &jobs[0].params;
     for (int i = 0; i < n; i++) {
         const sva_sgm_params* q = &jobs[i].params;
@@ -924,91 +1000,55 @@ int sgm_batch_d(void* ctx, const sva_pair_d* jobs, int n, int W, int H, size_t p
     // chunks of at most tune::kBatchMaxPairs frames, whose workspaces stay
     // under tune::kBatchMaxBytes
     const int Dp = padded_D(p0->D);
-    const TileGeom tg = tile_geom(W, H, Dp);
-    const size_t per = (size_t)W * H * (size_t)Dp * (1 + kDiagVolumes) + tg.hck_bytes + tg.vck_bytes;
+    const size_t np = (size_t)W * H;
+    const size_t per = np * (size_t)Dp * (1 + kDiagVolumes) + frame_ckpt_bytes(tile_geom(W, H, Dp), false);
     int chunk = tune::kBatchMaxPairs;
     while (chunk > 1 && per * (size_t)chunk > tune::kBatchMaxBytes) chunk--;
-    const size_t np = (size_t)W * H;
     for (int i0 = 0; i0 < n; i0 += chunk) {
-        const int m = std::min(chunk, n - i0);
-        ConfOut cfi;
-        if (cf) {
-            cfi = *cf;
-            if (cfi.cost_min) cfi.cost_min += (size_t)i0 * np;
-            if (cfi.cost_second) cfi.cost_second += (size_t)i0 * np;
-        }
+        const ConfOut cfi = conf_at(cf, (size_t)i0 * np);
         // (the injected failure counts the first chunk's launches, as before)
-        if ((s = run_sgm_batch(c, jobs + i0, m, W, H, pitch, maps + (size_t)i0 * np,
-                               sub ? sub + (size_t)i0 * np : nullptr, cf ? &cfi : nullptr,
-                               i0 == 0 ? fail_at : 0)))
+        if ((s = run_sgm_batch(c, jobs + i0, std::min(chunk, n - i0), W, H, pitch,
+                               maps + (size_t)i0 * np, sub ? sub + (size_t)i0 * np : nullptr,
+                               cf ? &cfi : nullptr, i0 == 0 ? fail_at : 0)))
             return s;
     }
     return SVA_OK;
 }
 }  // namespace
 
-int sva_disparity_sgm_batch_d(void* ctx, const sva_pair_d* jobs, int n, int W, int H,
-                              size_t pitch, uint16_t* maps, float* sub) {
-    return sgm_batch_d(ctx, jobs, n, W, H, pitch, maps, sub, nullptr);
+int sva_disparity_sgm_d(void* ctx, const uint8_t* left, const uint8_t* right, int W, int H,
+                        size_t pitch, const sva_sgm_params* p, uint16_t* disp, float* sub) {
+    Ctx* c = as_ctx(ctx);
+    SVA_CHECK_CTX(c);
+    if (int s = check_sgm_frame(c, left, right, W, H, pitch, p, 0, disp)) return s;
+    return run_sgm_device(c, left, right, W, H, pitch, p, disp, p->subpixel ? sub : nullptr);
 }
 
 int sva_disparity_sgm(void* ctx, const uint8_t* left, const uint8_t* right, int W, int H,
                       size_t pitch, const sva_sgm_params* p, uint16_t* disp, float* sub) {
-    Ctx* c = as_ctx(ctx);
-    SVA_CHECK_CTX(c);
-    int s;
-    if ((s = check_image(c, left, W, H, pitch)) || (s = check_image(c, right, W, H, pitch)) ||
-        (s = check_sgm(c, p, W, H)))
-        return s;
-    if (!disp) return fail(c, SVA_ERR_INVALID_ARG, "null disparity output");
-    const bool want_sub = p->subpixel && sub;
-    const size_t np = (size_t)W * H;
-    SVA_HIP(c, c->in_a.ensure(np), "staging");
-    SVA_HIP(c, c->in_b.ensure(np), "staging");
-    SVA_HIP(c, c->out_a.ensure(np * 2), "staging");
-    if (want_sub) SVA_HIP(c, c->out_b.ensure(np * 4), "staging");
-    SVA_HIP(c, hipMemcpy2DAsync(c->in_a.ptr, W, left, pitch, W, H, hipMemcpyHostToDevice, c->stream),
-            "upload");
-    SVA_HIP(c, hipMemcpy2DAsync(c->in_b.ptr, W, right, pitch, W, H, hipMemcpyHostToDevice, c->stream),
-            "upload");
-    if ((s = run_sgm_device(c, (uint8_t*)c->in_a.ptr, (uint8_t*)c->in_b.ptr, W, H, W, p,
-                            (uint16_t*)c->out_a.ptr, want_sub ? (float*)c->out_b.ptr : nullptr)))
-        return s;
-    SVA_HIP(c, hipMemcpyAsync(disp, c->out_a.ptr, np * 2, hipMemcpyDeviceToHost, c->stream),
-            "download");
-    if (want_sub)
-        SVA_HIP(c, hipMemcpyAsync(sub, c->out_b.ptr, np * 4, hipMemcpyDeviceToHost, c->stream),
-                "download");
-    SVA_HIP(c, hipStreamSynchronize(c->stream), "sync");
-    return SVA_OK;
+    return sgm_host(ctx, left, right, W, H, pitch, p, false, 0, disp, sub, nullptr, nullptr);
 }
-
-// Mode S with the WTA's confidence planes and the uniqueness filter (DESIGN.md
-// §2.4b): the frame route with wta_hv's confidence instance.
-namespace {
-int check_uniqueness(Ctx* c, int uniqueness) {
-    if (uniqueness < 0 || uniqueness > 100)
-        return fail(c, SVA_ERR_INVALID_ARG, "uniqueness must be 0..100 (percent, 0 = off)");
-    return SVA_OK;
-}
-}  // namespace
 
 int sva_disparity_sgm_conf_d(void* ctx, const uint8_t* left, const uint8_t* right, int W, int H,
                              size_t pitch, const sva_sgm_params* p, int uniqueness, uint16_t* disp,
                              float* sub, uint16_t* cost_min, uint16_t* cost_second) {
     Ctx* c = as_ctx(ctx);
     SVA_CHECK_CTX(c);
-    int s;
-    if ((s = check_image(c, left, W, H, pitch)) || (s = check_image(c, right, W, H, pitch)) ||
-        (s = check_sgm(c, p, W, H)) || (s = check_uniqueness(c, uniqueness)))
-        return s;
-    if (!disp) return fail(c, SVA_ERR_INVALID_ARG, "null disparity output");
-    ConfOut cf;
-    cf.cost_min = cost_min;
-    cf.cost_second = cost_second;
-    cf.uniqueness = uniqueness;
-    cf.invalid = p->invalid;
+    if (int s = check_sgm_frame(c, left, right, W, H, pitch, p, uniqueness, disp)) return s;
+    const ConfOut cf{cost_min, cost_second, uniqueness, p->invalid};
     return run_sgm_device(c, left, right, W, H, pitch, p, disp, p->subpixel ? sub : nullptr, &cf);
+}
+
+int sva_disparity_sgm_conf(void* ctx, const uint8_t* left, const uint8_t* right, int W, int H,
+                           size_t pitch, const sva_sgm_params* p, int uniqueness, uint16_t* disp,
+                           float* sub, uint16_t* cost_min, uint16_t* cost_second) {
+    return sgm_host(ctx, left, right, W, H, pitch, p, true, uniqueness, disp, sub, cost_min,
+                    cost_second);
+}
+
+int sva_disparity_sgm_batch_d(void* ctx, const sva_pair_d* jobs, int n, int W, int H,
+                              size_t pitch, uint16_t* maps, float* sub) {
+    return sgm_batch_d(ctx, jobs, n, W, H, pitch, maps, sub, nullptr);
 }
 
 // The batch route with the confidence instance: frame j's
@@ -1016,59 +1056,9 @@ int sva_disparity_sgm_conf_d(void* ctx, const uint8_t* left, const uint8_t* righ
 int sva_disparity_sgm_batch_conf_d(void* ctx, const sva_pair_d* jobs, int n, int W, int H,
                                    size_t pitch, int uniqueness, uint16_t* maps, float* sub,
                                    uint16_t* cost_min, uint16_t* cost_second) {
-    ConfOut cf;
-    cf.cost_min = cost_min;
-    cf.cost_second = cost_second;
-    cf.uniqueness = uniqueness;
-    cf.invalid = jobs && n > 0 ? jobs[0].params.invalid : 0xffffu;
+    const ConfOut cf{cost_min, cost_second, uniqueness,
+                     jobs && n > 0 ? jobs[0].params.invalid : 0xffffu};
     return sgm_batch_d(ctx, jobs, n, W, H, pitch, maps, sub, &cf);
-}
-
-int sva_disparity_sgm_conf(void* ctx, const uint8_t* left, const uint8_t* right, int W, int H,
-                           size_t pitch, const sva_sgm_params* p, int uniqueness, uint16_t* disp,
-                           float* sub, uint16_t* cost_min, uint16_t* cost_second) {
-    Ctx* c = as_ctx(ctx);
-    SVA_CHECK_CTX(c);
-    int s;
-    if ((s = check_image(c, left, W, H, pitch)) || (s = check_image(c, right, W, H, pitch)) ||
-        (s = check_sgm(c, p, W, H)) || (s = check_uniqueness(c, uniqueness)))
-        return s;
-    if (!disp) return fail(c, SVA_ERR_INVALID_ARG, "null disparity output");
-    const bool want_sub = p->subpixel && sub;
-    const size_t np = (size_t)W * H;
-    SVA_HIP(c, c->in_a.ensure(np), "staging");
-    SVA_HIP(c, c->in_b.ensure(np), "staging");
-    SVA_HIP(c, c->out_a.ensure(np * 2), "staging");
-    if (want_sub) SVA_HIP(c, c->out_b.ensure(np * 4), "staging");
-    // the two cost planes share one staging buffer
-    if (cost_min || cost_second) SVA_HIP(c, c->out_c.ensure(np * 4), "staging");
-    ConfOut cf;
-    cf.cost_min = cost_min ? (uint16_t*)c->out_c.ptr : nullptr;
-    cf.cost_second = cost_second ? (uint16_t*)c->out_c.ptr + np : nullptr;
-    cf.uniqueness = uniqueness;
-    cf.invalid = p->invalid;
-    SVA_HIP(c, hipMemcpy2DAsync(c->in_a.ptr, W, left, pitch, W, H, hipMemcpyHostToDevice, c->stream),
-            "upload");
-    SVA_HIP(c, hipMemcpy2DAsync(c->in_b.ptr, W, right, pitch, W, H, hipMemcpyHostToDevice, c->stream),
-            "upload");
-    if ((s = run_sgm_device(c, (uint8_t*)c->in_a.ptr, (uint8_t*)c->in_b.ptr, W, H, W, p,
-                            (uint16_t*)c->out_a.ptr, want_sub ? (float*)c->out_b.ptr : nullptr,
-                            &cf)))
-        return s;
-    SVA_HIP(c, hipMemcpyAsync(disp, c->out_a.ptr, np * 2, hipMemcpyDeviceToHost, c->stream),
-            "download");
-    if (want_sub)
-        SVA_HIP(c, hipMemcpyAsync(sub, c->out_b.ptr, np * 4, hipMemcpyDeviceToHost, c->stream),
-                "download");
-    if (cost_min)
-        SVA_HIP(c, hipMemcpyAsync(cost_min, cf.cost_min, np * 2, hipMemcpyDeviceToHost, c->stream),
-                "download");
-    if (cost_second)
-        SVA_HIP(c, hipMemcpyAsync(cost_second, cf.cost_second, np * 2, hipMemcpyDeviceToHost,
-                                  c->stream),
-                "download");
-    SVA_HIP(c, hipStreamSynchronize(c->stream), "sync");
-    return SVA_OK;
 }
 
 int sva_census_d(void* ctx, const uint8_t* img, int W, int H, size_t pitch, uint64_t* census) {
@@ -1101,16 +1091,13 @@ int sva_census_cost_d(void* ctx, const uint8_t* left, const uint8_t* right, int 
     if ((s = check_image(c, left, W, H, pitch))) return s;
     if ((s = check_image(c, right, W, H, pitch))) return s;
     if (!C) return fail(c, SVA_ERR_INVALID_ARG, "null cost output");
-    if (p->dir_y == 0 && census_cost_supported(p->D)) {
-        SVA_HIP(c, launch_census_cost(*c, left, right, W, H, pitch, p->D, p->dmin, p->dir, C),
-                "cost launch");
-        return SVA_OK;
-    }
-    if (!census_cost2_supported(p->D, p->dir, p->dir_y))
+    const CostRoute route = cost_route(p->D, p->dir, p->dir_y);
+    if (route == CostRoute::Split)
         return fail(c, SVA_ERR_UNSUPPORTED,
                     "census+cost kernel: D in {64,128,192,256}, 1-D steps or 2-D steps whose "
                     "primitive form has |dir_y| = 1 and |dir| <= 3");
-    SVA_HIP(c, launch_census_cost2(*c, left, right, W, H, pitch, p->D, p->dmin, p->dir, p->dir_y, C),
+    SVA_HIP(c, form_cost(*c, route, left, right, W, H, pitch, p->D, p, p->dir, p->dir_y, C, nullptr,
+                         nullptr, false),
             "cost launch");
     return SVA_OK;
 }
@@ -1206,11 +1193,7 @@ int sva_wta_conf_d(void* ctx, const uint16_t* S, int W, int H, const sva_sgm_par
     int s;
     if ((s = check_sgm(c, p, W, H, true)) || (s = check_uniqueness(c, uniqueness))) return s;
     if (!S || !disp || W <= 0 || H <= 0) return fail(c, SVA_ERR_INVALID_ARG, "bad argument");
-    ConfOut cf;
-    cf.cost_min = cost_min;
-    cf.cost_second = cost_second;
-    cf.uniqueness = uniqueness;
-    cf.invalid = p->invalid;
+    const ConfOut cf{cost_min, cost_second, uniqueness, p->invalid};
     SVA_HIP(c, launch_wta_from_sum(*c, S, W, H, p->D, p->dmin, disp, p->subpixel ? sub : nullptr,
                                    &cf),
             "wta launch");
@@ -1232,18 +1215,28 @@ int sva_ref_endpoints_d(void* ctx, int W, int H, const sva_camera* cref, const s
     return SVA_OK;
 }
 
-int sva_disparity_ref_d(void* ctx, const uint8_t* ref, const uint8_t* other, int W, int H,
-                        size_t pitch, const uint8_t* mask, const sva_camera* cref,
-                        const sva_camera* coth, int k, double t_near, double t_far, uint8_t* d8,
-                        uint16_t* d16, uint8_t* valid) {
-    Ctx* c = as_ctx(ctx);
-    SVA_CHECK_CTX(c);
+namespace {
+int check_ref_frame(Ctx* c, const uint8_t* ref, const uint8_t* other, int W, int H, size_t pitch,
+                    const sva_camera* cref, const sva_camera* coth, int k, double t_near,
+                    double t_far, const uint8_t* d8) {
     int s;
     if ((s = check_image(c, ref, W, H, pitch)) || (s = check_image(c, other, W, H, pitch)) ||
         (s = check_camera(c, cref)) || (s = check_camera(c, coth)) ||
         (s = check_ref_args(c, W, H, k, t_near, t_far)))
         return s;
     if (!d8) return fail(c, SVA_ERR_INVALID_ARG, "null disparity output");
+    return SVA_OK;
+}
+}  // namespace
+
+int sva_disparity_ref_d(void* ctx, const uint8_t* ref, const uint8_t* other, int W, int H,
+                        size_t pitch, const uint8_t* mask, const sva_camera* cref,
+                        const sva_camera* coth, int k, double t_near, double t_far, uint8_t* d8,
+                        uint16_t* d16, uint8_t* valid) {
+    Ctx* c = as_ctx(ctx);
+    SVA_CHECK_CTX(c);
+    if (int s = check_ref_frame(c, ref, other, W, H, pitch, cref, coth, k, t_near, t_far, d8))
+        return s;
     return run_ref_device(c, ref, other, W, H, pitch, mask, cref, coth, k, t_near, t_far, d8, d16,
                           valid);
 }
@@ -1255,36 +1248,25 @@ int sva_disparity_ref(void* ctx, const uint8_t* ref, const uint8_t* other, int W
     Ctx* c = as_ctx(ctx);
     SVA_CHECK_CTX(c);
     int s;
-    if ((s = check_image(c, ref, W, H, pitch)) || (s = check_image(c, other, W, H, pitch)) ||
-        (s = check_camera(c, cref)) || (s = check_camera(c, coth)) ||
-        (s = check_ref_args(c, W, H, k, t_near, t_far)))
+    if ((s = check_ref_frame(c, ref, other, W, H, pitch, cref, coth, k, t_near, t_far, d8)))
         return s;
-    if (!d8) return fail(c, SVA_ERR_INVALID_ARG, "null disparity output");
     const size_t np = (size_t)W * H;
-    SVA_HIP(c, c->in_a.ensure(np), "staging");
-    SVA_HIP(c, c->in_b.ensure(np), "staging");
-    SVA_HIP(c, c->out_a.ensure(np), "staging");
-    if (mask) SVA_HIP(c, c->in_mask.ensure(np), "staging");
-    if (d16) SVA_HIP(c, c->out_b.ensure(np * 2), "staging");
-    if (valid) SVA_HIP(c, c->out_c.ensure(np), "staging");
-    hipStream_t st = c->stream;
-    SVA_HIP(c, hipMemcpy2DAsync(c->in_a.ptr, W, ref, pitch, W, H, hipMemcpyHostToDevice, st), "upload");
-    SVA_HIP(c, hipMemcpy2DAsync(c->in_b.ptr, W, other, pitch, W, H, hipMemcpyHostToDevice, st), "upload");
-    if (mask) SVA_HIP(c, hipMemcpyAsync(c->in_mask.ptr, mask, np, hipMemcpyHostToDevice, st), "upload");
+    Staging g{c};
+    const uint8_t* dref = g.up2d(c->in_a, ref, pitch, W, H);
+    const uint8_t* doth = g.up2d(c->in_b, other, pitch, W, H);
+    const uint8_t* dmask = mask ? g.up<uint8_t>(c->in_mask, mask, np) : nullptr;
     // untouched pixels keep the caller's values (CameraStereoVision.cpp:46,55)
-    SVA_HIP(c, hipMemcpyAsync(c->out_a.ptr, d8, np, hipMemcpyHostToDevice, st), "upload");
-    if (d16) SVA_HIP(c, hipMemcpyAsync(c->out_b.ptr, d16, np * 2, hipMemcpyHostToDevice, st), "upload");
-    if (valid) SVA_HIP(c, hipMemcpyAsync(c->out_c.ptr, valid, np, hipMemcpyHostToDevice, st), "upload");
-    if ((s = run_ref_device(c, (uint8_t*)c->in_a.ptr, (uint8_t*)c->in_b.ptr, W, H, W,
-                            mask ? (uint8_t*)c->in_mask.ptr : nullptr, cref, coth, k, t_near,
-                            t_far, (uint8_t*)c->out_a.ptr, d16 ? (uint16_t*)c->out_b.ptr : nullptr,
-                            valid ? (uint8_t*)c->out_c.ptr : nullptr)))
+    uint8_t* o8 = g.up<uint8_t>(c->out_a, d8, np);
+    uint16_t* o16 = d16 ? g.up<uint16_t>(c->out_b, d16, np * 2) : nullptr;
+    uint8_t* ov = valid ? g.up<uint8_t>(c->out_c, valid, np) : nullptr;
+    if (g.st) return g.st;
+    if ((s = run_ref_device(c, dref, doth, W, H, W, dmask, cref, coth, k, t_near, t_far, o8, o16,
+                            ov)))
         return s;
-    SVA_HIP(c, hipMemcpyAsync(d8, c->out_a.ptr, np, hipMemcpyDeviceToHost, st), "download");
-    if (d16) SVA_HIP(c, hipMemcpyAsync(d16, c->out_b.ptr, np * 2, hipMemcpyDeviceToHost, st), "download");
-    if (valid) SVA_HIP(c, hipMemcpyAsync(valid, c->out_c.ptr, np, hipMemcpyDeviceToHost, st), "download");
-    SVA_HIP(c, hipStreamSynchronize(st), "sync");
-    return SVA_OK;
+    g.down(d8, o8, np);
+    g.down(d16, o16, np * 2);
+    g.down(valid, ov, np);
+    return g.sync();
 }
 
 int sva_disparity_to_depth_d(void* ctx, const uint8_t* disp, int n, double cam_distance,
@@ -1303,18 +1285,16 @@ int sva_disparity_to_depth(void* ctx, const uint8_t* disp, int n, double cam_dis
     SVA_CHECK_CTX(c);
     if (!disp || !depth || n < 0) return fail(c, SVA_ERR_INVALID_ARG, "bad argument");
     if (n == 0) return SVA_OK;
-    SVA_HIP(c, c->in_a.ensure((size_t)n), "staging");
-    SVA_HIP(c, c->out_a.ensure((size_t)n * 8), "staging");
-    SVA_HIP(c, hipMemcpyAsync(c->in_a.ptr, disp, (size_t)n, hipMemcpyHostToDevice, c->stream),
-            "upload");
-    SVA_HIP(c, launch_disp_to_depth(*c, (uint8_t*)c->in_a.ptr, n, cam_distance, f, pixel_size,
-                                    (double*)c->out_a.ptr), "depth launch");
-    SVA_HIP(c, hipMemcpyAsync(depth, c->out_a.ptr, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream),
-            "download");
-    SVA_HIP(c, hipStreamSynchronize(c->stream), "sync");
-    return SVA_OK;
+    Staging g{c};
+    const uint8_t* dd = g.up<uint8_t>(c->in_a, disp, (size_t)n);
+    double* dz = g.out<double>(c->out_a, (size_t)n * 8);
+    if (g.st) return g.st;
+    SVA_HIP(c, launch_disp_to_depth(*c, dd, n, cam_distance, f, pixel_size, dz), "depth launch");
+    g.down(depth, dz, (size_t)n * 8);
+    return g.sync();
 }
 
+namespace {
 int check_fuse(Ctx* c, const uint16_t* disps, int n_maps, int W, int H, const double* b,
                const double* depth) {
     if (!disps || !b || !depth) return fail(c, SVA_ERR_INVALID_ARG, "null pointer");
@@ -1323,49 +1303,8 @@ int check_fuse(Ctx* c, const uint16_t* disps, int n_maps, int W, int H, const do
     return SVA_OK;
 }
 
-int sva_fuse_depth_d(void* ctx, const uint16_t* disps, int n_maps, int W, int H,
-                     const double* baselines, double f, double pixel_size, uint16_t invalid,
-                     double* depth, uint8_t* n_valid) {
-    Ctx* c = as_ctx(ctx);
-    SVA_CHECK_CTX(c);
-    int s;
-    if ((s = check_fuse(c, disps, n_maps, W, H, baselines, depth))) return s;
-    double num[32];
-    for (int i = 0; i < n_maps; i++) num[i] = baselines[i] * f;
-    SVA_HIP(c, launch_fuse_depth(*c, disps, n_maps, (size_t)W * H, num, pixel_size, invalid,
-                                 depth, n_valid), "fuse launch");
-    return SVA_OK;
-}
-
-int sva_fuse_depth(void* ctx, const uint16_t* disps, int n_maps, int W, int H,
-                   const double* baselines, double f, double pixel_size, uint16_t invalid,
-                   double* depth, uint8_t* n_valid) {
-    Ctx* c = as_ctx(ctx);
-    SVA_CHECK_CTX(c);
-    int s;
-    if ((s = check_fuse(c, disps, n_maps, W, H, baselines, depth))) return s;
-    const size_t np = (size_t)W * H, in_bytes = np * 2 * (size_t)n_maps;
-    double num[32];
-    for (int i = 0; i < n_maps; i++) num[i] = baselines[i] * f;
-    SVA_HIP(c, c->in_a.ensure(in_bytes), "staging");
-    SVA_HIP(c, c->out_a.ensure(np * 8), "staging");
-    SVA_HIP(c, c->out_b.ensure(np), "staging");
-    SVA_HIP(c, hipMemcpyAsync(c->in_a.ptr, disps, in_bytes, hipMemcpyHostToDevice, c->stream),
-            "upload");
-    SVA_HIP(c, launch_fuse_depth(*c, (const uint16_t*)c->in_a.ptr, n_maps, np, num, pixel_size,
-                                 invalid, (double*)c->out_a.ptr, (uint8_t*)c->out_b.ptr),
-            "fuse launch");
-    SVA_HIP(c, hipMemcpyAsync(depth, c->out_a.ptr, np * 8, hipMemcpyDeviceToHost, c->stream),
-            "download");
-    if (n_valid)
-        SVA_HIP(c, hipMemcpyAsync(n_valid, c->out_b.ptr, np, hipMemcpyDeviceToHost, c->stream),
-                "download");
-    SVA_HIP(c, hipStreamSynchronize(c->stream), "sync");
-    return SVA_OK;
-}
-
 // Cost-aware fusion.
-static int check_fuse_conf(Ctx* c, const uint16_t* disps, const uint16_t* cost_min,
+int check_fuse_conf(Ctx* c, const uint16_t* disps, const uint16_t* cost_min,
                     const uint16_t* cost_second, int n_maps, int W, int H, const double* b,
                     int mode, const double* depth) {
     if (!disps || !cost_min || !b || !depth) return fail(c, SVA_ERR_INVALID_ARG, "null pointer");
@@ -1378,21 +1317,75 @@ static int check_fuse_conf(Ctx* c, const uint16_t* disps, const uint16_t* cost_m
     return SVA_OK;
 }
 
+// Both fusions on device planes: the median (mode < 0; cost planes and winner
+// unused) and the cost-aware ones.
+int run_fuse(Ctx* c, const uint16_t* disps, const uint16_t* cost_min, const uint16_t* cost_second,
+             int n_maps, size_t np, const double* baselines, double f, double pixel_size,
+             uint16_t invalid, int mode, double* depth, uint8_t* n_valid, uint8_t* winner) {
+    double num[32];
+    for (int i = 0; i < n_maps; i++) num[i] = baselines[i] * f;
+    SVA_HIP(c, mode < 0 ? launch_fuse_depth(*c, disps, n_maps, np, num, pixel_size, invalid, depth,
+                                            n_valid)
+                        : launch_fuse_depth_conf(*c, disps, cost_min, cost_second, n_maps, np, num,
+                                                 pixel_size, invalid, mode, depth, n_valid, winner),
+            "fuse launch");
+    return SVA_OK;
+}
+
+// The host-buffer forms of both fusions, after their checks (median: mode < 0).
+int fuse_host(Ctx* c, const uint16_t* disps, const uint16_t* cost_min, const uint16_t* cost_second,
+              int n_maps, int W, int H, const double* baselines, double f, double pixel_size,
+              uint16_t invalid, int mode, double* depth, uint8_t* n_valid, uint8_t* winner) {
+    const size_t np = (size_t)W * H, in_bytes = np * 2 * (size_t)n_maps;
+    Staging g{c};
+    const uint16_t* dd = g.up<uint16_t>(c->in_a, disps, in_bytes);
+    const uint16_t* dmin = cost_min ? g.up<uint16_t>(c->in_b, cost_min, in_bytes) : nullptr;
+    const uint16_t* dsec = cost_second ? g.up<uint16_t>(c->in_c, cost_second, in_bytes) : nullptr;
+    double* dz = g.out<double>(c->out_a, np * 8);
+    uint8_t* dn = g.out<uint8_t>(c->out_b, np);
+    uint8_t* dw = mode < 0 ? nullptr : g.out<uint8_t>(c->out_c, np);
+    if (g.st) return g.st;
+    if (int s = run_fuse(c, dd, dmin, dsec, n_maps, np, baselines, f, pixel_size, invalid, mode, dz,
+                         dn, dw))
+        return s;
+    g.down(depth, dz, np * 8);
+    g.down(n_valid, dn, np);
+    g.down(winner, dw, np);
+    return g.sync();
+}
+}  // namespace
+
+int sva_fuse_depth_d(void* ctx, const uint16_t* disps, int n_maps, int W, int H,
+                     const double* baselines, double f, double pixel_size, uint16_t invalid,
+                     double* depth, uint8_t* n_valid) {
+    Ctx* c = as_ctx(ctx);
+    SVA_CHECK_CTX(c);
+    if (int s = check_fuse(c, disps, n_maps, W, H, baselines, depth)) return s;
+    return run_fuse(c, disps, nullptr, nullptr, n_maps, (size_t)W * H, baselines, f, pixel_size,
+                    invalid, -1, depth, n_valid, nullptr);
+}
+
+int sva_fuse_depth(void* ctx, const uint16_t* disps, int n_maps, int W, int H,
+                   const double* baselines, double f, double pixel_size, uint16_t invalid,
+                   double* depth, uint8_t* n_valid) {
+    Ctx* c = as_ctx(ctx);
+    SVA_CHECK_CTX(c);
+    if (int s = check_fuse(c, disps, n_maps, W, H, baselines, depth)) return s;
+    return fuse_host(c, disps, nullptr, nullptr, n_maps, W, H, baselines, f, pixel_size, invalid,
+                     -1, depth, n_valid, nullptr);
+}
+
 int sva_fuse_depth_conf_d(void* ctx, const uint16_t* disps, const uint16_t* cost_min,
                           const uint16_t* cost_second, int n_maps, int W, int H,
                           const double* baselines, double f, double pixel_size, uint16_t invalid,
                           int mode, double* depth, uint8_t* n_valid, uint8_t* winner) {
     Ctx* c = as_ctx(ctx);
     SVA_CHECK_CTX(c);
-    int s;
-    if ((s = check_fuse_conf(c, disps, cost_min, cost_second, n_maps, W, H, baselines, mode, depth)))
+    if (int s = check_fuse_conf(c, disps, cost_min, cost_second, n_maps, W, H, baselines, mode,
+                                depth))
         return s;
-    double num[32];
-    for (int i = 0; i < n_maps; i++) num[i] = baselines[i] * f;
-    SVA_HIP(c, launch_fuse_depth_conf(*c, disps, cost_min, cost_second, n_maps, (size_t)W * H, num,
-                                      pixel_size, invalid, mode, depth, n_valid, winner),
-            "fuse launch");
-    return SVA_OK;
+    return run_fuse(c, disps, cost_min, cost_second, n_maps, (size_t)W * H, baselines, f,
+                    pixel_size, invalid, mode, depth, n_valid, winner);
 }
 
 int sva_fuse_depth_conf(void* ctx, const uint16_t* disps, const uint16_t* cost_min,
@@ -1401,55 +1394,92 @@ int sva_fuse_depth_conf(void* ctx, const uint16_t* disps, const uint16_t* cost_m
                         int mode, double* depth, uint8_t* n_valid, uint8_t* winner) {
     Ctx* c = as_ctx(ctx);
     SVA_CHECK_CTX(c);
-    int s;
-    if ((s = check_fuse_conf(c, disps, cost_min, cost_second, n_maps, W, H, baselines, mode, depth)))
+    if (int s = check_fuse_conf(c, disps, cost_min, cost_second, n_maps, W, H, baselines, mode,
+                                depth))
         return s;
-    const size_t np = (size_t)W * H, in_bytes = np * 2 * (size_t)n_maps;
-    double num[32];
-    for (int i = 0; i < n_maps; i++) num[i] = baselines[i] * f;
-    SVA_HIP(c, c->in_a.ensure(in_bytes), "staging");
-    SVA_HIP(c, c->in_b.ensure(in_bytes), "staging");
-    if (cost_second) SVA_HIP(c, c->in_c.ensure(in_bytes), "staging");
-    SVA_HIP(c, c->out_a.ensure(np * 8), "staging");
-    SVA_HIP(c, c->out_b.ensure(np), "staging");
-    SVA_HIP(c, c->out_c.ensure(np), "staging");
-    SVA_HIP(c, hipMemcpyAsync(c->in_a.ptr, disps, in_bytes, hipMemcpyHostToDevice, c->stream),
-            "upload");
-    SVA_HIP(c, hipMemcpyAsync(c->in_b.ptr, cost_min, in_bytes, hipMemcpyHostToDevice, c->stream),
-            "upload");
-    if (cost_second)
-        SVA_HIP(c, hipMemcpyAsync(c->in_c.ptr, cost_second, in_bytes, hipMemcpyHostToDevice,
-                                  c->stream),
-                "upload");
-    SVA_HIP(c, launch_fuse_depth_conf(*c, (const uint16_t*)c->in_a.ptr,
-                                      (const uint16_t*)c->in_b.ptr,
-                                      cost_second ? (const uint16_t*)c->in_c.ptr : nullptr, n_maps,
-                                      np, num, pixel_size, invalid, mode, (double*)c->out_a.ptr,
-                                      (uint8_t*)c->out_b.ptr, (uint8_t*)c->out_c.ptr),
-            "fuse launch");
-    SVA_HIP(c, hipMemcpyAsync(depth, c->out_a.ptr, np * 8, hipMemcpyDeviceToHost, c->stream),
-            "download");
-    if (n_valid)
-        SVA_HIP(c, hipMemcpyAsync(n_valid, c->out_b.ptr, np, hipMemcpyDeviceToHost, c->stream),
-                "download");
-    if (winner)
-        SVA_HIP(c, hipMemcpyAsync(winner, c->out_c.ptr, np, hipMemcpyDeviceToHost, c->stream),
-                "download");
-    SVA_HIP(c, hipStreamSynchronize(c->stream), "sync");
-    return SVA_OK;
+    return fuse_host(c, disps, cost_min, cost_second, n_maps, W, H, baselines, f, pixel_size,
+                     invalid, mode, depth, n_valid, winner);
 }
 
 // ------------------------------------------ refinement / 3-D --
+namespace {
+int check_shift(Ctx* c, const sva_camera* in_cam, const sva_camera* out_cam, const void* a,
+                const void* b, const void* out, int W, int H, size_t pitch) {
+    int s;
+    if ((s = check_planes(c, W, H, pitch)) || (s = check_camera(c, in_cam)) ||
+        (s = check_camera(c, out_cam)))
+        return s;
+    if (!a || !b || !out) return fail(c, SVA_ERR_INVALID_ARG, "null plane");
+    return SVA_OK;
+}
+
+int check_improve(Ctx* c, const uint8_t* disparity, const uint8_t* center,
+                  const uint8_t* const* images, const sva_camera* cam_pairs, int n_pairs, int W,
+                  int H, size_t pitch, int window_size, const uint8_t* out) {
+    int s;
+    if ((s = check_planes(c, W, H, pitch)) || (s = check_window(c, window_size))) return s;
+    if (n_pairs < 0 || (n_pairs > 0 && (!images || !cam_pairs)))
+        return fail(c, SVA_ERR_INVALID_ARG, "bad pair list");
+    if (!disparity || !center || !out) return fail(c, SVA_ERR_INVALID_ARG, "null plane");
+    for (int i = 0; i < n_pairs; i++)
+        if (!images[i]) return fail(c, SVA_ERR_INVALID_ARG, "null pair image");
+    return SVA_OK;
+}
+
+int run_shift2(Ctx* c, const sva_camera* in_cam, const sva_camera* out_cam, const double* depth,
+               int W, int H, double* shifted) {
+    SVA_HIP(c, c->keys.ensure((size_t)W * H * 4), "key workspace");
+    SVA_HIP(c, launch_shift_perspective2(*c, *in_cam, *out_cam, depth, W, H,
+                                         (unsigned*)c->keys.ptr, shifted), "shift2 launch");
+    return SVA_OK;
+}
+
+int check_points_to_depth(Ctx* c, const double* points, int64_t n_points, const sva_camera* cam,
+                          int W, int H, const double* depth) {
+    int s;
+    if ((s = check_planes(c, W, H, (size_t)W)) || (s = check_camera(c, cam))) return s;
+    if (n_points < 0 || n_points > 0xfffffffell || (n_points > 0 && !points) || !depth)
+        return fail(c, SVA_ERR_INVALID_ARG, "bad point list");
+    return SVA_OK;
+}
+
+int run_points_to_depth(Ctx* c, const double* points, int64_t n_points, const sva_camera* cam,
+                        int W, int H, double* depth) {
+    SVA_HIP(c, c->keys.ensure((size_t)W * H * 4), "key workspace");
+    SVA_HIP(c, launch_points_to_depth(*c, points, n_points, *cam, W, H, (unsigned*)c->keys.ptr,
+                                      depth), "points launch");
+    return SVA_OK;
+}
+
+int check_depth_to_points(Ctx* c, const double* depth, int W, int H, const sva_camera* cam,
+                          const double* points, const int64_t* n_points) {
+    int s;
+    if ((s = check_planes(c, W, H, (size_t)W)) || (s = check_camera(c, cam))) return s;
+    if (!depth || !points || !n_points) return fail(c, SVA_ERR_INVALID_ARG, "null argument");
+    return SVA_OK;
+}
+
+// The points of a device depth map, compacted into device `points`; *n (host)
+// is their number once this returns (it synchronises).
+int run_depth_to_points(Ctx* c, const double* depth, int W, int H, const sva_camera* cam,
+                        double* points, long long* n) {
+    SVA_HIP(c, c->counts.ensure(d2p_units(W, H) * 4), "count workspace");
+    SVA_HIP(c, c->total.ensure(sizeof(long long)), "count workspace");
+    SVA_HIP(c, launch_depth_to_points(*c, depth, W, H, *cam, (unsigned*)c->counts.ptr,
+                                      (long long*)c->total.ptr, points), "d2p launch");
+    SVA_HIP(c, hipMemcpyAsync(n, c->total.ptr, sizeof(*n), hipMemcpyDeviceToHost, c->stream),
+            "download");
+    SVA_HIP(c, hipStreamSynchronize(c->stream), "sync");
+    return SVA_OK;
+}
+}  // namespace
+
 int sva_shift_perspective_d(void* ctx, const sva_camera* in_cam, const sva_camera* out_cam,
                             const uint8_t* disparity, const uint8_t* image, int W, int H,
                             size_t pitch, uint8_t* shifted) {
     Ctx* c = as_ctx(ctx);
     SVA_CHECK_CTX(c);
-    int s;
-    if ((s = check_planes(c, W, H, pitch)) || (s = check_camera(c, in_cam)) ||
-        (s = check_camera(c, out_cam)))
-        return s;
-    if (!disparity || !image || !shifted) return fail(c, SVA_ERR_INVALID_ARG, "null plane");
+    if (int s = check_shift(c, in_cam, out_cam, disparity, image, shifted, W, H, pitch)) return s;
     SVA_HIP(c, launch_shift_perspective(*c, *in_cam, *out_cam, disparity, image, W, H, pitch,
                                         shifted), "shift launch");
     return SVA_OK;
@@ -1460,25 +1490,18 @@ int sva_shift_perspective(void* ctx, const sva_camera* in_cam, const sva_camera*
                           size_t pitch, uint8_t* shifted) {
     Ctx* c = as_ctx(ctx);
     SVA_CHECK_CTX(c);
-    int s;
-    if ((s = check_planes(c, W, H, pitch)) || (s = check_camera(c, in_cam)) ||
-        (s = check_camera(c, out_cam)))
-        return s;
-    if (!disparity || !image || !shifted) return fail(c, SVA_ERR_INVALID_ARG, "null plane");
+    if (int s = check_shift(c, in_cam, out_cam, disparity, image, shifted, W, H, pitch)) return s;
     const size_t bytes = (size_t)H * pitch;
-    SVA_HIP(c, c->in_a.ensure(bytes), "staging");
-    SVA_HIP(c, c->in_b.ensure(bytes), "staging");
-    SVA_HIP(c, c->out_a.ensure(bytes), "staging");
-    hipStream_t st = c->stream;
-    SVA_HIP(c, hipMemcpyAsync(c->in_a.ptr, disparity, bytes, hipMemcpyHostToDevice, st), "upload");
-    SVA_HIP(c, hipMemcpyAsync(c->in_b.ptr, image, bytes, hipMemcpyHostToDevice, st), "upload");
-    SVA_HIP(c, hipMemcpyAsync(c->out_a.ptr, shifted, bytes, hipMemcpyHostToDevice, st), "upload");
-    SVA_HIP(c, launch_shift_perspective(*c, *in_cam, *out_cam, (uint8_t*)c->in_a.ptr,
-                                        (uint8_t*)c->in_b.ptr, W, H, pitch,
-                                        (uint8_t*)c->out_a.ptr), "shift launch");
-    SVA_HIP(c, hipMemcpyAsync(shifted, c->out_a.ptr, bytes, hipMemcpyDeviceToHost, st), "download");
-    SVA_HIP(c, hipStreamSynchronize(st), "sync");
-    return SVA_OK;
+    Staging g{c};
+    const uint8_t* dd = g.up<uint8_t>(c->in_a, disparity, bytes);
+    const uint8_t* di = g.up<uint8_t>(c->in_b, image, bytes);
+    // pixels no source pixel lands on keep the caller's values
+    uint8_t* ds = g.up<uint8_t>(c->out_a, shifted, bytes);
+    if (g.st) return g.st;
+    SVA_HIP(c, launch_shift_perspective(*c, *in_cam, *out_cam, dd, di, W, H, pitch, ds),
+            "shift launch");
+    g.down(shifted, ds, bytes);
+    return g.sync();
 }
 
 int sva_improve_with_disparity_d(void* ctx, const uint8_t* disparity, const uint8_t* center,
@@ -1487,13 +1510,9 @@ int sva_improve_with_disparity_d(void* ctx, const uint8_t* disparity, const uint
                                  int window_size, int strict, uint8_t* out) {
     Ctx* c = as_ctx(ctx);
     SVA_CHECK_CTX(c);
-    int s;
-    if ((s = check_planes(c, W, H, pitch)) || (s = check_window(c, window_size))) return s;
-    if (n_pairs < 0 || (n_pairs > 0 && (!images || !cam_pairs)))
-        return fail(c, SVA_ERR_INVALID_ARG, "bad pair list");
-    if (!disparity || !center || !out) return fail(c, SVA_ERR_INVALID_ARG, "null plane");
-    for (int i = 0; i < n_pairs; i++)
-        if (!images[i]) return fail(c, SVA_ERR_INVALID_ARG, "null pair image");
+    if (int s = check_improve(c, disparity, center, images, cam_pairs, n_pairs, W, H, pitch,
+                              window_size, out))
+        return s;
     return run_improve(c, disparity, center, images, cam_pairs, n_pairs, W, H, pitch, mask,
                        window_size, strict, out, nullptr);
 }
@@ -1505,54 +1524,39 @@ int sva_improve_with_disparity(void* ctx, const uint8_t* disparity, const uint8_
     Ctx* c = as_ctx(ctx);
     SVA_CHECK_CTX(c);
     int s;
-    if ((s = check_planes(c, W, H, pitch)) || (s = check_window(c, window_size))) return s;
-    if (n_pairs < 0 || (n_pairs > 0 && (!images || !cam_pairs)))
-        return fail(c, SVA_ERR_INVALID_ARG, "bad pair list");
-    if (!disparity || !center || !out) return fail(c, SVA_ERR_INVALID_ARG, "null plane");
-    for (int i = 0; i < n_pairs; i++)
-        if (!images[i]) return fail(c, SVA_ERR_INVALID_ARG, "null pair image");
+    if ((s = check_improve(c, disparity, center, images, cam_pairs, n_pairs, W, H, pitch,
+                           window_size, out)))
+        return s;
     const size_t bytes = (size_t)H * pitch;
-    SVA_HIP(c, c->in_a.ensure(bytes), "staging");
-    SVA_HIP(c, c->in_b.ensure(bytes), "staging");
-    SVA_HIP(c, c->in_c.ensure(bytes), "staging");
-    SVA_HIP(c, c->out_a.ensure(bytes), "staging");
-    if (mask) SVA_HIP(c, c->in_mask.ensure(bytes), "staging");
-    hipStream_t st = c->stream;
-    SVA_HIP(c, hipMemcpyAsync(c->in_a.ptr, disparity, bytes, hipMemcpyHostToDevice, st), "upload");
-    SVA_HIP(c, hipMemcpyAsync(c->in_b.ptr, center, bytes, hipMemcpyHostToDevice, st), "upload");
-    if (mask) SVA_HIP(c, hipMemcpyAsync(c->in_mask.ptr, mask, bytes, hipMemcpyHostToDevice, st), "upload");
+    Staging g{c};
+    const uint8_t* dd = g.up<uint8_t>(c->in_a, disparity, bytes);
+    const uint8_t* dc = g.up<uint8_t>(c->in_b, center, bytes);
+    const uint8_t* dmask = mask ? g.up<uint8_t>(c->in_mask, mask, bytes) : nullptr;
     // pixels the refinement does not reach keep the caller's values
-    SVA_HIP(c, hipMemcpyAsync(c->out_a.ptr, out, bytes, hipMemcpyHostToDevice, st), "upload");
-    uint8_t* dimg = (uint8_t*)c->in_c.ptr;
+    uint8_t* dout = g.up<uint8_t>(c->out_a, out, bytes);
+    uint8_t* dimg = g.out<uint8_t>(c->in_c, bytes);
+    if (g.st) return g.st;
     auto fetch = [&](int i, const uint8_t** img) -> int {
         // one staging buffer reused per pair: stream order keeps the upload
         // of pair i behind pair i-1's kernels
-        SVA_HIP(c, hipMemcpyAsync(dimg, images[i], bytes, hipMemcpyHostToDevice, st), "upload");
+        SVA_HIP(c, hipMemcpyAsync(dimg, images[i], bytes, hipMemcpyHostToDevice, c->stream),
+                "upload");
         *img = dimg;
         return SVA_OK;
     };
-    if ((s = run_improve(c, (uint8_t*)c->in_a.ptr, (uint8_t*)c->in_b.ptr, nullptr, cam_pairs,
-                         n_pairs, W, H, pitch, mask ? (uint8_t*)c->in_mask.ptr : nullptr,
-                         window_size, strict, (uint8_t*)c->out_a.ptr, fetch)))
+    if ((s = run_improve(c, dd, dc, nullptr, cam_pairs, n_pairs, W, H, pitch, dmask, window_size,
+                         strict, dout, fetch)))
         return s;
-    SVA_HIP(c, hipMemcpyAsync(out, c->out_a.ptr, bytes, hipMemcpyDeviceToHost, st), "download");
-    SVA_HIP(c, hipStreamSynchronize(st), "sync");
-    return SVA_OK;
+    g.down(out, dout, bytes);
+    return g.sync();
 }
 
 int sva_shift_perspective2_d(void* ctx, const sva_camera* in_cam, const sva_camera* out_cam,
                              const double* depth, int W, int H, double* shifted) {
     Ctx* c = as_ctx(ctx);
     SVA_CHECK_CTX(c);
-    int s;
-    if ((s = check_planes(c, W, H, (size_t)W)) || (s = check_camera(c, in_cam)) ||
-        (s = check_camera(c, out_cam)))
-        return s;
-    if (!depth || !shifted) return fail(c, SVA_ERR_INVALID_ARG, "null plane");
-    SVA_HIP(c, c->keys.ensure((size_t)W * H * 4), "key workspace");
-    SVA_HIP(c, launch_shift_perspective2(*c, *in_cam, *out_cam, depth, W, H,
-                                         (unsigned*)c->keys.ptr, shifted), "shift2 launch");
-    return SVA_OK;
+    if (int s = check_shift(c, in_cam, out_cam, depth, depth, shifted, W, H, (size_t)W)) return s;
+    return run_shift2(c, in_cam, out_cam, depth, W, H, shifted);
 }
 
 int sva_shift_perspective2(void* ctx, const sva_camera* in_cam, const sva_camera* out_cam,
@@ -1560,37 +1564,23 @@ int sva_shift_perspective2(void* ctx, const sva_camera* in_cam, const sva_camera
     Ctx* c = as_ctx(ctx);
     SVA_CHECK_CTX(c);
     int s;
-    if ((s = check_planes(c, W, H, (size_t)W)) || (s = check_camera(c, in_cam)) ||
-        (s = check_camera(c, out_cam)))
-        return s;
-    if (!depth || !shifted) return fail(c, SVA_ERR_INVALID_ARG, "null plane");
+    if ((s = check_shift(c, in_cam, out_cam, depth, depth, shifted, W, H, (size_t)W))) return s;
     const size_t bytes = (size_t)W * H * 8;
-    SVA_HIP(c, c->in_a.ensure(bytes), "staging");
-    SVA_HIP(c, c->out_a.ensure(bytes), "staging");
-    SVA_HIP(c, c->keys.ensure((size_t)W * H * 4), "key workspace");
-    hipStream_t st = c->stream;
-    SVA_HIP(c, hipMemcpyAsync(c->in_a.ptr, depth, bytes, hipMemcpyHostToDevice, st), "upload");
-    SVA_HIP(c, hipMemcpyAsync(c->out_a.ptr, shifted, bytes, hipMemcpyHostToDevice, st), "upload");
-    SVA_HIP(c, launch_shift_perspective2(*c, *in_cam, *out_cam, (double*)c->in_a.ptr, W, H,
-                                         (unsigned*)c->keys.ptr, (double*)c->out_a.ptr),
-            "shift2 launch");
-    SVA_HIP(c, hipMemcpyAsync(shifted, c->out_a.ptr, bytes, hipMemcpyDeviceToHost, st), "download");
-    SVA_HIP(c, hipStreamSynchronize(st), "sync");
-    return SVA_OK;
+    Staging g{c};
+    const double* dd = g.up<double>(c->in_a, depth, bytes);
+    double* ds = g.up<double>(c->out_a, shifted, bytes);   // (untouched pixels: the caller's)
+    if (g.st) return g.st;
+    if ((s = run_shift2(c, in_cam, out_cam, dd, W, H, ds))) return s;
+    g.down(shifted, ds, bytes);
+    return g.sync();
 }
 
 int sva_points_to_depth_d(void* ctx, const double* points, int64_t n_points,
                           const sva_camera* cam, int W, int H, double* depth) {
     Ctx* c = as_ctx(ctx);
     SVA_CHECK_CTX(c);
-    int s;
-    if ((s = check_planes(c, W, H, (size_t)W)) || (s = check_camera(c, cam))) return s;
-    if (n_points < 0 || n_points > 0xfffffffell || (n_points > 0 && !points) || !depth)
-        return fail(c, SVA_ERR_INVALID_ARG, "bad point list");
-    SVA_HIP(c, c->keys.ensure((size_t)W * H * 4), "key workspace");
-    SVA_HIP(c, launch_points_to_depth(*c, points, n_points, *cam, W, H, (unsigned*)c->keys.ptr,
-                                      depth), "points launch");
-    return SVA_OK;
+    if (int s = check_points_to_depth(c, points, n_points, cam, W, H, depth)) return s;
+    return run_points_to_depth(c, points, n_points, cam, W, H, depth);
 }
 
 int sva_points_to_depth(void* ctx, const double* points, int64_t n_points, const sva_camera* cam,
@@ -1598,23 +1588,15 @@ int sva_points_to_depth(void* ctx, const double* points, int64_t n_points, const
     Ctx* c = as_ctx(ctx);
     SVA_CHECK_CTX(c);
     int s;
-    if ((s = check_planes(c, W, H, (size_t)W)) || (s = check_camera(c, cam))) return s;
-    if (n_points < 0 || n_points > 0xfffffffell || (n_points > 0 && !points) || !depth)
-        return fail(c, SVA_ERR_INVALID_ARG, "bad point list");
+    if ((s = check_points_to_depth(c, points, n_points, cam, W, H, depth))) return s;
     const size_t pbytes = (size_t)n_points * 24, dbytes = (size_t)W * H * 8;
-    SVA_HIP(c, c->in_a.ensure(pbytes ? pbytes : 8), "staging");
-    SVA_HIP(c, c->out_a.ensure(dbytes), "staging");
-    SVA_HIP(c, c->keys.ensure((size_t)W * H * 4), "key workspace");
-    hipStream_t st = c->stream;
-    if (pbytes)
-        SVA_HIP(c, hipMemcpyAsync(c->in_a.ptr, points, pbytes, hipMemcpyHostToDevice, st), "upload");
-    SVA_HIP(c, hipMemcpyAsync(c->out_a.ptr, depth, dbytes, hipMemcpyHostToDevice, st), "upload");
-    SVA_HIP(c, launch_points_to_depth(*c, (double*)c->in_a.ptr, n_points, *cam, W, H,
-                                      (unsigned*)c->keys.ptr, (double*)c->out_a.ptr),
-            "points launch");
-    SVA_HIP(c, hipMemcpyAsync(depth, c->out_a.ptr, dbytes, hipMemcpyDeviceToHost, st), "download");
-    SVA_HIP(c, hipStreamSynchronize(st), "sync");
-    return SVA_OK;
+    Staging g{c};
+    const double* dp = pbytes ? g.up<double>(c->in_a, points, pbytes) : g.out<double>(c->in_a, 8);
+    double* dz = g.up<double>(c->out_a, depth, dbytes);     // (untouched pixels: the caller's)
+    if (g.st) return g.st;
+    if ((s = run_points_to_depth(c, dp, n_points, cam, W, H, dz))) return s;
+    g.down(depth, dz, dbytes);
+    return g.sync();
 }
 
 int sva_depth_to_points_d(void* ctx, const double* depth, int W, int H, const sva_camera* cam,
@@ -1622,16 +1604,9 @@ int sva_depth_to_points_d(void* ctx, const double* depth, int W, int H, const sv
     Ctx* c = as_ctx(ctx);
     SVA_CHECK_CTX(c);
     int s;
-    if ((s = check_planes(c, W, H, (size_t)W)) || (s = check_camera(c, cam))) return s;
-    if (!depth || !points || !n_points) return fail(c, SVA_ERR_INVALID_ARG, "null argument");
-    SVA_HIP(c, c->counts.ensure(d2p_units(W, H) * 4), "count workspace");
-    SVA_HIP(c, c->total.ensure(sizeof(long long)), "count workspace");
-    SVA_HIP(c, launch_depth_to_points(*c, depth, W, H, *cam, (unsigned*)c->counts.ptr,
-                                      (long long*)c->total.ptr, points), "d2p launch");
+    if ((s = check_depth_to_points(c, depth, W, H, cam, points, n_points))) return s;
     long long n = 0;
-    SVA_HIP(c, hipMemcpyAsync(&n, c->total.ptr, sizeof(n), hipMemcpyDeviceToHost, c->stream),
-            "download");
-    SVA_HIP(c, hipStreamSynchronize(c->stream), "sync");
+    if ((s = run_depth_to_points(c, depth, W, H, cam, points, &n))) return s;
     *n_points = n;
     return SVA_OK;
 }
@@ -1641,25 +1616,17 @@ int sva_depth_to_points(void* ctx, const double* depth, int W, int H, const sva_
     Ctx* c = as_ctx(ctx);
     SVA_CHECK_CTX(c);
     int s;
-    if ((s = check_planes(c, W, H, (size_t)W)) || (s = check_camera(c, cam))) return s;
-    if (!depth || !points || !n_points) return fail(c, SVA_ERR_INVALID_ARG, "null argument");
+    if ((s = check_depth_to_points(c, depth, W, H, cam, points, n_points))) return s;
     const size_t np = (size_t)W * H;
-    SVA_HIP(c, c->in_a.ensure(np * 8), "staging");
-    SVA_HIP(c, c->out_a.ensure(np * 24), "staging");
-    SVA_HIP(c, c->counts.ensure(d2p_units(W, H) * 4), "count workspace");
-    SVA_HIP(c, c->total.ensure(sizeof(long long)), "count workspace");
-    hipStream_t st = c->stream;
-    SVA_HIP(c, hipMemcpyAsync(c->in_a.ptr, depth, np * 8, hipMemcpyHostToDevice, st), "upload");
-    SVA_HIP(c, launch_depth_to_points(*c, (double*)c->in_a.ptr, W, H, *cam,
-                                      (unsigned*)c->counts.ptr, (long long*)c->total.ptr,
-                                      (double*)c->out_a.ptr), "d2p launch");
+    Staging g{c};
+    const double* dd = g.up<double>(c->in_a, depth, np * 8);
+    double* dp = g.out<double>(c->out_a, np * 24);
+    if (g.st) return g.st;
     long long n = 0;
-    SVA_HIP(c, hipMemcpyAsync(&n, c->total.ptr, sizeof(n), hipMemcpyDeviceToHost, st), "download");
-    SVA_HIP(c, hipStreamSynchronize(st), "sync");
-    if (n > 0)
-        SVA_HIP(c, hipMemcpyAsync(points, c->out_a.ptr, (size_t)n * 24, hipMemcpyDeviceToHost, st),
-                "download");
-    SVA_HIP(c, hipStreamSynchronize(st), "sync");
+    if ((s = run_depth_to_points(c, dd, W, H, cam, dp, &n))) return s;
+    // (n is known only after that synchronise: the n points, then a second one)
+    if (n > 0) g.down(points, dp, (size_t)n * 24);
+    if ((s = g.sync())) return s;
     *n_points = n;
     return SVA_OK;
 }
@@ -1671,15 +1638,26 @@ int sva_resize_half_size(int W, int H, int* out_w, int* out_h) {
     return SVA_OK;
 }
 
-int sva_resize_half_d(void* ctx, const uint8_t* src, int W, int H, size_t pitch, uint8_t* dst,
-                      size_t dst_pitch) {
-    Ctx* c = as_ctx(ctx);
-    SVA_CHECK_CTX(c);
+namespace {
+// *dst_rows: the output's rows, 0 when it has no pixels.
+int check_resize_half(Ctx* c, const uint8_t* src, int W, int H, size_t pitch, const uint8_t* dst,
+                      size_t dst_pitch, size_t* dst_rows) {
     int s, dw, dh;
     if ((s = check_planes(c, W, H, pitch))) return s;
     resize_half_size(W, H, &dw, &dh);
     if (!src || (!dst && dw > 0 && dh > 0) || dst_pitch < (size_t)dw)
         return fail(c, SVA_ERR_INVALID_ARG, "bad resize argument");
+    *dst_rows = dw > 0 ? (size_t)dh : 0;
+    return SVA_OK;
+}
+}  // namespace
+
+int sva_resize_half_d(void* ctx, const uint8_t* src, int W, int H, size_t pitch, uint8_t* dst,
+                      size_t dst_pitch) {
+    Ctx* c = as_ctx(ctx);
+    SVA_CHECK_CTX(c);
+    size_t rows;
+    if (int s = check_resize_half(c, src, W, H, pitch, dst, dst_pitch, &rows)) return s;
     SVA_HIP(c, launch_resize_half(*c, src, W, H, pitch, dst, dst_pitch), "resize launch");
     return SVA_OK;
 }
@@ -1688,22 +1666,17 @@ int sva_resize_half(void* ctx, const uint8_t* src, int W, int H, size_t pitch, u
                     size_t dst_pitch) {
     Ctx* c = as_ctx(ctx);
     SVA_CHECK_CTX(c);
-    int s, dw, dh;
-    if ((s = check_planes(c, W, H, pitch))) return s;
-    resize_half_size(W, H, &dw, &dh);
-    if (!src || (!dst && dw > 0 && dh > 0) || dst_pitch < (size_t)dw)
-        return fail(c, SVA_ERR_INVALID_ARG, "bad resize argument");
-    if (dw == 0 || dh == 0) return SVA_OK;
-    const size_t sb = (size_t)H * pitch, db = (size_t)dh * dst_pitch;
-    SVA_HIP(c, c->in_a.ensure(sb), "staging");
-    SVA_HIP(c, c->out_a.ensure(db), "staging");
-    hipStream_t st = c->stream;
-    SVA_HIP(c, hipMemcpyAsync(c->in_a.ptr, src, sb, hipMemcpyHostToDevice, st), "upload");
-    SVA_HIP(c, launch_resize_half(*c, (uint8_t*)c->in_a.ptr, W, H, pitch, (uint8_t*)c->out_a.ptr,
-                                  dst_pitch), "resize launch");
-    SVA_HIP(c, hipMemcpyAsync(dst, c->out_a.ptr, db, hipMemcpyDeviceToHost, st), "download");
-    SVA_HIP(c, hipStreamSynchronize(st), "sync");
-    return SVA_OK;
+    size_t rows;
+    if (int s = check_resize_half(c, src, W, H, pitch, dst, dst_pitch, &rows)) return s;
+    if (rows == 0) return SVA_OK;    // an empty output (the host form only)
+    const size_t db = rows * dst_pitch;
+    Staging g{c};
+    const uint8_t* ds = g.up<uint8_t>(c->in_a, src, (size_t)H * pitch);
+    uint8_t* dd = g.out<uint8_t>(c->out_a, db);
+    if (g.st) return g.st;
+    SVA_HIP(c, launch_resize_half(*c, ds, W, H, pitch, dd, dst_pitch), "resize launch");
+    g.down(dst, dd, db);
+    return g.sync();
 }
 
 // ----------------------------------------------------------- evaluation --
@@ -1714,98 +1687,88 @@ int check_dims(Ctx* c, int w, int h) {
     return SVA_OK;
 }
 
-// Host-buffer form of the resize / error entry points: upload, run, download.
-int host_resize(Ctx* c, const double* src, int sw, int sh, const double* ref, int dw, int dh,
-                double scale, double* dst) {
-    const size_t sb = (size_t)sw * sh * 8, db = (size_t)dw * dh * 8;
-    SVA_HIP(c, c->in_a.ensure(sb), "staging");
-    SVA_HIP(c, c->out_a.ensure(db), "staging");
-    if (ref) SVA_HIP(c, c->in_b.ensure(db), "staging");
-    hipStream_t st = c->stream;
-    SVA_HIP(c, hipMemcpyAsync(c->in_a.ptr, src, sb, hipMemcpyHostToDevice, st), "upload");
-    if (ref) SVA_HIP(c, hipMemcpyAsync(c->in_b.ptr, ref, db, hipMemcpyHostToDevice, st), "upload");
-    SVA_HIP(c, launch_resize_linear(*c, (double*)c->in_a.ptr, sw, sh, (double*)c->out_a.ptr, dw, dh,
-                                    ref ? (double*)c->in_b.ptr : nullptr, scale), "resize launch");
-    SVA_HIP(c, hipMemcpyAsync(dst, c->out_a.ptr, db, hipMemcpyDeviceToHost, st), "download");
-    SVA_HIP(c, hipStreamSynchronize(st), "sync");
+// sva_resize_linear_f64[_d] (ref unused) and sva_ref_error[_d] (need_ref):
+// dst = resize(src, dw x dh), with ref (dst - ref) * scale.  host: the
+// buffers are the caller's host memory.
+int resize_entry(void* ctx, bool host, const double* src, int sw, int sh, const double* ref,
+                 bool need_ref, int dw, int dh, double scale, double* dst) {
+    Ctx* c = as_ctx(ctx);
+    SVA_CHECK_CTX(c);
+    int s;
+    if ((s = check_dims(c, sw, sh)) || (s = check_dims(c, dw, dh))) return s;
+    if (!src || !dst || (need_ref && !ref)) return fail(c, SVA_ERR_INVALID_ARG, "null matrix");
+    Staging g{c};
+    double* out = dst;
+    if (host) {
+        const size_t db = (size_t)dw * dh * 8;
+        src = g.up<double>(c->in_a, src, (size_t)sw * sh * 8);
+        out = g.out<double>(c->out_a, db);
+        if (ref) ref = g.up<double>(c->in_b, ref, db);
+        if (g.st) return g.st;
+    }
+    SVA_HIP(c, launch_resize_linear(*c, src, sw, sh, out, dw, dh, ref, scale), "resize launch");
+    if (!host) return SVA_OK;
+    g.down(dst, out, (size_t)dw * dh * 8);
+    return g.sync();
+}
+
+int check_mean(Ctx* c, const double* image, int w, int h, const double* mean) {
+    if (int s = check_dims(c, w, h)) return s;
+    if (!image || !mean) return fail(c, SVA_ERR_INVALID_ARG, "null argument");
+    return SVA_OK;
+}
+
+// cv::mean(image, mask)[0] of device buffers into host *mean (synchronises).
+int run_mean(Ctx* c, const double* image, const uint8_t* mask, size_t n, double* mean) {
+    SVA_HIP(c, c->scratch_u16.ensure(masked_mean_workspace()), "reduction workspace");
+    double* dmean = (double*)((char*)c->scratch_u16.ptr + masked_mean_workspace() - sizeof(double));
+    SVA_HIP(c, launch_masked_mean(*c, image, mask, n, c->scratch_u16.ptr, dmean), "mean launch");
+    SVA_HIP(c, hipMemcpyAsync(mean, dmean, sizeof(double), hipMemcpyDeviceToHost, c->stream),
+            "download");
+    SVA_HIP(c, hipStreamSynchronize(c->stream), "sync");
     return SVA_OK;
 }
 }  // namespace
 
 int sva_resize_linear_f64_d(void* ctx, const double* src, int sw, int sh, double* dst, int dw,
                             int dh) {
-    Ctx* c = as_ctx(ctx);
-    SVA_CHECK_CTX(c);
-    int s;
-    if ((s = check_dims(c, sw, sh)) || (s = check_dims(c, dw, dh))) return s;
-    if (!src || !dst) return fail(c, SVA_ERR_INVALID_ARG, "null matrix");
-    SVA_HIP(c, launch_resize_linear(*c, src, sw, sh, dst, dw, dh, nullptr, 0.0), "resize launch");
-    return SVA_OK;
+    return resize_entry(ctx, false, src, sw, sh, nullptr, false, dw, dh, 0.0, dst);
 }
 
 int sva_resize_linear_f64(void* ctx, const double* src, int sw, int sh, double* dst, int dw,
                           int dh) {
-    Ctx* c = as_ctx(ctx);
-    SVA_CHECK_CTX(c);
-    int s;
-    if ((s = check_dims(c, sw, sh)) || (s = check_dims(c, dw, dh))) return s;
-    if (!src || !dst) return fail(c, SVA_ERR_INVALID_ARG, "null matrix");
-    return host_resize(c, src, sw, sh, nullptr, dw, dh, 0.0, dst);
+    return resize_entry(ctx, true, src, sw, sh, nullptr, false, dw, dh, 0.0, dst);
 }
 
 int sva_ref_error_d(void* ctx, const double* depth, int w, int h, const double* ref, int rw,
                     int rh, double scale, double* error) {
-    Ctx* c = as_ctx(ctx);
-    SVA_CHECK_CTX(c);
-    int s;
-    if ((s = check_dims(c, w, h)) || (s = check_dims(c, rw, rh))) return s;
-    if (!depth || !ref || !error) return fail(c, SVA_ERR_INVALID_ARG, "null matrix");
-    SVA_HIP(c, launch_resize_linear(*c, depth, w, h, error, rw, rh, ref, scale), "resize launch");
-    return SVA_OK;
+    return resize_entry(ctx, false, depth, w, h, ref, true, rw, rh, scale, error);
 }
 
 int sva_ref_error(void* ctx, const double* depth, int w, int h, const double* ref, int rw, int rh,
                   double scale, double* error) {
-    Ctx* c = as_ctx(ctx);
-    SVA_CHECK_CTX(c);
-    int s;
-    if ((s = check_dims(c, w, h)) || (s = check_dims(c, rw, rh))) return s;
-    if (!depth || !ref || !error) return fail(c, SVA_ERR_INVALID_ARG, "null matrix");
-    return host_resize(c, depth, w, h, ref, rw, rh, scale, error);
+    return resize_entry(ctx, true, depth, w, h, ref, true, rw, rh, scale, error);
 }
 
 int sva_masked_mean_d(void* ctx, const double* image, const uint8_t* mask, int w, int h,
                       double* mean) {
     Ctx* c = as_ctx(ctx);
     SVA_CHECK_CTX(c);
-    int s;
-    if ((s = check_dims(c, w, h))) return s;
-    if (!image || !mean) return fail(c, SVA_ERR_INVALID_ARG, "null argument");
-    SVA_HIP(c, c->scratch_u16.ensure(masked_mean_workspace()), "reduction workspace");
-    double* dmean = (double*)((char*)c->scratch_u16.ptr + masked_mean_workspace() - sizeof(double));
-    SVA_HIP(c, launch_masked_mean(*c, image, mask, (size_t)w * h, c->scratch_u16.ptr, dmean),
-            "mean launch");
-    SVA_HIP(c, hipMemcpyAsync(mean, dmean, sizeof(double), hipMemcpyDeviceToHost, c->stream),
-            "download");
-    SVA_HIP(c, hipStreamSynchronize(c->stream), "sync");
-    return SVA_OK;
+    if (int s = check_mean(c, image, w, h, mean)) return s;
+    return run_mean(c, image, mask, (size_t)w * h, mean);
 }
 
 int sva_masked_mean(void* ctx, const double* image, const uint8_t* mask, int w, int h,
                     double* mean) {
     Ctx* c = as_ctx(ctx);
     SVA_CHECK_CTX(c);
-    int s;
-    if ((s = check_dims(c, w, h))) return s;
-    if (!image || !mean) return fail(c, SVA_ERR_INVALID_ARG, "null argument");
+    if (int s = check_mean(c, image, w, h, mean)) return s;
     const size_t n = (size_t)w * h;
-    SVA_HIP(c, c->in_a.ensure(n * 8), "staging");
-    SVA_HIP(c, c->in_mask.ensure(mask ? n : 1), "staging");
-    hipStream_t st = c->stream;
-    SVA_HIP(c, hipMemcpyAsync(c->in_a.ptr, image, n * 8, hipMemcpyHostToDevice, st), "upload");
-    if (mask) SVA_HIP(c, hipMemcpyAsync(c->in_mask.ptr, mask, n, hipMemcpyHostToDevice, st), "upload");
-    return sva_masked_mean_d(ctx, (double*)c->in_a.ptr, mask ? (uint8_t*)c->in_mask.ptr : nullptr, w,
-                             h, mean);
+    Staging g{c};
+    const double* di = g.up<double>(c->in_a, image, n * 8);
+    const uint8_t* dm = mask ? g.up<uint8_t>(c->in_mask, mask, n) : g.out<uint8_t>(c->in_mask, 1);
+    if (g.st) return g.st;
+    return run_mean(c, di, mask ? dm : nullptr, n, mean);
 }
 
 }  // extern "C"

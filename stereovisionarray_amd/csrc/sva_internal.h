@@ -17,12 +17,6 @@
 
 namespace sva {
 
-// Host-side status carrier: every launcher returns hipError_t, the API maps it.
-struct Status {
-    int code = SVA_OK;
-    std::string msg;
-};
-
 // Per-kernel hipEvent timing on the context stream.  Events are only recorded
 // while timing is enabled; resolution happens lazily in kernel_time().
 struct KernelTimer {
@@ -277,7 +271,6 @@ hipError_t launch_ref_match(Ctx& c, const uint8_t* ref, const uint8_t* other, in
                             size_t pitch, const uint8_t* mask, const int32_t* ends,
                             const uint8_t* valid_in, int k, uint8_t* disp_u8,
                             uint16_t* disp_u16, uint8_t* valid_out);
-// depth.hip
 // refine.hip
 hipError_t launch_shift_perspective(Ctx& c, const sva_camera& in, const sva_camera& out,
                                     const uint8_t* disp, const uint8_t* img, int W, int H,

@@ -94,18 +94,35 @@ def test_vertical_shift_exact(ctx, sva):
     assert (disp[d0 + 40: H - 40, 8:-8] == d0).all()
 
 
-@pytest.mark.parametrize("sx,sy", [(0, -1), (-1, -1), (1, 1), (-2, 1)])
+# (1, 3) and (4, 1) are steps no census+cost kernel takes: census_pair + cost2,
+# whose right-referenced pass reuses the two census maps with roles swapped
+SPLIT_STEPS = [(1, 3), (4, 1)]
+
+
+@pytest.mark.parametrize("sx,sy", [(0, -1), (-1, -1), (1, 1), (-2, 1)] + SPLIT_STEPS)
 def test_lr_check_2d(ctx, sva, oracle, sx, sy):
     W, H, D = 110, 180, 64
     L, R, _ = synth.stereo_pair2(H, W, D, 0, sx, sy, seed=5, stripes=6, step=9)
     p = sva.default_params(D=D, dir=sx, dir_y=sy, lr_check=1, lr_max_diff=1, subpixel=1)
+    split = (sx, sy) in SPLIT_STEPS
+    if split:
+        ctx.reset_timing()
+        ctx.set_timing(sva.SVA_TIMING_ALL)
     disp, sub = ctx.disparity_sgm(L, R, p)
+    if split:
+        ctx.set_timing(sva.SVA_TIMING_OFF)
+        counts = {k: ctx.kernel_time(k)[1] for k in ("census", "cost", "sgm_paths", "wta_hv",
+                                                      "lr_check")}
+        ctx.reset_timing()
+        assert counts == {"census": 1, "cost": 2, "sgm_paths": 2, "wta_hv": 2, "lr_check": 1}
     dl, osub = oracle.sgm2(L, R, D, 0, sx, sy, subpixel=True)
     dr, _ = oracle.sgm2(R, L, D, 0, -sx, -sy, subpixel=False)
     exp = oracle.lr_check2(dl, dr, sx, sy, 1, 0xFFFF)
     assert np.array_equal(disp, exp)
     assert (disp == 0xFFFF).any() and (disp != 0xFFFF).any()
     assert_sub_close(sub, oracle.lr_sub(exp, osub, 0xFFFF))
+    if split:
+        assert np.array_equal(ctx.disparity_sgm_conf(L, R, p, uniqueness=0)[0], disp)
 
 
 def _fuse_inputs(n, H, W, seed):

@@ -27,11 +27,11 @@ SUB_TOL = 1e-5          # the project's sub-pixel tolerance against the oracle (
 STEPS = [(-1, 0), (1, 0), (0, -1), (0, 1), (-1, -1), (1, 1), (-2, -1), (1, -1), (-1, 1)]
 
 
-def frames(H, W, D, n, seed):
+def frames(H, W, D, n, seed, steps=STEPS):
     """The frames of test_batch_gpu.py: every frame its own step."""
     out = []
     for i in range(n):
-        sx, sy = STEPS[i % len(STEPS)]
+        sx, sy = steps[i % len(steps)]
         if sy == 0:
             L, R, _ = synth.stereo_pair(H, W, D, 0, sx, seed=seed + i, stripes=4, step=5)
         else:
@@ -120,6 +120,14 @@ def test_equals_single_frame_conf_route(ctx, sva, torch_dev, D, H, W, u):
     b = Batch(sva, torch_dev, frames(H, W, D, 5, seed=H * W + D), D)
     b.run(ctx, u)
     check_equals_single(ctx, torch_dev, b, u, b.fetch(ctx))
+
+
+def test_split_route_frames_share_a_census_slot(ctx, sva, torch_dev):
+    """test_batch_gpu.py's 7-frame mix of split-route and fused steps."""
+    steps = [(1, 3), (-1, 0), (4, 1), (-1, 2), (1, 3), (0, 1), (4, 1)]
+    b = Batch(sva, torch_dev, frames(40, 77, 64, 7, seed=40 * 77 + 64, steps=steps), 64)
+    b.run(ctx, 25)
+    check_equals_single(ctx, torch_dev, b, 25, b.fetch(ctx))
 
 
 @functools.lru_cache(maxsize=None)

@@ -18,10 +18,10 @@ pytestmark = pytest.mark.gpu
 STEPS = [(-1, 0), (1, 0), (0, -1), (0, 1), (-1, -1), (1, 1), (-2, -1), (1, -1), (-1, 1)]
 
 
-def frames(H, W, D, n, seed):
+def frames(H, W, D, n, seed, steps=STEPS):
     out = []
     for i in range(n):
-        sx, sy = STEPS[i % len(STEPS)]
+        sx, sy = steps[i % len(steps)]
         if sy == 0:
             L, R, _ = synth.stereo_pair(H, W, D, 0, sx, seed=seed + i, stripes=4, step=5)
         else:
@@ -63,6 +63,28 @@ def test_batch_equals_single_frames(ctx, sva, torch_dev, D, H, W):
     for i in range(len(fr)):
         assert np.array_equal(maps[i], ref_m[i]), f"frame {i} step {fr[i][2:]}"
         assert np.array_equal(sub[i].view(np.uint32), ref_s[i].view(np.uint32)), f"sub {i}"
+
+
+# Steps no census+cost kernel takes -- (1, 3), (4, 1), (-1, 2) -- among fused
+# ones: census_pair + cost2 through the side streams' census scratch.
+SPLIT_MIX = [(1, 3), (-1, 0), (4, 1), (-1, 2), (1, 3), (0, 1), (4, 1)]
+
+
+def test_batch_split_route_shares_a_census_slot(ctx, sva, oracle, torch_dev):
+    """7 frames over 3 side streams and sub-batches of 4: stream 0 carries
+    frames 0, 3 and 6, three split-route frames in a row through one
+    census_side slot, across two sub-batches."""
+    D, H, W = 64, 40, 77
+    fr = frames(H, W, D, 7, seed=H * W + D, steps=SPLIT_MIX)
+    maps, sub, ref_m, ref_s = run_batch(ctx, sva, torch_dev, fr, D)
+    for i in range(len(fr)):
+        assert np.array_equal(maps[i], ref_m[i]), f"frame {i} step {fr[i][2:]}"
+        assert np.array_equal(sub[i].view(np.uint32), ref_s[i].view(np.uint32)), f"sub {i}"
+    for i in (0, 2, 3):
+        L, R, sx, sy = fr[i]
+        od, osub = oracle.sgm2(L, R, D, 0, sx, sy, subpixel=True)
+        assert np.array_equal(maps[i].view(np.uint16), od), i
+        assert np.max(np.abs(sub[i] - osub)) <= 1e-5, i
 
 
 def test_batch_past_one_chunk_and_padded_D(ctx, sva, torch_dev):
