@@ -227,6 +227,42 @@ int sva_disparity_sgm_conf_d(void* ctx, const uint8_t* left, const uint8_t* righ
                              uint16_t* disp, float* subpix, uint16_t* cost_min,
                              uint16_t* cost_second);
 
+/* Multi-baseline Mode S: ONE reference image against n
+ * matched images (1 <= n <= 32), image i along its own step steps[i] = (dir,
+ * dir_y) (steps: host [n][2] i32; p->dir and p->dir_y are ignored).  The n
+ * pairs' cost volumes are fused before the aggregation -- per pixel and
+ * disparity the mean, rounded half up, over the pairs whose matched pixel lies
+ * inside the image, 62 where none does -- and one 8-path SGM + WTA runs on the
+ * fused volume.  The same disparity must mean the same depth in every pair:
+ * pairs whose baselines share their major-axis component (all 8 neighbours of a
+ * camera).  n = 1 equals sva_disparity_sgm_conf* of that pair;
+ * the result does not depend on the order of the images.  others: host array of
+ * n image pointers (device images for _d, host images otherwise).  The outputs,
+ * uniqueness and the size limits are those of sva_disparity_sgm_conf*; the
+ * confidence planes are optional.  Any D in 1..256.  lr_check has no multi-view
+ * definition: SVA_ERR_UNSUPPORTED.  n outside 1..32, a null image or a zero
+ * step: SVA_ERR_INVALID_ARG, before anything is launched.
+ * Workspace: the context's cost workspace grows to (n + 1) * W * H * Dn bytes
+ * (Dn = D rounded up to 64, 128, 192 or 256; 2.4 GB for n = 8 at 1080p D = 128)
+ * next to the aggregation's own volumes, and stays allocated. */
+int sva_disparity_sgm_multi(void* ctx, const uint8_t* ref, const uint8_t* const* others,
+                            const int32_t* steps, int n, int width, int height, size_t pitch,
+                            const sva_sgm_params* p, int uniqueness, uint16_t* disp,
+                            float* subpix, uint16_t* cost_min, uint16_t* cost_second);
+int sva_disparity_sgm_multi_d(void* ctx, const uint8_t* ref, const uint8_t* const* others,
+                              const int32_t* steps, int n, int width, int height, size_t pitch,
+                              const sva_sgm_params* p, int uniqueness, uint16_t* disp,
+                              float* subpix, uint16_t* cost_min, uint16_t* cost_second);
+/* The fusion stage alone: n device volumes [H][W][D] u8, volume i at volumes +
+ * i * stride (stride in bytes, >= W*H*D, may exceed 2^32), into fused
+ * [H][W][D].  D native (64, 128, 192, 256; SVA_ERR_UNSUPPORTED otherwise);
+ * dreal in 1..D: fused = 255 at d >= dreal.  Any u8 input
+ * values are accepted.  volumes, stride and fused must be multiples of 16
+ * (SVA_ERR_INVALID_ARG). */
+int sva_cost_fuse_d(void* ctx, const uint8_t* volumes, size_t stride, int n, int width,
+                    int height, int D, int dreal, int dmin, const int32_t* steps,
+                    uint8_t* fused);
+
 /* A batch of device-resident frames of one shape on this context's stream:
  * pair j matches jobs[j].left against jobs[j].right along its own step
  * (params.dir, params.dir_y), and every frame's cost volume then goes through
@@ -597,6 +633,26 @@ int sva_array_depth_conf(void* multi, const uint8_t* const* images, int n_images
                          int uniqueness, int mode, double* depth, uint8_t* n_valid,
                          uint8_t* winner, uint16_t* maps, uint16_t* cost_min,
                          uint16_t* cost_second);
+/* The multi-baseline ("mb") array frame: the shard unit is
+ * the GROUP.  Group g runs ONE sva_disparity_sgm_multi_d -- its reference view
+ * against all its matched views, the cost volumes fused before a single
+ * aggregation -- on device g mod n_devices, round-robin over that device's
+ * streams; one map per group is gathered (2 bytes per pixel and group, plus 2
+ * for each cost plane asked for, instead of per pair) and turned into depth by
+ * sva_fuse_depth_d with n_maps = 1: baseline * f / ((double)d * pixel_size), 0
+ * where d is 0 or invalid.  depth: host [n_groups][H][W] f64; maps, cost_min,
+ * cost_second (each nullable): host [n_groups][H][W] u16.  uniqueness as for
+ * sva_array_depth_conf.  Within a group the pairs must share ref, D, dmin, P1,
+ * P2 and invalid, and their baselines may differ by at most 1e-9 relative (a
+ * different major-axis baseline is a different depth scale):
+ * SVA_ERR_INVALID_ARG otherwise.  lr_check: SVA_ERR_UNSUPPORTED.  Each context
+ * that runs a group grows its cost workspace as sva_disparity_sgm_multi_d
+ * says.  Synchronous. */
+int sva_array_depth_mb(void* multi, const uint8_t* const* images, int n_images, int width,
+                       int height, size_t pitch, const sva_array_pair* pairs, int n_pairs,
+                       const int32_t* group_start, int n_groups, double f, double pixel_size,
+                       int uniqueness, double* depth, uint16_t* maps, uint16_t* cost_min,
+                       uint16_t* cost_second);
 
 #ifdef __cplusplus
 }

@@ -557,6 +557,75 @@ inline std::vector<std::vector<double>> computeArrayDepthConf(
     return fr.split(depth);
 }
 
+// ---- multi-baseline Mode S -----------------------------
+
+// One reference image against several matched images, image i along steps[i]
+// (PairStep of (ref, other_i); the pairs must share PairStep::k, so that one
+// disparity is one depth in all of them): the pairs' cost volumes are fused
+// before ONE aggregation (sva_disparity_sgm_multi).  p.dir / p.dir_y are
+// ignored.  uniqueness 0..100 (0 = off); subpix, cost_min, cost_second are
+// optional outputs as for sva_disparity_sgm_conf.
+inline std::vector<uint16_t> computeDisparityMulti(
+    Engine& eng, const ImageView& ref, const std::vector<ImageView>& others,
+    const std::vector<PairStep>& steps, const sva_sgm_params& p, int uniqueness = 0,
+    std::vector<float>* subpix = nullptr, std::vector<uint16_t>* cost_min = nullptr,
+    std::vector<uint16_t>* cost_second = nullptr) {
+    if (others.empty() || others.size() != steps.size())
+        throw Error(SVA_ERR_INVALID_ARG, "computeDisparityMulti: need one step per matched image");
+    std::vector<const uint8_t*> ptrs;
+    std::vector<int32_t> st;
+    for (size_t i = 0; i < others.size(); i++) {
+        const ImageView& o = others[i];
+        if (o.width != ref.width || o.height != ref.height || o.pitch != ref.pitch)
+            throw Error(SVA_ERR_INVALID_ARG, "computeDisparityMulti: images differ in size");
+        if (steps[i].k != steps[0].k)
+            throw Error(SVA_ERR_INVALID_ARG, "computeDisparityMulti: pairs of unequal baselines");
+        ptrs.push_back(o.data);
+        st.push_back(steps[i].dir);
+        st.push_back(steps[i].dir_y);
+    }
+    const size_t np = (size_t)ref.width * ref.height;
+    std::vector<uint16_t> disp(np);
+    float* sp = nullptr;
+    if (subpix && p.subpixel) {
+        subpix->resize(np);
+        sp = subpix->data();
+    }
+    if (cost_min) cost_min->resize(np);
+    if (cost_second) cost_second->resize(np);
+    eng.check(sva_disparity_sgm_multi(eng.handle(), ref.data, ptrs.data(), st.data(),
+                                      (int)ptrs.size(), ref.width, ref.height, ref.pitch, &p,
+                                      uniqueness, disp.data(), sp,
+                                      cost_min ? cost_min->data() : nullptr,
+                                      cost_second ? cost_second->data() : nullptr));
+    return disp;
+}
+
+// computeArrayDepth on the multi-baseline route (sva_array_depth_mb): the same
+// grouping by reference camera, but each group's pairs are fused at the cost
+// level and aggregated once, so there is ONE map per reference camera: depth =
+// baseline * f / (d * pixel_size).  The pairs of a group must have equal
+// major-axis baselines (e.g. a camera's 8 neighbours).  maps (nullable)
+// receives each group's u16 map, in the order of the result.
+inline std::vector<std::vector<double>> computeArrayDepthMulti(
+    MultiEngine& m, const std::vector<ImageView>& images, const std::vector<Camera>& cameras,
+    const std::vector<std::array<int, 2>>& pairs, const sva_sgm_params& p, int uniqueness = 0,
+    double pitch = 0.05, std::vector<std::vector<uint16_t>>* maps = nullptr) {
+    const detail::ArrayFrame fr = detail::arrayFrame(images, cameras, pairs, p, pitch,
+                                                     "computeArrayDepthMulti");
+    const size_t np = (size_t)fr.W * fr.H;
+    const int ng = (int)fr.refs.size();
+    std::vector<double> depth(np * ng);
+    std::vector<uint16_t> all(maps ? np * ng : 0);
+    const Camera& c0 = cameras.at(fr.refs[0]);
+    m.check(sva_array_depth_mb(m.handle(), fr.ptrs.data(), (int)fr.ptrs.size(), fr.W, fr.H,
+                               fr.pitch, fr.ap.data(), (int)fr.ap.size(), fr.group_start.data(),
+                               ng, c0.f, c0.pixel_size, uniqueness, depth.data(),
+                               maps ? all.data() : nullptr, nullptr, nullptr));
+    if (maps) *maps = fr.split(all);
+    return fr.split(depth);
+}
+
 // ---- refinement and 3-D output ----
 // The reference's names and argument meaning; cv::Mat becomes ImageView (u8)
 // or a dense W*H std::vector<double>.  Pixels a routine does not write keep

@@ -67,7 +67,8 @@ EXPORTED = [
     "sva_batch_sgm_d", "sva_array_depth", "sva_disparity_sgm_batch_d", "sva_set_debug",
     "sva_get_debug", "sva_disparity_sgm_conf", "sva_disparity_sgm_conf_d", "sva_wta_conf_d",
     "sva_fuse_depth_conf", "sva_fuse_depth_conf_d", "sva_disparity_sgm_batch_conf_d",
-    "sva_batch_sgm_conf_d", "sva_array_depth_conf",
+    "sva_batch_sgm_conf_d", "sva_array_depth_conf", "sva_cost_fuse_d", "sva_disparity_sgm_multi",
+    "sva_disparity_sgm_multi_d", "sva_array_depth_mb",
 ]
 SVA_FUSE_MIN_COST = 0
 SVA_FUSE_MAX_MARGIN = 1
@@ -236,6 +237,13 @@ def _load() -> ct.CDLL:
         "sva_batch_sgm_conf_d": (i32, [vp, P(PairD), i32, i32, i32, sz, i32, vp, vp, vp, vp]),
         "sva_array_depth_conf": (i32, [vp, P(vp), i32, i32, i32, sz, P(ArrayPair), i32, P(i32),
                                        i32, dbl, dbl, i32, i32, vp, vp, vp, vp, vp, vp]),
+        "sva_cost_fuse_d": (i32, [vp, vp, sz, i32, i32, i32, i32, i32, i32, P(ct.c_int32), vp]),
+        "sva_disparity_sgm_multi": (i32, [vp, vp, P(vp), P(ct.c_int32), i32, i32, i32, sz,
+                                          P(SgmParams), i32, vp, vp, vp, vp]),
+        "sva_disparity_sgm_multi_d": (i32, [vp, vp, P(vp), P(ct.c_int32), i32, i32, i32, sz,
+                                            P(SgmParams), i32, vp, vp, vp, vp]),
+        "sva_array_depth_mb": (i32, [vp, P(vp), i32, i32, i32, sz, P(ArrayPair), i32, P(i32), i32,
+                                     dbl, dbl, i32, vp, vp, vp, vp]),
         "sva_resize_linear_f64_d": (i32, [vp, vp, i32, i32, vp, i32, i32]),
         "sva_resize_linear_f64": (i32, [vp, vp, i32, i32, vp, i32, i32]),
         "sva_ref_error_d": (i32, [vp, vp, i32, i32, vp, i32, i32, ct.c_double, vp]),
@@ -422,6 +430,45 @@ class Context:
         self._chk(lib.sva_disparity_sgm_conf_d(self.h, _ptr(left), _ptr(right), W, H, pitch,
                                                ct.byref(params), int(uniqueness), _ptr(disp),
                                                _ptr(sub), _ptr(cost_min), _ptr(cost_second)))
+
+    # -- multi-baseline Mode S: one reference image, n matched images
+    def disparity_sgm_multi(self, ref: np.ndarray, others, steps, params: SgmParams,
+                            uniqueness: int = 0):
+        """(disp, sub, cost_min, cost_second): sva_disparity_sgm_multi.  others: n
+        HxW u8 images, steps: n (dir, dir_y) steps; the n cost volumes are fused
+        (mean over the pairs whose matched pixel is inside the image) before one
+        aggregation.  params.dir / dir_y are ignored."""
+        ref = np.ascontiguousarray(ref, dtype=np.uint8)
+        oth = [np.ascontiguousarray(a, dtype=np.uint8) for a in others]
+        assert len(oth) == len(steps) and all(a.shape == ref.shape for a in oth)
+        H, W = ref.shape
+        ptrs = (ct.c_void_p * max(1, len(oth)))(*[_ptr(a) for a in oth])
+        st = (ct.c_int32 * max(2, 2 * len(steps)))(*[int(v) for s in steps for v in s])
+        disp = np.zeros((H, W), np.uint16)
+        sub = np.zeros((H, W), np.float32) if params.subpixel else None
+        cmin = np.zeros((H, W), np.uint16)
+        csec = np.zeros((H, W), np.uint16)
+        self._chk(lib.sva_disparity_sgm_multi(self.h, _ptr(ref), ptrs, st, len(oth), W, H, W,
+                                              ct.byref(params), int(uniqueness), _ptr(disp),
+                                              _ptr(sub), _ptr(cmin), _ptr(csec)))
+        return disp, sub, cmin, csec
+
+    def disparity_sgm_multi_d(self, ref, others, steps, W, H, pitch, params, uniqueness, disp,
+                              sub=None, cost_min=None, cost_second=None):
+        """Device pointers; others: n image pointers, steps: n (dir, dir_y)."""
+        ptrs = (ct.c_void_p * max(1, len(others)))(*[_ptr(a) for a in others])
+        st = (ct.c_int32 * max(2, 2 * len(steps)))(*[int(v) for s in steps for v in s])
+        self._chk(lib.sva_disparity_sgm_multi_d(self.h, _ptr(ref), ptrs, st, len(others), W, H,
+                                                pitch, ct.byref(params), int(uniqueness),
+                                                _ptr(disp), _ptr(sub), _ptr(cost_min),
+                                                _ptr(cost_second)))
+
+    def cost_fuse_d(self, volumes, stride, steps, W, H, D, dreal, dmin, fused):
+        """sva_cost_fuse_d: len(steps) device volumes [H][W][D] u8, `stride` bytes
+        apart, fused into `fused`."""
+        st = (ct.c_int32 * max(2, 2 * len(steps)))(*[int(v) for s in steps for v in s])
+        self._chk(lib.sva_cost_fuse_d(self.h, _ptr(volumes), stride, len(steps), W, H, D, dreal,
+                                      dmin, st, _ptr(fused)))
 
     def wta_conf_d(self, S, W, H, params, uniqueness, disp, sub=None, cost_min=None,
                    cost_second=None):
@@ -813,6 +860,29 @@ class Multi:
                                            _ptr(depth), _ptr(nv), _ptr(win), _ptr(maps),
                                            _ptr(cmin), _ptr(csec)))
         return depth, nv, win, maps, cmin, csec
+
+    def array_depth_mb(self, images, pairs, group_start, f, pixel_size, uniqueness=0,
+                       want_maps=False, want_costs=False):
+        """The multi-baseline array frame (sva_array_depth_mb): each group's pairs
+        (one reference view, equal baselines) are fused at the cost level and
+        aggregated once.  Returns (depth [G,H,W] f64, maps, cost_min,
+        cost_second), the last three [G,H,W] u16 or None."""
+        imgs = [np.ascontiguousarray(a, dtype=np.uint8) for a in images]
+        H, W = imgs[0].shape
+        ptrs = (ct.c_void_p * len(imgs))(*[_ptr(a) for a in imgs])
+        jp = (ArrayPair * len(pairs))()
+        for i, (a, b, p, base) in enumerate(pairs):
+            jp[i] = ArrayPair(a, b, p, base)
+        gs = (ct.c_int32 * len(group_start))(*group_start)
+        G = len(group_start) - 1
+        depth = np.zeros((G, H, W), np.float64)
+        maps = np.zeros((G, H, W), np.uint16) if want_maps else None
+        cmin = np.zeros((G, H, W), np.uint16) if want_costs else None
+        csec = np.zeros((G, H, W), np.uint16) if want_costs else None
+        self._chk(lib.sva_array_depth_mb(self.h, ptrs, len(imgs), W, H, W, jp, len(pairs), gs, G,
+                                         f, pixel_size, int(uniqueness), _ptr(depth), _ptr(maps),
+                                         _ptr(cmin), _ptr(csec)))
+        return depth, maps, cmin, csec
 
     def array_depth(self, images, pairs, group_start, f, pixel_size, want_maps=False):
         """images: list of HxW u8 numpy views; pairs: list of (ref, other,

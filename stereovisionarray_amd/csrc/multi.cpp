@@ -12,14 +12,18 @@
 // through the public per-context entry points (sva_disparity_sgm_d,
 // sva_fuse_depth_d, and sva_disparity_sgm_conf_d / sva_fuse_depth_conf_d for
 // the confidence forms, whose cost planes are gathered like the maps); there
-// is no CPU path.
+// is no CPU path.  sva_array_depth_mb shards GROUPS instead (one
+// sva_disparity_sgm_multi_d per reference camera) through the
+// same plan, slots and gather (run_jobs).
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
 #include <dlfcn.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstring>
+#include <functional>
 #include <new>
 #include <string>
 #include <thread>
@@ -244,14 +248,20 @@ struct ConfPlanes {
     uint16_t* cost_second = nullptr;
 };
 
-// The shared part of sva_batch_sgm_d / sva_array_depth and their confidence
-// forms: run every pair on its context, gather to devices[0].  left/right:
-// per-job device pointers; maps/sub on devices[0] ([n][H][W]); sub may be
-// null; cp null = the plain route (sva_disparity_sgm_d).
-int run_pairs(Multi* m, const Plan& P, const std::vector<const uint8_t*>& left,
-              const std::vector<const uint8_t*>& right, const std::vector<sva_sgm_params>& prm,
-              const std::vector<std::vector<hipEvent_t>>& wait_for, int W, int H, size_t pitch,
-              uint16_t* maps, float* sub, const ConfPlanes* cp = nullptr) {
+// One job's compute call on context cx (its device is current, its waits are
+// queued): the map to od, and to os / omin / osec where they are non-null.
+using JobCall = std::function<int(int j, void* cx, uint16_t* od, float* os, uint16_t* omin,
+                                  uint16_t* osec)>;
+
+// The shared part of sva_batch_sgm_d / sva_array_depth, their confidence forms
+// and sva_array_depth_mb: run every job on its context, gather to devices[0].
+// A job is whatever `call` computes into one set of [H][W] planes: a pair
+// (run_pairs) or a reference camera's whole group (sva_array_depth_mb).
+// maps/sub on devices[0] ([n][H][W]); sub may be null, has_sub[j] = job j
+// writes one; cp null = no cost planes.
+int run_jobs(Multi* m, const Plan& P, const std::vector<std::vector<hipEvent_t>>& wait_for, int W,
+             int H, uint16_t* maps, float* sub, const std::vector<char>& has_sub,
+             const ConfPlanes* cp, const JobCall& call, const char* what) {
     const int n = (int)P.dev.size();
     const size_t np = (size_t)W * H;
     uint16_t* const cmin = cp ? cp->cost_min : nullptr;
@@ -320,11 +330,8 @@ int run_pairs(Multi* m, const Plan& P, const std::vector<const uint8_t*>& left,
         }
         MHIP(m, hipSetDevice(m->devices[d]), "hipSetDevice");
         for (hipEvent_t e : wait_for[j]) MHIP(m, hipStreamWaitEvent(m->st(d, s), e, 0), "wait");
-        const int st = cp ? sva_disparity_sgm_conf_d(m->ctx[ci], left[j], right[j], W, H, pitch,
-                                                     &prm[j], cp->uniqueness, od, os, omin, osec)
-                          : sva_disparity_sgm_d(m->ctx[ci], left[j], right[j], W, H, pitch, &prm[j],
-                                                od, os);
-        if (st != SVA_OK) return m->ctx_fail(st, m->ctx[ci], "pair");
+        const int st = call(j, m->ctx[ci], od, os, omin, osec);
+        if (st != SVA_OK) return m->ctx_fail(st, m->ctx[ci], what);
     }
     // 3. join each device's streams into its stream 0
     for (int d = 0; d < m->nd(); d++)
@@ -340,7 +347,7 @@ int run_pairs(Multi* m, const Plan& P, const std::vector<const uint8_t*>& left,
         // only jobs that asked for a sub-pixel map have one (sva.h); the
         // others' planes of `sub` are left untouched, local or remote
         std::vector<char> remote_sub(remote);
-        for (int j = 0; j < n; j++) remote_sub[j] = remote[j] && prm[j].subpixel != 0;
+        for (int j = 0; j < n; j++) remote_sub[j] = remote[j] && has_sub[j];
         if ((st = gather(m, P, remote_sub, src_sub, (uint8_t*)sub, np * 4))) return st;
     }
     if (cmin && (st = gather(m, P, remote, src_min, (uint8_t*)cmin, np * 2))) return st;
@@ -351,6 +358,24 @@ int run_pairs(Multi* m, const Plan& P, const std::vector<const uint8_t*>& left,
     }
     m->gathered_valid = true;
     return SVA_OK;
+}
+
+// Pairs as jobs: left/right are per-job device pointers; cp null = the plain
+// route (sva_disparity_sgm_d), else sva_disparity_sgm_conf_d.
+int run_pairs(Multi* m, const Plan& P, const std::vector<const uint8_t*>& left,
+              const std::vector<const uint8_t*>& right, const std::vector<sva_sgm_params>& prm,
+              const std::vector<std::vector<hipEvent_t>>& wait_for, int W, int H, size_t pitch,
+              uint16_t* maps, float* sub, const ConfPlanes* cp = nullptr) {
+    std::vector<char> has_sub(prm.size());
+    for (size_t j = 0; j < prm.size(); j++) has_sub[j] = prm[j].subpixel != 0;
+    return run_jobs(
+        m, P, wait_for, W, H, maps, sub, has_sub, cp,
+        [&](int j, void* cx, uint16_t* od, float* os, uint16_t* omin, uint16_t* osec) {
+            return cp ? sva_disparity_sgm_conf_d(cx, left[j], right[j], W, H, pitch, &prm[j],
+                                                 cp->uniqueness, od, os, omin, osec)
+                      : sva_disparity_sgm_d(cx, left[j], right[j], W, H, pitch, &prm[j], od, os);
+        },
+        "pair");
 }
 
 int check_params(const sva_sgm_params& p) {
@@ -691,6 +716,71 @@ int batch_sgm_d(void* mp, const sva_pair_d* jobs, int n_jobs, int W, int H, size
     return run_pairs(m, P, l, r, prm, none, W, H, pitch, maps, any_sub ? sub : nullptr, cp);
 }
 
+// The host views of an array frame onto the devices that need them
+// (sva_array_depth*): pair j runs on device dev_of[j].  Out: slot_of[d][v], the
+// slot of view v in m->images[d] (-1: not needed there), and up_ev[d][v], the
+// event of its upload on the device's copy stream.
+int upload_views(Multi* m, const uint8_t* const* images, int n_images, int W, int H, size_t pitch,
+                 const sva_array_pair* pairs, int n_pairs, const std::vector<int32_t>& dev_of,
+                 std::vector<std::vector<int>>& slot_of,
+                 std::vector<std::vector<hipEvent_t>>& up_ev) {
+    const size_t np = (size_t)W * H;
+    if (m->copy.empty()) {
+        m->copy.assign(m->nd(), nullptr);
+        m->down.assign(m->nd(), nullptr);
+        for (int d = 0; d < m->nd(); d++) {
+            MHIP(m, hipSetDevice(m->devices[d]), "hipSetDevice");
+            MHIP(m, hipStreamCreateWithFlags(&m->copy[d], hipStreamNonBlocking), "stream");
+            MHIP(m, hipStreamCreateWithFlags(&m->down[d], hipStreamNonBlocking), "stream");
+        }
+    }
+    // 1. which views each device needs, staged once into pinned memory
+    slot_of.assign(m->nd(), std::vector<int>(n_images, -1));
+    std::vector<int> n_need(m->nd(), 0);
+    std::vector<char> used(n_images, 0);
+    for (int j = 0; j < n_pairs; j++)
+        for (int v : {pairs[j].ref, pairs[j].other}) {
+            used[v] = 1;
+            int& s = slot_of[dev_of[j]][v];
+            if (s < 0) s = n_need[dev_of[j]]++;
+        }
+    std::vector<int> pin_slot(n_images, -1);
+    int n_pin = 0;
+    for (int v = 0; v < n_images; v++)
+        if (used[v]) pin_slot[v] = n_pin++;
+    // the previous call's uploads must be done before the pinned staging is rewritten
+    for (int d = 0; d < m->nd(); d++) {
+        MHIP(m, hipSetDevice(m->devices[d]), "hipSetDevice");
+        MHIP(m, hipStreamSynchronize(m->copy[d]), "synchronize");
+    }
+    MHIP(m, m->stage_in.ensure((size_t)n_pin * np), "pinned staging");
+    // 2. uploads on each device's copy stream, one event per (device, view);
+    // the images buffer is reused only after the previous call's pairs ran
+    up_ev.assign(m->nd(), std::vector<hipEvent_t>(n_images));
+    for (int v = 0; v < n_images; v++)
+        if (used[v])
+            copy_plane((uint8_t*)m->stage_in.ptr + (size_t)pin_slot[v] * np, images[v], W, H, pitch);
+    for (int d = 0; d < m->nd(); d++) {
+        if (!n_need[d]) continue;
+        MHIP(m, hipSetDevice(m->devices[d]), "hipSetDevice");
+        for (int s = 0; s < m->spd; s++) {
+            int st = stream_after(m, d, m->st(d, s), m->copy[d]);
+            if (st) return st;
+        }
+        MHIP(m, m->images[d].ensure((size_t)n_need[d] * np), "view workspace");
+        for (int v = 0; v < n_images; v++) {
+            if (slot_of[d][v] < 0) continue;
+            MHIP(m, hipMemcpyAsync((uint8_t*)m->images[d].ptr + (size_t)slot_of[d][v] * np,
+                                   (uint8_t*)m->stage_in.ptr + (size_t)pin_slot[v] * np, np,
+                                   hipMemcpyHostToDevice, m->copy[d]),
+                 "upload");
+            MHIP(m, ev_on(m, d, &up_ev[d][v]), "event");
+            MHIP(m, hipEventRecord(up_ev[d][v], m->copy[d]), "event record");
+        }
+    }
+    return SVA_OK;
+}
+
 // sva_array_depth (conf false: plain matching, median fusion) and
 // sva_array_depth_conf (every pair through the uniqueness filter; `mode` picks
 // the fusion; winner, cost_min, cost_second: nullable host outputs).
@@ -733,59 +823,11 @@ int array_depth(void* mp, const uint8_t* const* images, int n_images, int W, int
     const size_t np = (size_t)W * H;
     Plan P;
     make_plan(m->nd(), m->spd, n_pairs, P);
-    if (m->copy.empty()) {
-        m->copy.assign(m->nd(), nullptr);
-        m->down.assign(m->nd(), nullptr);
-        for (int d = 0; d < m->nd(); d++) {
-            MHIP(m, hipSetDevice(m->devices[d]), "hipSetDevice");
-            MHIP(m, hipStreamCreateWithFlags(&m->copy[d], hipStreamNonBlocking), "stream");
-            MHIP(m, hipStreamCreateWithFlags(&m->down[d], hipStreamNonBlocking), "stream");
-        }
-    }
-    // 1. which views each device needs, staged once into pinned memory
-    std::vector<std::vector<int>> slot_of(m->nd(), std::vector<int>(n_images, -1));
-    std::vector<int> n_need(m->nd(), 0);
-    std::vector<char> used(n_images, 0);
-    for (int j = 0; j < n_pairs; j++)
-        for (int v : {pairs[j].ref, pairs[j].other}) {
-            used[v] = 1;
-            int& s = slot_of[P.dev[j]][v];
-            if (s < 0) s = n_need[P.dev[j]]++;
-        }
-    std::vector<int> pin_slot(n_images, -1);
-    int n_pin = 0;
-    for (int v = 0; v < n_images; v++)
-        if (used[v]) pin_slot[v] = n_pin++;
-    // the previous call's uploads must be done before the pinned staging is rewritten
-    for (int d = 0; d < m->nd(); d++) {
-        MHIP(m, hipSetDevice(m->devices[d]), "hipSetDevice");
-        MHIP(m, hipStreamSynchronize(m->copy[d]), "synchronize");
-    }
-    MHIP(m, m->stage_in.ensure((size_t)n_pin * np), "pinned staging");
-    // 2. uploads on each device's copy stream, one event per (device, view);
-    // the images buffer is reused only after the previous call's pairs ran
-    std::vector<std::vector<hipEvent_t>> up_ev(m->nd(), std::vector<hipEvent_t>(n_images));
-    for (int v = 0; v < n_images; v++)
-        if (used[v])
-            copy_plane((uint8_t*)m->stage_in.ptr + (size_t)pin_slot[v] * np, images[v], W, H, pitch);
-    for (int d = 0; d < m->nd(); d++) {
-        if (!n_need[d]) continue;
-        MHIP(m, hipSetDevice(m->devices[d]), "hipSetDevice");
-        for (int s = 0; s < m->spd; s++) {
-            int st = stream_after(m, d, m->st(d, s), m->copy[d]);
-            if (st) return st;
-        }
-        MHIP(m, m->images[d].ensure((size_t)n_need[d] * np), "view workspace");
-        for (int v = 0; v < n_images; v++) {
-            if (slot_of[d][v] < 0) continue;
-            MHIP(m, hipMemcpyAsync((uint8_t*)m->images[d].ptr + (size_t)slot_of[d][v] * np,
-                                   (uint8_t*)m->stage_in.ptr + (size_t)pin_slot[v] * np, np,
-                                   hipMemcpyHostToDevice, m->copy[d]),
-                 "upload");
-            MHIP(m, ev_on(m, d, &up_ev[d][v]), "event");
-            MHIP(m, hipEventRecord(up_ev[d][v], m->copy[d]), "event record");
-        }
-    }
+    // 1-2. the views each device needs, uploaded on its copy stream
+    std::vector<std::vector<int>> slot_of;
+    std::vector<std::vector<hipEvent_t>> up_ev;
+    if (int st = upload_views(m, images, n_images, W, H, pitch, pairs, n_pairs, P.dev, slot_of, up_ev))
+        return st;
     // 3. pairs + gather into maps0 on device 0
     MHIP(m, hipSetDevice(m->devices[0]), "hipSetDevice");
     MHIP(m, hipStreamSynchronize(m->st(0, 0)), "synchronize");   // maps0/depth0 reuse
@@ -877,6 +919,143 @@ int array_depth(void* mp, const uint8_t* const* images, int n_images, int W, int
     if (cost_second) std::memcpy(cost_second, pout + o_sec, plane);
     return SVA_OK;
 }
+
+// sva_array_depth_mb: the multi-baseline array route.  The
+// job is the GROUP: group g's pairs go through one sva_disparity_sgm_multi_d
+// on device g mod n_devices, and one map per group is gathered and turned
+// into depth.
+int array_depth_mb(void* mp, const uint8_t* const* images, int n_images, int W, int H, size_t pitch,
+                   const sva_array_pair* pairs, int n_pairs, const int32_t* group_start,
+                   int n_groups, double f, double pixel_size, int uniqueness, double* depth,
+                   uint16_t* maps, uint16_t* cost_min, uint16_t* cost_second) {
+    Multi* m = as_multi(mp);
+    if (!m) return SVA_ERR_INVALID_ARG;
+    if (uniqueness < 0 || uniqueness > 100)
+        return m->fail(SVA_ERR_INVALID_ARG, "uniqueness must be 0..100");
+    if (!images || n_images <= 0 || !pairs || n_pairs <= 0 || !group_start || n_groups <= 0 ||
+        !depth || W <= 0 || H <= 0 || pitch < (size_t)W)
+        return m->fail(SVA_ERR_INVALID_ARG, "bad array arguments");
+    if (group_start[0] != 0 || group_start[n_groups] != n_pairs)
+        return m->fail(SVA_ERR_INVALID_ARG, "group_start must run from 0 to n_pairs");
+    for (int j = 0; j < n_pairs; j++) {
+        const sva_array_pair& q = pairs[j];
+        if (q.ref < 0 || q.ref >= n_images || q.other < 0 || q.other >= n_images ||
+            !images[q.ref] || !images[q.other] || check_params(q.params))
+            return m->fail(SVA_ERR_INVALID_ARG, "bad pair " + std::to_string(j));
+        if (q.params.lr_check)
+            return m->fail(SVA_ERR_UNSUPPORTED, "the multi-baseline route has no L/R check");
+    }
+    for (int g = 0; g < n_groups; g++) {
+        const int j0 = group_start[g], n = group_start[g + 1] - j0;
+        if (n <= 0 || n > 32) return m->fail(SVA_ERR_UNSUPPORTED, "groups of 1..32 pairs");
+        // one reference view, one disparity range, one depth scale per group
+        const sva_array_pair& a = pairs[j0];
+        for (int j = j0 + 1; j < j0 + n; j++) {
+            const sva_array_pair& q = pairs[j];
+            if (q.ref != a.ref)
+                return m->fail(SVA_ERR_INVALID_ARG,
+                               "the pairs of group " + std::to_string(g) + " do not share ref");
+            if (q.params.D != a.params.D || q.params.dmin != a.params.dmin ||
+                q.params.P1 != a.params.P1 || q.params.P2 != a.params.P2 ||
+                q.params.invalid != a.params.invalid)
+                return m->fail(SVA_ERR_INVALID_ARG, "the pairs of group " + std::to_string(g) +
+                                                        " must share D, dmin, P1, P2 and invalid");
+            const double big = std::max(std::fabs(q.baseline), std::fabs(a.baseline));
+            if (!(std::fabs(q.baseline - a.baseline) <= 1e-9 * big))
+                return m->fail(SVA_ERR_INVALID_ARG, "the pairs of group " + std::to_string(g) +
+                                                        " have different major-axis baselines");
+        }
+    }
+    ev_reset(m);
+    const size_t np = (size_t)W * H;
+    Plan P;
+    make_plan(m->nd(), m->spd, n_groups, P);
+    std::vector<int32_t> dev_of(n_pairs);
+    for (int g = 0; g < n_groups; g++)
+        for (int j = group_start[g]; j < group_start[g + 1]; j++) dev_of[j] = P.dev[g];
+    std::vector<std::vector<int>> slot_of;
+    std::vector<std::vector<hipEvent_t>> up_ev;
+    if (int st = upload_views(m, images, n_images, W, H, pitch, pairs, n_pairs, dev_of, slot_of,
+                              up_ev))
+        return st;
+    MHIP(m, hipSetDevice(m->devices[0]), "hipSetDevice");
+    MHIP(m, hipStreamSynchronize(m->st(0, 0)), "synchronize");   // maps0/depth0 reuse
+    const size_t plane = np * 2 * n_groups;
+    MHIP(m, m->maps0.ensure(plane), "map workspace");
+    MHIP(m, m->depth0.ensure(np * 8 * n_groups), "depth workspace");
+    if (cost_min || cost_second)
+        MHIP(m, m->conf0.ensure(plane * ((cost_min ? 1 : 0) + (cost_second ? 1 : 0))),
+             "cost planes");
+    uint16_t* maps0 = (uint16_t*)m->maps0.ptr;
+    ConfPlanes cp;
+    cp.uniqueness = uniqueness;
+    cp.cost_min = cost_min ? (uint16_t*)m->conf0.ptr : nullptr;
+    cp.cost_second =
+        cost_second ? (uint16_t*)m->conf0.ptr + (cost_min ? np * n_groups : 0) : nullptr;
+    // per group: its reference view, its matched views and steps, its uploads
+    std::vector<std::vector<const uint8_t*>> others(n_groups);
+    std::vector<std::vector<int32_t>> steps(n_groups);
+    std::vector<const uint8_t*> ref(n_groups);
+    std::vector<sva_sgm_params> prm(n_groups);
+    std::vector<std::vector<hipEvent_t>> waits(n_groups);
+    for (int g = 0; g < n_groups; g++) {
+        const int d = P.dev[g], j0 = group_start[g];
+        const uint8_t* base = (const uint8_t*)m->images[d].ptr;
+        ref[g] = base + (size_t)slot_of[d][pairs[j0].ref] * np;
+        waits[g].push_back(up_ev[d][pairs[j0].ref]);
+        for (int j = j0; j < group_start[g + 1]; j++) {
+            others[g].push_back(base + (size_t)slot_of[d][pairs[j].other] * np);
+            steps[g].push_back(pairs[j].params.dir);
+            steps[g].push_back(pairs[j].params.dir_y);
+            waits[g].push_back(up_ev[d][pairs[j].other]);
+        }
+        prm[g] = pairs[j0].params;
+        prm[g].subpixel = 0;
+    }
+    int st = run_jobs(
+        m, P, waits, W, H, maps0, nullptr, std::vector<char>(n_groups, 0), &cp,
+        [&](int g, void* cx, uint16_t* od, float*, uint16_t* omin, uint16_t* osec) {
+            return sva_disparity_sgm_multi_d(cx, ref[g], others[g].data(), steps[g].data(),
+                                             (int)others[g].size(), W, H, W, &prm[g], uniqueness,
+                                             od, nullptr, omin, osec);
+        },
+        "group");
+    if (st) return st;
+    // depth per group on device 0 (one map: the median of one is the map's own
+    // depth), each group's download as soon as it is done
+    MHIP(m, hipSetDevice(m->devices[0]), "hipSetDevice");
+    const size_t o_maps = np * 8 * n_groups, o_min = o_maps + (maps ? plane : 0);
+    const size_t o_sec = o_min + (cost_min ? plane : 0);
+    MHIP(m, m->stage_out.ensure(o_sec + (cost_second ? plane : 0)), "pinned staging");
+    uint8_t* pout = (uint8_t*)m->stage_out.ptr;
+    double* depth0 = (double*)m->depth0.ptr;
+    for (int g = 0; g < n_groups; g++) {
+        const sva_array_pair& a = pairs[group_start[g]];
+        st = sva_fuse_depth_d(m->ctx[0], maps0 + (size_t)g * np, 1, W, H, &a.baseline, f,
+                              pixel_size, a.params.invalid, depth0 + (size_t)g * np, nullptr);
+        if (st) return m->ctx_fail(st, m->ctx[0], "depth");
+        if ((st = stream_after(m, 0, m->st(0, 0), m->down[0]))) return st;
+        MHIP(m, hipMemcpyAsync(pout + (size_t)g * np * 8, depth0 + (size_t)g * np, np * 8,
+                               hipMemcpyDeviceToHost, m->down[0]),
+             "download");
+    }
+    if (maps)
+        MHIP(m, hipMemcpyAsync(pout + o_maps, maps0, plane, hipMemcpyDeviceToHost, m->down[0]),
+             "download");
+    if (cost_min)
+        MHIP(m, hipMemcpyAsync(pout + o_min, cp.cost_min, plane, hipMemcpyDeviceToHost, m->down[0]),
+             "download");
+    if (cost_second)
+        MHIP(m, hipMemcpyAsync(pout + o_sec, cp.cost_second, plane, hipMemcpyDeviceToHost,
+                               m->down[0]),
+             "download");
+    MHIP(m, hipStreamSynchronize(m->down[0]), "synchronize");
+    std::memcpy(depth, pout, np * 8 * n_groups);
+    if (maps) std::memcpy(maps, pout + o_maps, plane);
+    if (cost_min) std::memcpy(cost_min, pout + o_min, plane);
+    if (cost_second) std::memcpy(cost_second, pout + o_sec, plane);
+    return SVA_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -914,6 +1093,15 @@ int sva_array_depth_conf(void* mp, const uint8_t* const* images, int n_images, i
     return array_depth(mp, images, n_images, W, H, pitch, pairs, n_pairs, group_start, n_groups, f,
                        pixel_size, true, uniqueness, mode, depth, n_valid, winner, maps, cost_min,
                        cost_second);
+}
+
+int sva_array_depth_mb(void* mp, const uint8_t* const* images, int n_images, int W, int H,
+                       size_t pitch, const sva_array_pair* pairs, int n_pairs,
+                       const int32_t* group_start, int n_groups, double f, double pixel_size,
+                       int uniqueness, double* depth, uint16_t* maps, uint16_t* cost_min,
+                       uint16_t* cost_second) {
+    return array_depth_mb(mp, images, n_images, W, H, pitch, pairs, n_pairs, group_start, n_groups,
+                          f, pixel_size, uniqueness, depth, maps, cost_min, cost_second);
 }
 
 }  // extern "C"

@@ -1014,7 +1014,154 @@ int sgm_batch_d(void* ctx, const sva_pair_d* jobs, int n, int W, int H, size_t p
     }
     return SVA_OK;
 }
+
+// The steps of the multi-baseline entry points: n in 1..32 nonzero steps.
+int check_steps(Ctx* c, const int32_t* steps, int n) {
+    if (n < 1 || n > 32) return fail(c, SVA_ERR_INVALID_ARG, "n must be 1..32 matched images");
+    if (!steps) return fail(c, SVA_ERR_INVALID_ARG, "null steps");
+    for (int i = 0; i < n; i++) {
+        const int sx = steps[2 * i], sy = steps[2 * i + 1];
+        if (sx < -255 || sx > 255 || sy < -255 || sy > 255 || (sx == 0 && sy == 0))
+            return fail(c, SVA_ERR_INVALID_ARG, "every step must be nonzero, |comp| <= 255");
+    }
+    return SVA_OK;
+}
+
+// Arguments of sva_disparity_sgm_multi[_d]; nothing is launched before they pass.
+int check_sgm_multi(Ctx* c, const uint8_t* ref, const uint8_t* const* others, const int32_t* steps,
+                    int n, int W, int H, size_t pitch, const sva_sgm_params* p, int uniqueness,
+                    const uint16_t* disp) {
+    int s;
+    if (!p) return fail(c, SVA_ERR_INVALID_ARG, "null params");
+    if ((s = check_steps(c, steps, n))) return s;
+    if (!others) return fail(c, SVA_ERR_INVALID_ARG, "null image list");
+    if ((s = check_image(c, ref, W, H, pitch))) return s;
+    for (int i = 0; i < n; i++)
+        if ((s = check_image(c, others[i], W, H, pitch))) return s;
+    sva_sgm_params q = *p;   // (dir, dir_y) of the params are ignored: the steps stand in
+    q.dir = steps[0];
+    q.dir_y = steps[1];
+    q.lr_check = 0;
+    if ((s = check_sgm(c, &q, W, H)) || (s = check_uniqueness(c, uniqueness))) return s;
+    if (p->lr_check)
+        return fail(c, SVA_ERR_UNSUPPORTED, "the multi-baseline route has no L/R check");
+    if (!disp) return fail(c, SVA_ERR_INVALID_ARG, "null disparity output");
+    if (!wta_hv_supported(padded_D(p->D)))
+        return fail(c, SVA_ERR_UNSUPPORTED, "no tile pipeline for this D");
+    return SVA_OK;
+}
+
+// Multi-baseline Mode S on device buffers: pair i's cost
+// volume (ref against others[i] along steps[i]) into slot i of the cost
+// workspace, cost_fuse into slot n, then the frame's aggregation and WTA on the
+// fused volume.  The workspace holds n + 1 volumes.
+int run_sgm_multi_device(Ctx* c, const uint8_t* ref, const uint8_t* const* others,
+                         const int32_t* steps, int n, int W, int H, size_t pitch,
+                         const sva_sgm_params* p, uint16_t* disp, float* sub, const ConfOut* cf) {
+    const int Dp = padded_D(p->D);
+    const size_t np = (size_t)W * H, nv = np * (size_t)Dp;
+    SVA_HIP(c, c->cost.ensure(nv * ((size_t)n + 1)), "cost workspace");
+    uint8_t* C = (uint8_t*)c->cost.ptr;
+    // The pairs' cost kernels run one after another on the context stream: each
+    // fills the chip, and spreading them over side streams measured no faster
+    // (DESIGN.md §4.19).
+    uint64_t *cl = nullptr, *cr = nullptr;
+    for (int i = 0; i < n; i++) {
+        const int sx = steps[2 * i], sy = steps[2 * i + 1];
+        const CostRoute route = cost_route(Dp, sx, sy);
+        if (route == CostRoute::Split && !cl) {
+            SVA_HIP(c, c->census_l.ensure(np * 8), "census workspace");
+            SVA_HIP(c, c->census_r.ensure(np * 8), "census workspace");
+            cl = (uint64_t*)c->census_l.ptr;
+            cr = (uint64_t*)c->census_r.ptr;
+        }
+        const char* what = "cost launch";
+        const hipError_t e = form_cost(*c, route, ref, others[i], W, H, pitch, Dp, p, sx, sy,
+                                       C + (size_t)i * nv, cl, cr, true, &what);
+        if (e != hipSuccess) return hip_fail(c, e, what);
+    }
+    uint8_t* Cf = C + (size_t)n * nv;
+    SVA_HIP(c, launch_cost_fuse(*c, C, nv, n, W, H, Dp, p->D, p->dmin, steps, Cf), "fuse launch");
+    return paths_wta(c, Cf, W, H, p, Dp, disp, sub, cf);
+}
 }  // namespace
+
+int sva_cost_fuse_d(void* ctx, const uint8_t* volumes, size_t stride, int n, int W, int H, int D,
+                    int dreal, int dmin, const int32_t* steps, uint8_t* fused) {
+    Ctx* c = as_ctx(ctx);
+    SVA_CHECK_CTX(c);
+    int s;
+    if ((s = check_steps(c, steps, n))) return s;
+    if (!volumes || !fused) return fail(c, SVA_ERR_INVALID_ARG, "null volume");
+    if (W <= 0 || H <= 0) return fail(c, SVA_ERR_INVALID_ARG, "image size must be positive");
+    if (!paths_supported(D))
+        return fail(c, SVA_ERR_UNSUPPORTED, "stage entry points take D in {64,128,192,256}");
+    if (dreal < 1 || dreal > D) return fail(c, SVA_ERR_INVALID_ARG, "dreal must be 1..D");
+    if (dmin < 0 || dmin + D > 65535)
+        return fail(c, SVA_ERR_INVALID_ARG, "dmin >= 0 and dmin + D must fit the u16 disparity map");
+    if ((unsigned long long)W * (unsigned long long)H * (unsigned)D >= (1ull << 32))
+        return fail(c, SVA_ERR_UNSUPPORTED, "W*H*D must be < 2^32 (32-bit volume offsets)");
+    // one dwordx4 per lane and volume
+    if (((uintptr_t)volumes | (uintptr_t)fused | stride) & 15)
+        return fail(c, SVA_ERR_INVALID_ARG, "volumes, stride and fused must be 16-byte aligned");
+    if (n > 1 && stride < (size_t)W * H * (size_t)D)
+        return fail(c, SVA_ERR_INVALID_ARG, "stride smaller than one volume");
+    SVA_HIP(c, launch_cost_fuse(*c, volumes, stride, n, W, H, D, dreal, dmin, steps, fused),
+            "fuse launch");
+    return SVA_OK;
+}
+
+int sva_disparity_sgm_multi_d(void* ctx, const uint8_t* ref, const uint8_t* const* others,
+                              const int32_t* steps, int n, int W, int H, size_t pitch,
+                              const sva_sgm_params* p, int uniqueness, uint16_t* disp, float* sub,
+                              uint16_t* cost_min, uint16_t* cost_second) {
+    Ctx* c = as_ctx(ctx);
+    SVA_CHECK_CTX(c);
+    if (int s = check_sgm_multi(c, ref, others, steps, n, W, H, pitch, p, uniqueness, disp))
+        return s;
+    const ConfOut cf{cost_min, cost_second, uniqueness, p->invalid};
+    const bool conf = cost_min || cost_second || uniqueness;
+    return run_sgm_multi_device(c, ref, others, steps, n, W, H, pitch, p, disp,
+                                p->subpixel ? sub : nullptr, conf ? &cf : nullptr);
+}
+
+int sva_disparity_sgm_multi(void* ctx, const uint8_t* ref, const uint8_t* const* others,
+                            const int32_t* steps, int n, int W, int H, size_t pitch,
+                            const sva_sgm_params* p, int uniqueness, uint16_t* disp, float* sub,
+                            uint16_t* cost_min, uint16_t* cost_second) {
+    Ctx* c = as_ctx(ctx);
+    SVA_CHECK_CTX(c);
+    int s;
+    if ((s = check_sgm_multi(c, ref, others, steps, n, W, H, pitch, p, uniqueness, disp))) return s;
+    const bool want_sub = p->subpixel && sub;
+    const size_t np = (size_t)W * H;
+    Staging g{c};
+    const uint8_t* dref = g.up2d(c->in_a, ref, pitch, W, H);
+    // the matched images share one staging buffer
+    uint8_t* doth = g.out<uint8_t>(c->in_b, np * (size_t)n);
+    const uint8_t* dptr[32];
+    for (int i = 0; i < n && g.st == SVA_OK; i++) {
+        dptr[i] = doth + (size_t)i * np;
+        g.note(hipMemcpy2DAsync(doth + (size_t)i * np, W, others[i], pitch, W, H,
+                                hipMemcpyHostToDevice, c->stream),
+               "upload");
+    }
+    uint16_t* dd = g.out<uint16_t>(c->out_a, np * 2);
+    float* ds = want_sub ? g.out<float>(c->out_b, np * 4) : nullptr;
+    uint16_t* dc = cost_min || cost_second ? g.out<uint16_t>(c->out_c, np * 4) : nullptr;
+    if (g.st) return g.st;
+    const ConfOut cf{cost_min ? dc : nullptr, cost_second ? dc + np : nullptr, uniqueness,
+                     p->invalid};
+    const bool conf = cost_min || cost_second || uniqueness;
+    if ((s = run_sgm_multi_device(c, dref, dptr, steps, n, W, H, W, p, dd, ds,
+                                  conf ? &cf : nullptr)))
+        return s;
+    g.down(disp, dd, np * 2);
+    if (want_sub) g.down(sub, ds, np * 4);
+    g.down(cost_min, cf.cost_min, np * 2);
+    g.down(cost_second, cf.cost_second, np * 2);
+    return g.sync();
+}
 
 int sva_disparity_sgm_d(void* ctx, const uint8_t* left, const uint8_t* right, int W, int H,
                         size_t pitch, const sva_sgm_params* p, uint16_t* disp, float* sub) {

@@ -250,6 +250,13 @@ hipError_t launch_lr_check(Ctx& c, uint16_t* disp_l, const uint16_t* disp_r, flo
 // 2-D matching step (sy != 0); sy == 0 forwards to launch_cost(dir = sx).
 hipError_t launch_cost2(Ctx& c, const uint64_t* cl, const uint64_t* cr, int W, int H, int D,
                         int dmin, int sx, int sy, uint8_t* C, int dreal = 0);
+// cost_fuse.hip -- multi-baseline cost fusion: n <= 32 cost
+// volumes [H][W][D] (native D), volume i at volumes + i * stride, of one
+// reference image matched along steps[i] = (sx, sy), into `fused`: per cell the
+// mean (rounded half up) over the pairs whose matched pixel is inside the
+// image, 62 where none is, 255 at d >= dreal (0 = D).
+hipError_t launch_cost_fuse(Ctx& c, const uint8_t* volumes, size_t stride, int n, int W, int H,
+                            int D, int dreal, int dmin, const int32_t* steps, uint8_t* fused);
 // Median depth fusion over n_maps <= 32 u16 maps.
 // num[i] = baseline_i * f (host-computed, same f64 product as the oracle).
 hipError_t launch_fuse_depth(Ctx& c, const uint16_t* disps, int n_maps, size_t np,
