@@ -263,6 +263,49 @@ int sva_cost_fuse_d(void* ctx, const uint8_t* volumes, size_t stride, int n, int
                     int height, int D, int dreal, int dmin, const int32_t* steps,
                     uint8_t* fused);
 
+/* Mixed-baseline Mode S: sva_disparity_sgm_multi* for pairs
+ * of UNEQUAL baselines.  The group has one unit baseline; disparity s = dmin +
+ * d counts major-axis pixels of a pair whose baseline is that unit, and depth
+ * is unit_baseline * f / (d * pixel_size).  Pair i's major-axis baseline is
+ * ratios[i] = (num, den) times the unit (ratios: host [n][2] i32, each in 1..8,
+ * reduced by their gcd on entry): it matches pixel p at disparity s against
+ * p + off_i(t), t = (2*s*num + den) / (2*den) -- s*num/den rounded half up --
+ * with off_i the offset of its step, costs 62 where that pixel leaves the
+ * image, and is visible in the fusion exactly there.  Fusion, aggregation, WTA,
+ * confidence and uniqueness are those of sva_disparity_sgm_multi*, and with
+ * every ratio 1/1 so is every output byte.  The result does not depend on the
+ * order of the pairs.  A pair at 1/1 takes the frame's own cost kernels; every
+ * other pair costs one census launch and one cost_mixed launch.
+ * Refused before anything is launched: null ratios, num or den outside 1..8, a
+ * match distance t(dmin + D - 1) above 65535 (SVA_ERR_INVALID_ARG), and
+ * everything sva_disparity_sgm_multi* refuses (lr_check: SVA_ERR_UNSUPPORTED).
+ * Workspace as for sva_disparity_sgm_multi*, plus two census maps (16 bytes per
+ * pixel). */
+int sva_disparity_sgm_mixed(void* ctx, const uint8_t* ref, const uint8_t* const* others,
+                            const int32_t* steps, const int32_t* ratios, int n, int width,
+                            int height, size_t pitch, const sva_sgm_params* p, int uniqueness,
+                            uint16_t* disp, float* subpix, uint16_t* cost_min,
+                            uint16_t* cost_second);
+int sva_disparity_sgm_mixed_d(void* ctx, const uint8_t* ref, const uint8_t* const* others,
+                              const int32_t* steps, const int32_t* ratios, int n, int width,
+                              int height, size_t pitch, const sva_sgm_params* p, int uniqueness,
+                              uint16_t* disp, float* subpix, uint16_t* cost_min,
+                              uint16_t* cost_second);
+/* The cost stage of one such pair from two device census maps (sva_census_d):
+ * C[(y*W + x)*D + d] = popcount(census_ref(p) ^ census_oth(p + off(t(dmin +
+ * d)))) along the step (sx, sy) at ratio num/den, 62 outside the image, 255 at
+ * d >= dreal.  D native, dreal, dmin and the size limit as for sva_cost_fuse_d;
+ * C must be a multiple of 16, the maps of 8. */
+int sva_cost_mixed_d(void* ctx, const uint64_t* census_ref, const uint64_t* census_oth, int width,
+                     int height, int D, int dreal, int dmin, int sx, int sy, int num, int den,
+                     uint8_t* C);
+/* sva_cost_fuse_d with the visibility rule of §2.2d: volume i belongs to a pair
+ * at ratios[i] = (num, den) (host [n][2] i32, each in 1..8).  All ratios 1/1:
+ * the bytes of sva_cost_fuse_d. */
+int sva_cost_fuse_mixed_d(void* ctx, const uint8_t* volumes, size_t stride, int n, int width,
+                          int height, int D, int dreal, int dmin, const int32_t* steps,
+                          const int32_t* ratios, uint8_t* fused);
+
 /* A batch of device-resident frames of one shape on this context's stream:
  * pair j matches jobs[j].left against jobs[j].right along its own step
  * (params.dir, params.dir_y), and every frame's cost volume then goes through
@@ -653,6 +696,19 @@ int sva_array_depth_mb(void* multi, const uint8_t* const* images, int n_images, 
                        const int32_t* group_start, int n_groups, double f, double pixel_size,
                        int uniqueness, double* depth, uint16_t* maps, uint16_t* cost_min,
                        uint16_t* cost_second);
+/* sva_array_depth_mb for groups of UNEQUAL baselines: group g
+ * runs one sva_disparity_sgm_mixed_d.  unit_baseline: host [n_groups] f64, > 0;
+ * a pair's baseline / unit_baseline[g] must lie within 1e-9 relative of some
+ * num/den with both in 1..8 (the smallest den is taken), and its match
+ * distance must fit 16 bits: SVA_ERR_INVALID_ARG otherwise.  A group's
+ * disparity counts pixels of the unit baseline: depth = unit_baseline[g] * f /
+ * ((double)d * pixel_size).  Everything else as sva_array_depth_mb, which keeps
+ * refusing such groups. */
+int sva_array_depth_mixed(void* multi, const uint8_t* const* images, int n_images, int width,
+                          int height, size_t pitch, const sva_array_pair* pairs, int n_pairs,
+                          const int32_t* group_start, int n_groups, const double* unit_baseline,
+                          double f, double pixel_size, int uniqueness, double* depth,
+                          uint16_t* maps, uint16_t* cost_min, uint16_t* cost_second);
 
 #ifdef __cplusplus
 }

@@ -626,6 +626,86 @@ inline std::vector<std::vector<double>> computeArrayDepthMulti(
     return fr.split(depth);
 }
 
+// ---- mixed-baseline Mode S -----------------------------
+
+// computeDisparityMulti for pairs of UNEQUAL baselines (sva_disparity_sgm_mixed):
+// disparity counts pixels of a pair whose PairStep::k is unit_k, and pair i
+// enters at the ratio steps[i].k / unit_k (num and den in 1..8 once reduced;
+// the library refuses anything else).  Depth: unit_k * pitch * f / (d *
+// pixel_size).
+inline std::vector<uint16_t> computeDisparityMixed(
+    Engine& eng, const ImageView& ref, const std::vector<ImageView>& others,
+    const std::vector<PairStep>& steps, int unit_k, const sva_sgm_params& p, int uniqueness = 0,
+    std::vector<float>* subpix = nullptr, std::vector<uint16_t>* cost_min = nullptr,
+    std::vector<uint16_t>* cost_second = nullptr) {
+    if (others.empty() || others.size() != steps.size())
+        throw Error(SVA_ERR_INVALID_ARG, "computeDisparityMixed: need one step per matched image");
+    if (unit_k < 1) throw Error(SVA_ERR_INVALID_ARG, "computeDisparityMixed: unit_k must be >= 1");
+    std::vector<const uint8_t*> ptrs;
+    std::vector<int32_t> st, ratios;
+    for (size_t i = 0; i < others.size(); i++) {
+        const ImageView& o = others[i];
+        if (o.width != ref.width || o.height != ref.height || o.pitch != ref.pitch)
+            throw Error(SVA_ERR_INVALID_ARG, "computeDisparityMixed: images differ in size");
+        int a = steps[i].k, b = unit_k;
+        while (b) { const int r = a % b; a = b; b = r; }
+        if (a < 1) throw Error(SVA_ERR_INVALID_ARG, "computeDisparityMixed: a step with k = 0");
+        ptrs.push_back(o.data);
+        st.push_back(steps[i].dir);
+        st.push_back(steps[i].dir_y);
+        ratios.push_back(steps[i].k / a);
+        ratios.push_back(unit_k / a);
+    }
+    const size_t np = (size_t)ref.width * ref.height;
+    std::vector<uint16_t> disp(np);
+    float* sp = nullptr;
+    if (subpix && p.subpixel) {
+        subpix->resize(np);
+        sp = subpix->data();
+    }
+    if (cost_min) cost_min->resize(np);
+    if (cost_second) cost_second->resize(np);
+    eng.check(sva_disparity_sgm_mixed(eng.handle(), ref.data, ptrs.data(), st.data(),
+                                      ratios.data(), (int)ptrs.size(), ref.width, ref.height,
+                                      ref.pitch, &p, uniqueness, disp.data(), sp,
+                                      cost_min ? cost_min->data() : nullptr,
+                                      cost_second ? cost_second->data() : nullptr));
+    return disp;
+}
+
+// computeArrayDepthMulti for groups of unequal baselines (sva_array_depth_mixed):
+// every pair of a reference camera, whatever its baseline, in ONE fused volume.
+// unit_k: the PairStep::k that a group's disparity counts pixels of; 0 = each
+// group's largest k (the finest depth resolution).  Each pair's k / unit_k must
+// reduce to num/den in 1..8.
+inline std::vector<std::vector<double>> computeArrayDepthMixed(
+    MultiEngine& m, const std::vector<ImageView>& images, const std::vector<Camera>& cameras,
+    const std::vector<std::array<int, 2>>& pairs, const sva_sgm_params& p, int unit_k = 0,
+    int uniqueness = 0, double pitch = 0.05, std::vector<std::vector<uint16_t>>* maps = nullptr) {
+    if (unit_k < 0) throw Error(SVA_ERR_INVALID_ARG, "computeArrayDepthMixed: unit_k must be >= 0");
+    const detail::ArrayFrame fr = detail::arrayFrame(images, cameras, pairs, p, pitch,
+                                                     "computeArrayDepthMixed");
+    const size_t np = (size_t)fr.W * fr.H;
+    const int ng = (int)fr.refs.size();
+    std::vector<double> unit(ng);
+    for (int g = 0; g < ng; g++) {
+        double u = unit_k * pitch;
+        if (!unit_k)
+            for (int j = fr.group_start[g]; j < fr.group_start[g + 1]; j++)
+                u = std::max(u, fr.ap[j].baseline);
+        unit[g] = u;
+    }
+    std::vector<double> depth(np * ng);
+    std::vector<uint16_t> all(maps ? np * ng : 0);
+    const Camera& c0 = cameras.at(fr.refs[0]);
+    m.check(sva_array_depth_mixed(m.handle(), fr.ptrs.data(), (int)fr.ptrs.size(), fr.W, fr.H,
+                                  fr.pitch, fr.ap.data(), (int)fr.ap.size(), fr.group_start.data(),
+                                  ng, unit.data(), c0.f, c0.pixel_size, uniqueness, depth.data(),
+                                  maps ? all.data() : nullptr, nullptr, nullptr));
+    if (maps) *maps = fr.split(all);
+    return fr.split(depth);
+}
+
 // ---- refinement and 3-D output ----
 // The reference's names and argument meaning; cv::Mat becomes ImageView (u8)
 // or a dense W*H std::vector<double>.  Pixels a routine does not write keep

@@ -68,7 +68,9 @@ EXPORTED = [
     "sva_get_debug", "sva_disparity_sgm_conf", "sva_disparity_sgm_conf_d", "sva_wta_conf_d",
     "sva_fuse_depth_conf", "sva_fuse_depth_conf_d", "sva_disparity_sgm_batch_conf_d",
     "sva_batch_sgm_conf_d", "sva_array_depth_conf", "sva_cost_fuse_d", "sva_disparity_sgm_multi",
-    "sva_disparity_sgm_multi_d", "sva_array_depth_mb",
+    "sva_disparity_sgm_multi_d", "sva_array_depth_mb", "sva_cost_mixed_d",
+    "sva_cost_fuse_mixed_d", "sva_disparity_sgm_mixed", "sva_disparity_sgm_mixed_d",
+    "sva_array_depth_mixed",
 ]
 SVA_FUSE_MIN_COST = 0
 SVA_FUSE_MAX_MARGIN = 1
@@ -244,6 +246,15 @@ def _load() -> ct.CDLL:
                                             P(SgmParams), i32, vp, vp, vp, vp]),
         "sva_array_depth_mb": (i32, [vp, P(vp), i32, i32, i32, sz, P(ArrayPair), i32, P(i32), i32,
                                      dbl, dbl, i32, vp, vp, vp, vp]),
+        "sva_cost_mixed_d": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
+        "sva_cost_fuse_mixed_d": (i32, [vp, vp, sz, i32, i32, i32, i32, i32, i32, P(ct.c_int32),
+                                        P(ct.c_int32), vp]),
+        "sva_disparity_sgm_mixed": (i32, [vp, vp, P(vp), P(ct.c_int32), P(ct.c_int32), i32, i32,
+                                          i32, sz, P(SgmParams), i32, vp, vp, vp, vp]),
+        "sva_disparity_sgm_mixed_d": (i32, [vp, vp, P(vp), P(ct.c_int32), P(ct.c_int32), i32, i32,
+                                            i32, sz, P(SgmParams), i32, vp, vp, vp, vp]),
+        "sva_array_depth_mixed": (i32, [vp, P(vp), i32, i32, i32, sz, P(ArrayPair), i32, P(i32),
+                                        i32, P(dbl), dbl, dbl, i32, vp, vp, vp, vp]),
         "sva_resize_linear_f64_d": (i32, [vp, vp, i32, i32, vp, i32, i32]),
         "sva_resize_linear_f64": (i32, [vp, vp, i32, i32, vp, i32, i32]),
         "sva_ref_error_d": (i32, [vp, vp, i32, i32, vp, i32, i32, ct.c_double, vp]),
@@ -305,6 +316,13 @@ def _ptr(a) -> int | None:
     if isinstance(a, np.ndarray):
         return a.ctypes.data
     return a.data_ptr()  # torch tensor
+
+
+def _i32_pairs(pairs):
+    """A list of (a, b) as a C [n][2] i32 array; None stays a null pointer."""
+    if pairs is None:
+        return None
+    return (ct.c_int32 * max(2, 2 * len(pairs)))(*[int(v) for s in pairs for v in s])
 
 
 class Context:
@@ -469,6 +487,53 @@ class Context:
         st = (ct.c_int32 * max(2, 2 * len(steps)))(*[int(v) for s in steps for v in s])
         self._chk(lib.sva_cost_fuse_d(self.h, _ptr(volumes), stride, len(steps), W, H, D, dreal,
                                       dmin, st, _ptr(fused)))
+
+    # -- mixed-baseline Mode S: pairs of unequal baselines in one volume
+    def disparity_sgm_mixed(self, ref: np.ndarray, others, steps, ratios, params: SgmParams,
+                            uniqueness: int = 0):
+        """(disp, sub, cost_min, cost_second): sva_disparity_sgm_mixed.  As
+        disparity_sgm_multi, with ratios: n (num, den) -- pair i's major-axis
+        baseline over the group's unit baseline, each in 1..8 (None = a null
+        pointer, which the library refuses)."""
+        ref = np.ascontiguousarray(ref, dtype=np.uint8)
+        oth = [np.ascontiguousarray(a, dtype=np.uint8) for a in others]
+        assert len(oth) == len(steps) and all(a.shape == ref.shape for a in oth)
+        H, W = ref.shape
+        ptrs = (ct.c_void_p * max(1, len(oth)))(*[_ptr(a) for a in oth])
+        disp = np.zeros((H, W), np.uint16)
+        sub = np.zeros((H, W), np.float32) if params.subpixel else None
+        cmin = np.zeros((H, W), np.uint16)
+        csec = np.zeros((H, W), np.uint16)
+        self._chk(lib.sva_disparity_sgm_mixed(self.h, _ptr(ref), ptrs, _i32_pairs(steps),
+                                              _i32_pairs(ratios), len(oth), W, H, W,
+                                              ct.byref(params), int(uniqueness), _ptr(disp),
+                                              _ptr(sub), _ptr(cmin), _ptr(csec)))
+        return disp, sub, cmin, csec
+
+    def disparity_sgm_mixed_d(self, ref, others, steps, ratios, W, H, pitch, params, uniqueness,
+                              disp, sub=None, cost_min=None, cost_second=None):
+        """Device pointers; others: n image pointers, steps: n (dir, dir_y),
+        ratios: n (num, den)."""
+        ptrs = (ct.c_void_p * max(1, len(others)))(*[_ptr(a) for a in others])
+        self._chk(lib.sva_disparity_sgm_mixed_d(self.h, _ptr(ref), ptrs, _i32_pairs(steps),
+                                                _i32_pairs(ratios), len(others), W, H, pitch,
+                                                ct.byref(params), int(uniqueness), _ptr(disp),
+                                                _ptr(sub), _ptr(cost_min), _ptr(cost_second)))
+
+    def cost_mixed_d(self, census_ref, census_oth, W, H, D, dreal, dmin, step, ratio, C):
+        """sva_cost_mixed_d: the cost volume [H][W][D] u8 of one pair at ratio =
+        (num, den) of the unit baseline along step = (sx, sy), from two device
+        census maps."""
+        self._chk(lib.sva_cost_mixed_d(self.h, _ptr(census_ref), _ptr(census_oth), W, H, D, dreal,
+                                       dmin, int(step[0]), int(step[1]), int(ratio[0]),
+                                       int(ratio[1]), _ptr(C)))
+
+    def cost_fuse_mixed_d(self, volumes, stride, steps, ratios, W, H, D, dreal, dmin, fused):
+        """sva_cost_fuse_mixed_d: cost_fuse_d with volume i visible by the rule of
+        a pair at ratios[i] = (num, den)."""
+        self._chk(lib.sva_cost_fuse_mixed_d(self.h, _ptr(volumes), stride, len(steps), W, H, D,
+                                            dreal, dmin, _i32_pairs(steps), _i32_pairs(ratios),
+                                            _ptr(fused)))
 
     def wta_conf_d(self, S, W, H, params, uniqueness, disp, sub=None, cost_min=None,
                    cost_second=None):
@@ -882,6 +947,30 @@ class Multi:
         self._chk(lib.sva_array_depth_mb(self.h, ptrs, len(imgs), W, H, W, jp, len(pairs), gs, G,
                                          f, pixel_size, int(uniqueness), _ptr(depth), _ptr(maps),
                                          _ptr(cmin), _ptr(csec)))
+        return depth, maps, cmin, csec
+
+    def array_depth_mixed(self, images, pairs, group_start, unit_baseline, f, pixel_size,
+                          uniqueness=0, want_maps=False, want_costs=False):
+        """sva_array_depth_mixed: array_depth_mb for groups of unequal baselines.
+        unit_baseline: one per group; each pair's baseline must be num/den (1..8
+        each) of it, and the group's depth is unit_baseline * f / (d * pixel_size)."""
+        imgs = [np.ascontiguousarray(a, dtype=np.uint8) for a in images]
+        H, W = imgs[0].shape
+        ptrs = (ct.c_void_p * len(imgs))(*[_ptr(a) for a in imgs])
+        jp = (ArrayPair * len(pairs))()
+        for i, (a, b, p, base) in enumerate(pairs):
+            jp[i] = ArrayPair(a, b, p, base)
+        gs = (ct.c_int32 * len(group_start))(*group_start)
+        G = len(group_start) - 1
+        assert len(unit_baseline) == G
+        ub = (ct.c_double * G)(*[float(v) for v in unit_baseline])
+        depth = np.zeros((G, H, W), np.float64)
+        maps = np.zeros((G, H, W), np.uint16) if want_maps else None
+        cmin = np.zeros((G, H, W), np.uint16) if want_costs else None
+        csec = np.zeros((G, H, W), np.uint16) if want_costs else None
+        self._chk(lib.sva_array_depth_mixed(self.h, ptrs, len(imgs), W, H, W, jp, len(pairs), gs,
+                                            G, ub, f, pixel_size, int(uniqueness), _ptr(depth),
+                                            _ptr(maps), _ptr(cmin), _ptr(csec)))
         return depth, maps, cmin, csec
 
     def array_depth(self, images, pairs, group_start, f, pixel_size, want_maps=False):

@@ -25,7 +25,11 @@
 // HBM bytes per disparity: N read + 1 written.  VALU per lane: about 45 per
 // pair (masks, SWAR adds, lim) and about 130 for the 16 divisions; against
 // 16 * (N + 1) bytes that stays memory-bound from N = 2 up.
-#include "cost_fuse_math.h"
+//
+// Mixed-baseline groups (§2.2d) run cost_fuse_mixed_kernel: the same text
+// (cost_fuse_kernel.inc) with the visibility limit of a pair at a rational
+// baseline ratio (mixed_lim).
+#include "cost_mixed_math.h"
 #include "sva_device.h"
 #include "sva_internal.h"
 
@@ -39,79 +43,30 @@ struct FuseSteps {
     short sx[32], sy[32];
 };
 
-// NC = D / 16 lanes per pixel; NM = pair-count class (n <= NM).
-template <int NC, int NM>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void cost_fuse_kernel(
-    const uint8_t* __restrict__ volumes, size_t stride, int n, int W, int H, unsigned nlanes,
-    int dmin, int dreal, FuseSteps steps, uint8_t* __restrict__ fused) {
-    constexpr int D = NC * 16;
-    __shared__ unsigned magic[33];
-    if (threadIdx.x < 33) magic[threadIdx.x] = mb::mean_magic((int)threadIdx.x);
-    __syncthreads();
-    const unsigned lane = blockIdx.x * 256u + threadIdx.x;
-    if (lane >= nlanes) return;
-    const unsigned pix = lane / NC;
-    const int c = (int)(lane - pix * NC);
-    const int y = (int)(pix / (unsigned)W), x = (int)(pix - (unsigned)y * (unsigned)W);
-    const int d0 = 16 * c;
-    const unsigned off = lane * 16u;   // < W*H*D < 2^32: inside one volume
+// The pairs' baseline ratios of the mixed instance, reduced.
+struct FuseRatios {
+    unsigned char num[32], den[32];
+};
 
-    unsigned E[4] = {0, 0, 0, 0}, O[4] = {0, 0, 0, 0}, cnt[4] = {0, 0, 0, 0};
-    auto load4 = [&](int i0, v4u (&v)[4]) {
-#pragma unroll
-        for (int j = 0; j < 4; j++)
-            if (i0 + j < n) {   // uniform
-                // 64-bit and uniform; pinned to a scalar pair so that the load
-                // is "scalar base + 32-bit lane offset", not a 64-bit add per lane
-                uint64_t base = (uint64_t)volumes + (uint64_t)(i0 + j) * stride;
-                asm("" : "+s"(base));
-                v[j] = __builtin_nontemporal_load((gv4u*)(base + off));
-            }
-    };
-    auto sum4 = [&](int i0, const v4u (&v)[4]) {
-#pragma unroll
-        for (int j = 0; j < 4; j++)
-            if (i0 + j < n) {   // uniform
-                const int lim = mb::pair_lim(x, y, W, H, steps.sx[i0 + j], steps.sy[i0 + j], dmin, D);
-                const int k = lim - d0;   // visible bytes of this lane: the first k
-#pragma unroll
-                for (int q = 0; q < 4; q++) {
-                    const int kq = k - 4 * q;
-                    const unsigned mask =
-                        kq >= 4 ? 0xffffffffu : (kq <= 0 ? 0u : (1u << (8 * kq)) - 1u);
-                    const unsigned w = v[j][q] & mask;
-                    E[q] += w & 0x00ff00ffu;
-                    O[q] += (w >> 8) & 0x00ff00ffu;
-                    cnt[q] += mask & 0x04040404u;
-                }
-            }
-    };
-    v4u cur[4] = {}, nxt[4] = {};
-    load4(0, cur);
-#pragma unroll
-    for (int i0 = 0; i0 < NM; i0 += 4) {
-        if (i0 + 4 < NM && i0 + 4 < n) load4(i0 + 4, nxt);
-        if (i0 < n) sum4(i0, cur);
-#pragma unroll
-        for (int j = 0; j < 4; j++) cur[j] = nxt[j];
-    }
+// cost_fuse_kernel<NC, NM>: equal baselines, a pair is visible at d < pair_lim.
+#define SVA_FUSE_KERNEL cost_fuse_kernel
+#define SVA_FUSE_RATIOS
+#define SVA_FUSE_LIM(i) mb::pair_lim(x, y, W, H, steps.sx[i], steps.sy[i], dmin, D)
+#include "cost_fuse_kernel.inc"
+#undef SVA_FUSE_KERNEL
+#undef SVA_FUSE_RATIOS
+#undef SVA_FUSE_LIM
 
-    unsigned out[4];
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-        unsigned w = 0;
-#pragma unroll
-        for (int b = 0; b < 4; b++) {
-            const unsigned n4 = (cnt[q] >> (8 * b)) & 0xffu;   // 4 * n = the magic's LDS offset
-            const unsigned s = ((b & 1 ? O[q] : E[q]) >> (16 * (b >> 1))) & 0xffffu;
-            const unsigned mg = *(const unsigned*)((const char*)magic + n4);
-            const unsigned r = n4 ? mb::mean_round(2u * s + (n4 >> 2), mg) : 62u;
-            w |= r << (8 * b);
-        }
-        out[q] = w | pad_bytes(d0 + 4 * q, dreal);
-    }
-    *(v4u*)(fused + off) = (v4u){out[0], out[1], out[2], out[3]};
-}
+// cost_fuse_mixed_kernel<NC, NM>: pair i at ratios.num[i] / ratios.den[i] of
+// the unit baseline, visible at d < mixed_lim (§2.2d).
+#define SVA_FUSE_KERNEL cost_fuse_mixed_kernel
+#define SVA_FUSE_RATIOS FuseRatios ratios,
+#define SVA_FUSE_LIM(i) \
+    mb::mixed_lim(x, y, W, H, steps.sx[i], steps.sy[i], ratios.num[i], ratios.den[i], dmin, D)
+#include "cost_fuse_kernel.inc"
+#undef SVA_FUSE_KERNEL
+#undef SVA_FUSE_RATIOS
+#undef SVA_FUSE_LIM
 
 }  // namespace
 
@@ -131,6 +86,49 @@ hipError_t launch_cost_fuse(Ctx& c, const uint8_t* volumes, size_t stride, int n
 #define SVA_CF(NC, NM)                                                                          \
     hipLaunchKernelGGL((cost_fuse_kernel<NC, NM>), grid, dim3(256), 0, c.stream, volumes, stride, \
                        n, W, H, nlanes, dmin, dreal, k, fused)
+#define SVA_CF_N(NC)                      \
+    do {                                  \
+        if (n <= 4) SVA_CF(NC, 4);        \
+        else if (n <= 8) SVA_CF(NC, 8);   \
+        else if (n <= 16) SVA_CF(NC, 16); \
+        else SVA_CF(NC, 32);              \
+    } while (0)
+    switch (nc) {
+        case 4: SVA_CF_N(4); break;
+        case 8: SVA_CF_N(8); break;
+        case 12: SVA_CF_N(12); break;
+        case 16: SVA_CF_N(16); break;
+        default: return hipErrorInvalidValue;
+    }
+#undef SVA_CF_N
+#undef SVA_CF
+    return hipGetLastError();
+}
+
+// The mixed instance (§2.2d): ratios[i] = (num, den) of pair i, each in 1..8.
+hipError_t launch_cost_fuse_mixed(Ctx& c, const uint8_t* volumes, size_t stride, int n, int W,
+                                  int H, int D, int dreal, int dmin, const int32_t* steps,
+                                  const int32_t* ratios, uint8_t* fused) {
+    if (n < 1 || n > 32 || !paths_supported(D) || !ratios) return hipErrorInvalidValue;
+    if (dreal <= 0) dreal = D;
+    FuseSteps k{};
+    FuseRatios r{};
+    for (int i = 0; i < n; i++) {
+        const int num = ratios[2 * i], den = ratios[2 * i + 1];
+        if (num < 1 || num > mb::kMaxRatio || den < 1 || den > mb::kMaxRatio)
+            return hipErrorInvalidValue;
+        k.sx[i] = (short)steps[2 * i];
+        k.sy[i] = (short)steps[2 * i + 1];
+        r.num[i] = (unsigned char)num;
+        r.den[i] = (unsigned char)den;
+    }
+    ScopedKernelTimer t(c, "cost_fuse");
+    const int nc = D / 16;
+    const unsigned nlanes = (unsigned)((size_t)W * H * nc);   // W*H*D < 2^32 (check_sgm)
+    const dim3 grid((nlanes + 255u) / 256u);
+#define SVA_CF(NC, NM)                                                                       \
+    hipLaunchKernelGGL((cost_fuse_mixed_kernel<NC, NM>), grid, dim3(256), 0, c.stream, volumes, \
+                       stride, n, W, H, nlanes, dmin, dreal, k, r, fused)
 #define SVA_CF_N(NC)                      \
     do {                                  \
         if (n <= 4) SVA_CF(NC, 4);        \

@@ -14,7 +14,8 @@
 // the confidence forms, whose cost planes are gathered like the maps); there
 // is no CPU path.  sva_array_depth_mb shards GROUPS instead (one
 // sva_disparity_sgm_multi_d per reference camera) through the
-// same plan, slots and gather (run_jobs).
+// same plan, slots and gather (run_jobs); sva_array_depth_mixed is that route
+// with sva_disparity_sgm_mixed_d per group (§2.2d).
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
@@ -920,16 +921,35 @@ int array_depth(void* mp, const uint8_t* const* images, int n_images, int W, int
     return SVA_OK;
 }
 
+// The ratio num/den (both in 1..8) that baseline / unit equals within 1e-9
+// relative: den ascending, the first hit (so the reduced form).  False if none.
+bool baseline_ratio(double baseline, double unit, int32_t* num, int32_t* den) {
+    if (!(unit > 0) || !(baseline > 0)) return false;
+    const double r = baseline / unit;
+    for (int d = 1; d <= 8; d++)
+        for (int n = 1; n <= 8; n++)
+            if (std::fabs(r * d - n) <= 1e-9 * n) {
+                *num = n;
+                *den = d;
+                return true;
+            }
+    return false;
+}
+
 // sva_array_depth_mb: the multi-baseline array route.  The
 // job is the GROUP: group g's pairs go through one sva_disparity_sgm_multi_d
 // on device g mod n_devices, and one map per group is gathered and turned
-// into depth.
+// into depth.  unit_baseline set: sva_array_depth_mixed (§2.2d) -- a group's
+// baselines are rational multiples of unit_baseline[g], its call is
+// sva_disparity_sgm_mixed_d, and its depth scale is the unit baseline.
 int array_depth_mb(void* mp, const uint8_t* const* images, int n_images, int W, int H, size_t pitch,
                    const sva_array_pair* pairs, int n_pairs, const int32_t* group_start,
-                   int n_groups, double f, double pixel_size, int uniqueness, double* depth,
-                   uint16_t* maps, uint16_t* cost_min, uint16_t* cost_second) {
+                   int n_groups, double f, double pixel_size, int uniqueness,
+                   const double* unit_baseline, bool mixed, double* depth, uint16_t* maps,
+                   uint16_t* cost_min, uint16_t* cost_second) {
     Multi* m = as_multi(mp);
     if (!m) return SVA_ERR_INVALID_ARG;
+    if (mixed && !unit_baseline) return m->fail(SVA_ERR_INVALID_ARG, "null unit_baseline");
     if (uniqueness < 0 || uniqueness > 100)
         return m->fail(SVA_ERR_INVALID_ARG, "uniqueness must be 0..100");
     if (!images || n_images <= 0 || !pairs || n_pairs <= 0 || !group_start || n_groups <= 0 ||
@@ -961,11 +981,26 @@ int array_depth_mb(void* mp, const uint8_t* const* images, int n_images, int W, 
                 return m->fail(SVA_ERR_INVALID_ARG, "the pairs of group " + std::to_string(g) +
                                                         " must share D, dmin, P1, P2 and invalid");
             const double big = std::max(std::fabs(q.baseline), std::fabs(a.baseline));
-            if (!(std::fabs(q.baseline - a.baseline) <= 1e-9 * big))
+            if (!mixed && !(std::fabs(q.baseline - a.baseline) <= 1e-9 * big))
                 return m->fail(SVA_ERR_INVALID_ARG, "the pairs of group " + std::to_string(g) +
                                                         " have different major-axis baselines");
         }
     }
+    // mixed: every pair's baseline as a ratio of its group's unit
+    std::vector<int32_t> ratio(mixed ? 2 * (size_t)n_pairs : 0);
+    if (mixed)
+        for (int g = 0; g < n_groups; g++)
+            for (int j = group_start[g]; j < group_start[g + 1]; j++) {
+                int32_t* r = &ratio[2 * (size_t)j];
+                if (!baseline_ratio(pairs[j].baseline, unit_baseline[g], r, r + 1))
+                    return m->fail(SVA_ERR_INVALID_ARG,
+                                   "the baseline of pair " + std::to_string(j) +
+                                       " is no num/den (1..8 each) of its group's unit baseline");
+                const sva_sgm_params& q = pairs[j].params;
+                if ((2ll * (q.dmin + q.D - 1) * r[0] + r[1]) / (2 * r[1]) > 65535)
+                    return m->fail(SVA_ERR_INVALID_ARG, "the match distance of pair " +
+                                                            std::to_string(j) + " exceeds 16 bits");
+            }
     ev_reset(m);
     const size_t np = (size_t)W * H;
     Plan P;
@@ -1015,9 +1050,13 @@ int array_depth_mb(void* mp, const uint8_t* const* images, int n_images, int W, 
     int st = run_jobs(
         m, P, waits, W, H, maps0, nullptr, std::vector<char>(n_groups, 0), &cp,
         [&](int g, void* cx, uint16_t* od, float*, uint16_t* omin, uint16_t* osec) {
-            return sva_disparity_sgm_multi_d(cx, ref[g], others[g].data(), steps[g].data(),
-                                             (int)others[g].size(), W, H, W, &prm[g], uniqueness,
-                                             od, nullptr, omin, osec);
+            const int n = (int)others[g].size();
+            return mixed ? sva_disparity_sgm_mixed_d(cx, ref[g], others[g].data(), steps[g].data(),
+                                                     &ratio[2 * (size_t)group_start[g]], n, W, H, W,
+                                                     &prm[g], uniqueness, od, nullptr, omin, osec)
+                         : sva_disparity_sgm_multi_d(cx, ref[g], others[g].data(), steps[g].data(),
+                                                     n, W, H, W, &prm[g], uniqueness, od, nullptr,
+                                                     omin, osec);
         },
         "group");
     if (st) return st;
@@ -1031,7 +1070,8 @@ int array_depth_mb(void* mp, const uint8_t* const* images, int n_images, int W, 
     double* depth0 = (double*)m->depth0.ptr;
     for (int g = 0; g < n_groups; g++) {
         const sva_array_pair& a = pairs[group_start[g]];
-        st = sva_fuse_depth_d(m->ctx[0], maps0 + (size_t)g * np, 1, W, H, &a.baseline, f,
+        st = sva_fuse_depth_d(m->ctx[0], maps0 + (size_t)g * np, 1, W, H,
+                              mixed ? &unit_baseline[g] : &a.baseline, f,
                               pixel_size, a.params.invalid, depth0 + (size_t)g * np, nullptr);
         if (st) return m->ctx_fail(st, m->ctx[0], "depth");
         if ((st = stream_after(m, 0, m->st(0, 0), m->down[0]))) return st;
@@ -1101,7 +1141,18 @@ int sva_array_depth_mb(void* mp, const uint8_t* const* images, int n_images, int
                        int uniqueness, double* depth, uint16_t* maps, uint16_t* cost_min,
                        uint16_t* cost_second) {
     return array_depth_mb(mp, images, n_images, W, H, pitch, pairs, n_pairs, group_start, n_groups,
-                          f, pixel_size, uniqueness, depth, maps, cost_min, cost_second);
+                          f, pixel_size, uniqueness, nullptr, false, depth, maps, cost_min,
+                          cost_second);
+}
+
+int sva_array_depth_mixed(void* mp, const uint8_t* const* images, int n_images, int W, int H,
+                          size_t pitch, const sva_array_pair* pairs, int n_pairs,
+                          const int32_t* group_start, int n_groups, const double* unit_baseline,
+                          double f, double pixel_size, int uniqueness, double* depth,
+                          uint16_t* maps, uint16_t* cost_min, uint16_t* cost_second) {
+    return array_depth_mb(mp, images, n_images, W, H, pitch, pairs, n_pairs, group_start, n_groups,
+                          f, pixel_size, uniqueness, unit_baseline, true, depth, maps, cost_min,
+                          cost_second);
 }
 
 }  // extern "C"

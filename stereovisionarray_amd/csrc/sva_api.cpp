@@ -15,6 +15,7 @@
 #include <thread>
 #include <vector>
 
+#include "cost_mixed_math.h"
 #include "sva_internal.h"
 #include "sva_tuning.h"
 
@@ -1051,88 +1052,117 @@ int check_sgm_multi(Ctx* c, const uint8_t* ref, const uint8_t* const* others, co
     return SVA_OK;
 }
 
-// Multi-baseline Mode S on device buffers: pair i's cost
-// volume (ref against others[i] along steps[i]) into slot i of the cost
+// The baseline ratios of the mixed entry points: n (num, den)
+// pairs in 1..8, reduced by their gcd into red[2n].  dmin >= 0 and D > 0 set
+// the distance limit t(dmin + D - 1) <= 65535 (D = 0: no limit to check).
+int check_ratios(Ctx* c, const int32_t* ratios, int n, int dmin, int D, int32_t* red) {
+    if (!ratios) return fail(c, SVA_ERR_INVALID_ARG, "null ratios");
+    for (int i = 0; i < n; i++) {
+        int num = ratios[2 * i], den = ratios[2 * i + 1];
+        if (num < 1 || num > mb::kMaxRatio || den < 1 || den > mb::kMaxRatio)
+            return fail(c, SVA_ERR_INVALID_ARG, "every ratio needs num and den in 1..8");
+        int a = num, b = den;
+        while (b) { const int r = a % b; a = b; b = r; }
+        red[2 * i] = num /= a;
+        red[2 * i + 1] = den /= a;
+        if (D > 0 && mb::mixed_distance(dmin + D - 1, num, den) > 65535)
+            return fail(c, SVA_ERR_INVALID_ARG,
+                        "the match distance (dmin + D - 1) * num / den must fit 16 bits");
+    }
+    return SVA_OK;
+}
+
+// Multi-baseline Mode S on device buffers: pair i's
+// cost volume (ref against others[i] along steps[i]) into slot i of the cost
 // workspace, cost_fuse into slot n, then the frame's aggregation and WTA on the
-// fused volume.  The workspace holds n + 1 volumes.
+// fused volume.  The workspace holds n + 1 volumes.  ratios: null (equal
+// baselines) or n reduced (num, den); a pair at 1/1 takes the frame's own cost
+// route, every other pair census + cost_mixed.
 int run_sgm_multi_device(Ctx* c, const uint8_t* ref, const uint8_t* const* others,
-                         const int32_t* steps, int n, int W, int H, size_t pitch,
-                         const sva_sgm_params* p, uint16_t* disp, float* sub, const ConfOut* cf) {
+                         const int32_t* steps, const int32_t* ratios, int n, int W, int H,
+                         size_t pitch, const sva_sgm_params* p, uint16_t* disp, float* sub,
+                         const ConfOut* cf) {
     const int Dp = padded_D(p->D);
     const size_t np = (size_t)W * H, nv = np * (size_t)Dp;
+    auto unit = [&](int i) { return !ratios || (ratios[2 * i] == 1 && ratios[2 * i + 1] == 1); };
+    bool mixed = false;
+    for (int i = 0; i < n; i++) mixed = mixed || !unit(i);
     SVA_HIP(c, c->cost.ensure(nv * ((size_t)n + 1)), "cost workspace");
     uint8_t* C = (uint8_t*)c->cost.ptr;
     // The pairs' cost kernels run one after another on the context stream: each
     // fills the chip, and spreading them over side streams measured no faster
     // (DESIGN.md §4.19).
     uint64_t *cl = nullptr, *cr = nullptr;
+    auto census_maps = [&]() -> hipError_t {
+        if (cl) return hipSuccess;
+        hipError_t e = c->census_l.ensure(np * 8);
+        if (e == hipSuccess) e = c->census_r.ensure(np * 8);
+        cl = (uint64_t*)c->census_l.ptr;
+        cr = (uint64_t*)c->census_r.ptr;
+        return e;
+    };
     for (int i = 0; i < n; i++) {
+        if (!unit(i)) continue;
         const int sx = steps[2 * i], sy = steps[2 * i + 1];
         const CostRoute route = cost_route(Dp, sx, sy);
-        if (route == CostRoute::Split && !cl) {
-            SVA_HIP(c, c->census_l.ensure(np * 8), "census workspace");
-            SVA_HIP(c, c->census_r.ensure(np * 8), "census workspace");
-            cl = (uint64_t*)c->census_l.ptr;
-            cr = (uint64_t*)c->census_r.ptr;
-        }
+        if (route == CostRoute::Split) SVA_HIP(c, census_maps(), "census workspace");
         const char* what = "cost launch";
         const hipError_t e = form_cost(*c, route, ref, others[i], W, H, pitch, Dp, p, sx, sy,
                                        C + (size_t)i * nv, cl, cr, true, &what);
         if (e != hipSuccess) return hip_fail(c, e, what);
     }
     uint8_t* Cf = C + (size_t)n * nv;
-    SVA_HIP(c, launch_cost_fuse(*c, C, nv, n, W, H, Dp, p->D, p->dmin, steps, Cf), "fuse launch");
+    if (!mixed) {
+        SVA_HIP(c, launch_cost_fuse(*c, C, nv, n, W, H, Dp, p->D, p->dmin, steps, Cf),
+                "fuse launch");
+        return paths_wta(c, Cf, W, H, p, Dp, disp, sub, cf);
+    }
+    // The other pairs, after every unit pair: a split-route unit pair fills both
+    // census maps itself, so the reference map that the mixed pairs share is
+    // formed only once none of those is left to run (one stream: in order).
+    SVA_HIP(c, census_maps(), "census workspace");
+    SVA_HIP(c, launch_census(*c, ref, W, H, pitch, cl), "census launch");
+    for (int i = 0; i < n; i++) {
+        if (unit(i)) continue;
+        SVA_HIP(c, launch_census(*c, others[i], W, H, pitch, cr), "census launch");
+        SVA_HIP(c, launch_cost_mixed(*c, cl, cr, W, H, Dp, p->dmin, steps[2 * i], steps[2 * i + 1],
+                                     ratios[2 * i], ratios[2 * i + 1], C + (size_t)i * nv, p->D),
+                "cost launch");
+    }
+    SVA_HIP(c, launch_cost_fuse_mixed(*c, C, nv, n, W, H, Dp, p->D, p->dmin, steps, ratios, Cf),
+            "fuse launch");
     return paths_wta(c, Cf, W, H, p, Dp, disp, sub, cf);
 }
-}  // namespace
 
-int sva_cost_fuse_d(void* ctx, const uint8_t* volumes, size_t stride, int n, int W, int H, int D,
-                    int dreal, int dmin, const int32_t* steps, uint8_t* fused) {
-    Ctx* c = as_ctx(ctx);
-    SVA_CHECK_CTX(c);
-    int s;
-    if ((s = check_steps(c, steps, n))) return s;
-    if (!volumes || !fused) return fail(c, SVA_ERR_INVALID_ARG, "null volume");
-    if (W <= 0 || H <= 0) return fail(c, SVA_ERR_INVALID_ARG, "image size must be positive");
-    if (!paths_supported(D))
-        return fail(c, SVA_ERR_UNSUPPORTED, "stage entry points take D in {64,128,192,256}");
-    if (dreal < 1 || dreal > D) return fail(c, SVA_ERR_INVALID_ARG, "dreal must be 1..D");
-    if (dmin < 0 || dmin + D > 65535)
-        return fail(c, SVA_ERR_INVALID_ARG, "dmin >= 0 and dmin + D must fit the u16 disparity map");
-    if ((unsigned long long)W * (unsigned long long)H * (unsigned)D >= (1ull << 32))
-        return fail(c, SVA_ERR_UNSUPPORTED, "W*H*D must be < 2^32 (32-bit volume offsets)");
-    // one dwordx4 per lane and volume
-    if (((uintptr_t)volumes | (uintptr_t)fused | stride) & 15)
-        return fail(c, SVA_ERR_INVALID_ARG, "volumes, stride and fused must be 16-byte aligned");
-    if (n > 1 && stride < (size_t)W * H * (size_t)D)
-        return fail(c, SVA_ERR_INVALID_ARG, "stride smaller than one volume");
-    SVA_HIP(c, launch_cost_fuse(*c, volumes, stride, n, W, H, D, dreal, dmin, steps, fused),
-            "fuse launch");
-    return SVA_OK;
-}
-
-int sva_disparity_sgm_multi_d(void* ctx, const uint8_t* ref, const uint8_t* const* others,
-                              const int32_t* steps, int n, int W, int H, size_t pitch,
-                              const sva_sgm_params* p, int uniqueness, uint16_t* disp, float* sub,
-                              uint16_t* cost_min, uint16_t* cost_second) {
-    Ctx* c = as_ctx(ctx);
-    SVA_CHECK_CTX(c);
-    if (int s = check_sgm_multi(c, ref, others, steps, n, W, H, pitch, p, uniqueness, disp))
-        return s;
-    const ConfOut cf{cost_min, cost_second, uniqueness, p->invalid};
-    const bool conf = cost_min || cost_second || uniqueness;
-    return run_sgm_multi_device(c, ref, others, steps, n, W, H, pitch, p, disp,
-                                p->subpixel ? sub : nullptr, conf ? &cf : nullptr);
-}
-
-int sva_disparity_sgm_multi(void* ctx, const uint8_t* ref, const uint8_t* const* others,
-                            const int32_t* steps, int n, int W, int H, size_t pitch,
-                            const sva_sgm_params* p, int uniqueness, uint16_t* disp, float* sub,
-                            uint16_t* cost_min, uint16_t* cost_second) {
+// sva_disparity_sgm_multi_d (mixed false: ratios unused) and
+// sva_disparity_sgm_mixed_d (mixed true: ratios checked and reduced).
+int sgm_multi_d(void* ctx, const uint8_t* ref, const uint8_t* const* others, const int32_t* steps,
+                const int32_t* ratios, bool mixed, int n, int W, int H, size_t pitch,
+                const sva_sgm_params* p, int uniqueness, uint16_t* disp, float* sub,
+                uint16_t* cost_min, uint16_t* cost_second) {
     Ctx* c = as_ctx(ctx);
     SVA_CHECK_CTX(c);
     int s;
     if ((s = check_sgm_multi(c, ref, others, steps, n, W, H, pitch, p, uniqueness, disp))) return s;
+    int32_t red[64];
+    if (mixed && (s = check_ratios(c, ratios, n, p->dmin, p->D, red))) return s;
+    const ConfOut cf{cost_min, cost_second, uniqueness, p->invalid};
+    const bool conf = cost_min || cost_second || uniqueness;
+    return run_sgm_multi_device(c, ref, others, steps, mixed ? red : nullptr, n, W, H, pitch, p,
+                                disp, p->subpixel ? sub : nullptr, conf ? &cf : nullptr);
+}
+
+// The same from host images: sva_disparity_sgm_multi and sva_disparity_sgm_mixed.
+int sgm_multi_host(void* ctx, const uint8_t* ref, const uint8_t* const* others,
+                   const int32_t* steps, const int32_t* ratios, bool mixed, int n, int W, int H,
+                   size_t pitch, const sva_sgm_params* p, int uniqueness, uint16_t* disp,
+                   float* sub, uint16_t* cost_min, uint16_t* cost_second) {
+    Ctx* c = as_ctx(ctx);
+    SVA_CHECK_CTX(c);
+    int s;
+    if ((s = check_sgm_multi(c, ref, others, steps, n, W, H, pitch, p, uniqueness, disp))) return s;
+    int32_t red[64];
+    if (mixed && (s = check_ratios(c, ratios, n, p->dmin, p->D, red))) return s;
     const bool want_sub = p->subpixel && sub;
     const size_t np = (size_t)W * H;
     Staging g{c};
@@ -1153,14 +1183,116 @@ int sva_disparity_sgm_multi(void* ctx, const uint8_t* ref, const uint8_t* const*
     const ConfOut cf{cost_min ? dc : nullptr, cost_second ? dc + np : nullptr, uniqueness,
                      p->invalid};
     const bool conf = cost_min || cost_second || uniqueness;
-    if ((s = run_sgm_multi_device(c, dref, dptr, steps, n, W, H, W, p, dd, ds,
-                                  conf ? &cf : nullptr)))
+    if ((s = run_sgm_multi_device(c, dref, dptr, steps, mixed ? red : nullptr, n, W, H, W, p, dd,
+                                  ds, conf ? &cf : nullptr)))
         return s;
     g.down(disp, dd, np * 2);
     if (want_sub) g.down(sub, ds, np * 4);
     g.down(cost_min, cf.cost_min, np * 2);
     g.down(cost_second, cf.cost_second, np * 2);
     return g.sync();
+}
+
+// The size rules shared by sva_cost_fuse_d, sva_cost_fuse_mixed_d and
+// sva_cost_mixed_d: a native-D volume with 32-bit offsets.
+int check_stage_volume(Ctx* c, int W, int H, int D, int dreal, int dmin) {
+    if (W <= 0 || H <= 0) return fail(c, SVA_ERR_INVALID_ARG, "image size must be positive");
+    if (!paths_supported(D))
+        return fail(c, SVA_ERR_UNSUPPORTED, "stage entry points take D in {64,128,192,256}");
+    if (dreal < 1 || dreal > D) return fail(c, SVA_ERR_INVALID_ARG, "dreal must be 1..D");
+    if (dmin < 0 || dmin + D > 65535)
+        return fail(c, SVA_ERR_INVALID_ARG, "dmin >= 0 and dmin + D must fit the u16 disparity map");
+    if ((unsigned long long)W * (unsigned long long)H * (unsigned)D >= (1ull << 32))
+        return fail(c, SVA_ERR_UNSUPPORTED, "W*H*D must be < 2^32 (32-bit volume offsets)");
+    return SVA_OK;
+}
+
+// sva_cost_fuse_d (ratios null, mixed false) and sva_cost_fuse_mixed_d.
+int cost_fuse_d(void* ctx, const uint8_t* volumes, size_t stride, int n, int W, int H, int D,
+                int dreal, int dmin, const int32_t* steps, const int32_t* ratios, bool mixed,
+                uint8_t* fused) {
+    Ctx* c = as_ctx(ctx);
+    SVA_CHECK_CTX(c);
+    int s;
+    if ((s = check_steps(c, steps, n))) return s;
+    if (!volumes || !fused) return fail(c, SVA_ERR_INVALID_ARG, "null volume");
+    if ((s = check_stage_volume(c, W, H, D, dreal, dmin))) return s;
+    int32_t red[64];
+    if (mixed && (s = check_ratios(c, ratios, n, dmin, dreal, red))) return s;
+    // one dwordx4 per lane and volume
+    if (((uintptr_t)volumes | (uintptr_t)fused | stride) & 15)
+        return fail(c, SVA_ERR_INVALID_ARG, "volumes, stride and fused must be 16-byte aligned");
+    if (n > 1 && stride < (size_t)W * H * (size_t)D)
+        return fail(c, SVA_ERR_INVALID_ARG, "stride smaller than one volume");
+    SVA_HIP(c,
+            mixed ? launch_cost_fuse_mixed(*c, volumes, stride, n, W, H, D, dreal, dmin, steps, red,
+                                           fused)
+                  : launch_cost_fuse(*c, volumes, stride, n, W, H, D, dreal, dmin, steps, fused),
+            "fuse launch");
+    return SVA_OK;
+}
+}  // namespace
+
+int sva_cost_fuse_d(void* ctx, const uint8_t* volumes, size_t stride, int n, int W, int H, int D,
+                    int dreal, int dmin, const int32_t* steps, uint8_t* fused) {
+    return cost_fuse_d(ctx, volumes, stride, n, W, H, D, dreal, dmin, steps, nullptr, false, fused);
+}
+
+int sva_cost_fuse_mixed_d(void* ctx, const uint8_t* volumes, size_t stride, int n, int W, int H,
+                          int D, int dreal, int dmin, const int32_t* steps, const int32_t* ratios,
+                          uint8_t* fused) {
+    return cost_fuse_d(ctx, volumes, stride, n, W, H, D, dreal, dmin, steps, ratios, true, fused);
+}
+
+int sva_cost_mixed_d(void* ctx, const uint64_t* census_ref, const uint64_t* census_oth, int W, int H,
+                     int D, int dreal, int dmin, int sx, int sy, int num, int den, uint8_t* C) {
+    Ctx* c = as_ctx(ctx);
+    SVA_CHECK_CTX(c);
+    int s;
+    const int32_t step[2] = {sx, sy}, ratio[2] = {num, den};
+    int32_t red[2];
+    if ((s = check_steps(c, step, 1))) return s;
+    if (!census_ref || !census_oth || !C) return fail(c, SVA_ERR_INVALID_ARG, "null buffer");
+    if ((s = check_stage_volume(c, W, H, D, dreal, dmin))) return s;
+    if ((s = check_ratios(c, ratio, 1, dmin, dreal, red))) return s;
+    if (((uintptr_t)census_ref | (uintptr_t)census_oth) & 7 || (uintptr_t)C & 15)
+        return fail(c, SVA_ERR_INVALID_ARG, "census maps 8-byte, C 16-byte aligned");
+    SVA_HIP(c, launch_cost_mixed(*c, census_ref, census_oth, W, H, D, dmin, sx, sy, red[0], red[1],
+                                 C, dreal),
+            "cost launch");
+    return SVA_OK;
+}
+
+int sva_disparity_sgm_multi_d(void* ctx, const uint8_t* ref, const uint8_t* const* others,
+                              const int32_t* steps, int n, int W, int H, size_t pitch,
+                              const sva_sgm_params* p, int uniqueness, uint16_t* disp, float* sub,
+                              uint16_t* cost_min, uint16_t* cost_second) {
+    return sgm_multi_d(ctx, ref, others, steps, nullptr, false, n, W, H, pitch, p, uniqueness, disp,
+                       sub, cost_min, cost_second);
+}
+
+int sva_disparity_sgm_multi(void* ctx, const uint8_t* ref, const uint8_t* const* others,
+                            const int32_t* steps, int n, int W, int H, size_t pitch,
+                            const sva_sgm_params* p, int uniqueness, uint16_t* disp, float* sub,
+                            uint16_t* cost_min, uint16_t* cost_second) {
+    return sgm_multi_host(ctx, ref, others, steps, nullptr, false, n, W, H, pitch, p, uniqueness,
+                          disp, sub, cost_min, cost_second);
+}
+
+int sva_disparity_sgm_mixed_d(void* ctx, const uint8_t* ref, const uint8_t* const* others,
+                              const int32_t* steps, const int32_t* ratios, int n, int W, int H,
+                              size_t pitch, const sva_sgm_params* p, int uniqueness, uint16_t* disp,
+                              float* sub, uint16_t* cost_min, uint16_t* cost_second) {
+    return sgm_multi_d(ctx, ref, others, steps, ratios, true, n, W, H, pitch, p, uniqueness, disp,
+                       sub, cost_min, cost_second);
+}
+
+int sva_disparity_sgm_mixed(void* ctx, const uint8_t* ref, const uint8_t* const* others,
+                            const int32_t* steps, const int32_t* ratios, int n, int W, int H,
+                            size_t pitch, const sva_sgm_params* p, int uniqueness, uint16_t* disp,
+                            float* sub, uint16_t* cost_min, uint16_t* cost_second) {
+    return sgm_multi_host(ctx, ref, others, steps, ratios, true, n, W, H, pitch, p, uniqueness, disp,
+                          sub, cost_min, cost_second);
 }
 
 int sva_disparity_sgm_d(void* ctx, const uint8_t* left, const uint8_t* right, int W, int H,

@@ -257,6 +257,19 @@ hipError_t launch_cost2(Ctx& c, const uint64_t* cl, const uint64_t* cr, int W, i
 // image, 62 where none is, 255 at d >= dreal (0 = D).
 hipError_t launch_cost_fuse(Ctx& c, const uint8_t* volumes, size_t stride, int n, int W, int H,
                             int D, int dreal, int dmin, const int32_t* steps, uint8_t* fused);
+// The mixed-baseline instance: pair i's major-axis baseline
+// is ratios[2i] / ratios[2i+1] of the group's unit baseline (each in 1..8), and
+// it is visible where its matched pixel at distance t(dmin + d) is inside.
+hipError_t launch_cost_fuse_mixed(Ctx& c, const uint8_t* volumes, size_t stride, int n, int W,
+                                  int H, int D, int dreal, int dmin, const int32_t* steps,
+                                  const int32_t* ratios, uint8_t* fused);
+// cost_mixed.hip -- the cost volume of one such pair from two census maps
+// (DESIGN.md §2.2d, §4.20): C(p, d) against the matched pixel at distance
+// t(dmin + d) = (dmin + d) * num / den rounded half up along (sx, sy).  Native
+// D; num, den in 1..8; 255 at d >= dreal (0 = D).
+hipError_t launch_cost_mixed(Ctx& c, const uint64_t* cen_ref, const uint64_t* cen_oth, int W, int H,
+                             int D, int dmin, int sx, int sy, int num, int den, uint8_t* C,
+                             int dreal = 0);
 // Median depth fusion over n_maps <= 32 u16 maps.
 // num[i] = baseline_i * f (host-computed, same f64 product as the oracle).
 hipError_t launch_fuse_depth(Ctx& c, const uint16_t* disps, int n_maps, size_t np,
