@@ -434,8 +434,8 @@ private:
 };
 
 namespace detail {
-// The C-ABI form of one camera-array frame, shared by computeArrayDepth and
-// computeArrayDepthConf: the pairs grouped by reference camera (stable: the
+// The C-ABI form of one camera-array frame, shared by the four
+// computeArrayDepth*: the pairs grouped by reference camera (stable: the
 // order reference cameras first appear in `pairs`), each with its grid step.
 struct ArrayFrame {
     int W = 0, H = 0;
@@ -453,6 +453,12 @@ struct ArrayFrame {
         out->assign(n_pairs, {});
         for (size_t i = 0; i < ap.size(); i++)
             (*out)[order[i]].assign(all.begin() + i * np, all.begin() + (i + 1) * np);
+    }
+    // fn(handle, <the frame: images .. n_groups>, tail...): one of sva_array_depth*
+    template <typename Fn, typename... Tail>
+    int call(Fn fn, void* handle, Tail... tail) const {
+        return fn(handle, ptrs.data(), (int)ptrs.size(), W, H, pitch, ap.data(), (int)ap.size(),
+                  group_start.data(), (int)refs.size(), tail...);
     }
     template <typename T>
     std::vector<std::vector<T>> split(const std::vector<T>& planes) const {
@@ -499,6 +505,27 @@ inline ArrayFrame arrayFrame(const std::vector<ImageView>& images, const std::ve
     for (const auto& im : images) fr.ptrs.push_back(im.data);
     return fr;
 }
+
+// What computeArrayDepth, Conf, Multi and Mixed share around their one C call:
+// the depth planes and, when asked for, the map planes -- one per pair (back in
+// `pairs` order) or, per_group, one per reference camera.  call(f, pixel_size,
+// depth, maps) makes the call with the first reference camera's f and
+// pixel_size.
+template <typename Call>
+inline std::vector<std::vector<double>> arrayDepth(const ArrayFrame& fr,
+                                                   const std::vector<Camera>& cameras,
+                                                   size_t n_pairs, bool per_group,
+                                                   std::vector<std::vector<uint16_t>>* maps,
+                                                   const Call& call) {
+    const size_t np = (size_t)fr.W * fr.H, ng = fr.refs.size();
+    std::vector<double> depth(np * ng);
+    std::vector<uint16_t> all(maps ? np * (per_group ? ng : fr.ap.size()) : 0);
+    const Camera& c0 = cameras.at(fr.refs[0]);
+    call(c0.f, c0.pixel_size, depth.data(), maps ? all.data() : nullptr);
+    if (maps && per_group) *maps = fr.split(all);
+    else if (maps) fr.scatter(all, n_pairs, maps);
+    return fr.split(depth);
+}
 }  // namespace detail
 
 // One camera-array frame over a MultiEngine: replaces the pair loop of
@@ -515,16 +542,10 @@ inline std::vector<std::vector<double>> computeArrayDepth(
     std::vector<std::vector<uint16_t>>* maps = nullptr) {
     const detail::ArrayFrame fr = detail::arrayFrame(images, cameras, pairs, p, pitch,
                                                      "computeArrayDepth");
-    const size_t np = (size_t)fr.W * fr.H;
-    const int ng = (int)fr.refs.size();
-    std::vector<double> depth(np * ng);
-    std::vector<uint16_t> all(maps ? np * fr.ap.size() : 0);
-    const Camera& c0 = cameras.at(fr.refs[0]);
-    m.check(sva_array_depth(m.handle(), fr.ptrs.data(), (int)fr.ptrs.size(), fr.W, fr.H, fr.pitch,
-                            fr.ap.data(), (int)fr.ap.size(), fr.group_start.data(), ng, c0.f,
-                            c0.pixel_size, depth.data(), nullptr, maps ? all.data() : nullptr));
-    if (maps) fr.scatter(all, pairs.size(), maps);
-    return fr.split(depth);
+    return detail::arrayDepth(fr, cameras, pairs.size(), false, maps,
+                              [&](double f, double pixel_size, double* depth, uint16_t* all) {
+        m.check(fr.call(sva_array_depth, m.handle(), f, pixel_size, depth, nullptr, all));
+    });
 }
 
 // computeArrayDepth with confidence (sva_array_depth_conf): the same grouping,
@@ -541,23 +562,69 @@ inline std::vector<std::vector<double>> computeArrayDepthConf(
     std::vector<std::vector<uint8_t>>* winner = nullptr) {
     const detail::ArrayFrame fr = detail::arrayFrame(images, cameras, pairs, p, pitch,
                                                      "computeArrayDepthConf");
-    const size_t np = (size_t)fr.W * fr.H;
-    const int ng = (int)fr.refs.size();
-    std::vector<double> depth(np * ng);
-    std::vector<uint16_t> all(maps ? np * fr.ap.size() : 0);
-    std::vector<uint8_t> win(winner ? np * ng : 0);
-    const Camera& c0 = cameras.at(fr.refs[0]);
-    m.check(sva_array_depth_conf(m.handle(), fr.ptrs.data(), (int)fr.ptrs.size(), fr.W, fr.H,
-                                 fr.pitch, fr.ap.data(), (int)fr.ap.size(), fr.group_start.data(),
-                                 ng, c0.f, c0.pixel_size, uniqueness, mode, depth.data(), nullptr,
-                                 winner ? win.data() : nullptr, maps ? all.data() : nullptr,
-                                 nullptr, nullptr));
-    if (maps) fr.scatter(all, pairs.size(), maps);
+    std::vector<uint8_t> win(winner ? (size_t)fr.W * fr.H * fr.refs.size() : 0);
+    auto out = detail::arrayDepth(fr, cameras, pairs.size(), false, maps,
+                                  [&](double f, double pixel_size, double* depth, uint16_t* all) {
+        m.check(fr.call(sva_array_depth_conf, m.handle(), f, pixel_size, uniqueness, mode, depth,
+                        nullptr, winner ? win.data() : nullptr, all, nullptr, nullptr));
+    });
     if (winner) *winner = fr.split(win);
-    return fr.split(depth);
+    return out;
 }
 
-// ---- multi-baseline Mode S -----------------------------
+// ---- multi-baseline Mode S ----------------------
+
+namespace detail {
+// computeDisparityMulti (mixed false: the pairs share PairStep::k) and
+// computeDisparityMixed (pair i enters at the ratio steps[i].k / unit_k).
+inline std::vector<uint16_t> disparityMulti(
+    Engine& eng, const std::string& who, const ImageView& ref,
+    const std::vector<ImageView>& others, const std::vector<PairStep>& steps, bool mixed,
+    int unit_k, const sva_sgm_params& p, int uniqueness, std::vector<float>* subpix,
+    std::vector<uint16_t>* cost_min, std::vector<uint16_t>* cost_second) {
+    if (others.empty() || others.size() != steps.size())
+        throw Error(SVA_ERR_INVALID_ARG, who + ": need one step per matched image");
+    if (mixed && unit_k < 1) throw Error(SVA_ERR_INVALID_ARG, who + ": unit_k must be >= 1");
+    std::vector<const uint8_t*> ptrs;
+    std::vector<int32_t> st, ratios;
+    for (size_t i = 0; i < others.size(); i++) {
+        const ImageView& o = others[i];
+        if (o.width != ref.width || o.height != ref.height || o.pitch != ref.pitch)
+            throw Error(SVA_ERR_INVALID_ARG, who + ": images differ in size");
+        if (!mixed && steps[i].k != steps[0].k)
+            throw Error(SVA_ERR_INVALID_ARG, who + ": pairs of unequal baselines");
+        int a = steps[i].k, b = unit_k;
+        while (b) { const int r = a % b; a = b; b = r; }
+        if (mixed && a < 1) throw Error(SVA_ERR_INVALID_ARG, who + ": a step with k = 0");
+        ptrs.push_back(o.data);
+        st.push_back(steps[i].dir);
+        st.push_back(steps[i].dir_y);
+        if (mixed) {
+            ratios.push_back(steps[i].k / a);
+            ratios.push_back(unit_k / a);
+        }
+    }
+    const size_t np = (size_t)ref.width * ref.height;
+    std::vector<uint16_t> disp(np);
+    float* sp = nullptr;
+    if (subpix && p.subpixel) {
+        subpix->resize(np);
+        sp = subpix->data();
+    }
+    if (cost_min) cost_min->resize(np);
+    if (cost_second) cost_second->resize(np);
+    uint16_t* cmin = cost_min ? cost_min->data() : nullptr;
+    uint16_t* csec = cost_second ? cost_second->data() : nullptr;
+    const int n = (int)ptrs.size();
+    eng.check(mixed ? sva_disparity_sgm_mixed(eng.handle(), ref.data, ptrs.data(), st.data(),
+                                              ratios.data(), n, ref.width, ref.height, ref.pitch,
+                                              &p, uniqueness, disp.data(), sp, cmin, csec)
+                    : sva_disparity_sgm_multi(eng.handle(), ref.data, ptrs.data(), st.data(), n,
+                                              ref.width, ref.height, ref.pitch, &p, uniqueness,
+                                              disp.data(), sp, cmin, csec));
+    return disp;
+}
+}  // namespace detail
 
 // One reference image against several matched images, image i along steps[i]
 // (PairStep of (ref, other_i); the pairs must share PairStep::k, so that one
@@ -570,35 +637,8 @@ inline std::vector<uint16_t> computeDisparityMulti(
     const std::vector<PairStep>& steps, const sva_sgm_params& p, int uniqueness = 0,
     std::vector<float>* subpix = nullptr, std::vector<uint16_t>* cost_min = nullptr,
     std::vector<uint16_t>* cost_second = nullptr) {
-    if (others.empty() || others.size() != steps.size())
-        throw Error(SVA_ERR_INVALID_ARG, "computeDisparityMulti: need one step per matched image");
-    std::vector<const uint8_t*> ptrs;
-    std::vector<int32_t> st;
-    for (size_t i = 0; i < others.size(); i++) {
-        const ImageView& o = others[i];
-        if (o.width != ref.width || o.height != ref.height || o.pitch != ref.pitch)
-            throw Error(SVA_ERR_INVALID_ARG, "computeDisparityMulti: images differ in size");
-        if (steps[i].k != steps[0].k)
-            throw Error(SVA_ERR_INVALID_ARG, "computeDisparityMulti: pairs of unequal baselines");
-        ptrs.push_back(o.data);
-        st.push_back(steps[i].dir);
-        st.push_back(steps[i].dir_y);
-    }
-    const size_t np = (size_t)ref.width * ref.height;
-    std::vector<uint16_t> disp(np);
-    float* sp = nullptr;
-    if (subpix && p.subpixel) {
-        subpix->resize(np);
-        sp = subpix->data();
-    }
-    if (cost_min) cost_min->resize(np);
-    if (cost_second) cost_second->resize(np);
-    eng.check(sva_disparity_sgm_multi(eng.handle(), ref.data, ptrs.data(), st.data(),
-                                      (int)ptrs.size(), ref.width, ref.height, ref.pitch, &p,
-                                      uniqueness, disp.data(), sp,
-                                      cost_min ? cost_min->data() : nullptr,
-                                      cost_second ? cost_second->data() : nullptr));
-    return disp;
+    return detail::disparityMulti(eng, "computeDisparityMulti", ref, others, steps, false, 0, p,
+                                  uniqueness, subpix, cost_min, cost_second);
 }
 
 // computeArrayDepth on the multi-baseline route (sva_array_depth_mb): the same
@@ -613,20 +653,12 @@ inline std::vector<std::vector<double>> computeArrayDepthMulti(
     double pitch = 0.05, std::vector<std::vector<uint16_t>>* maps = nullptr) {
     const detail::ArrayFrame fr = detail::arrayFrame(images, cameras, pairs, p, pitch,
                                                      "computeArrayDepthMulti");
-    const size_t np = (size_t)fr.W * fr.H;
-    const int ng = (int)fr.refs.size();
-    std::vector<double> depth(np * ng);
-    std::vector<uint16_t> all(maps ? np * ng : 0);
-    const Camera& c0 = cameras.at(fr.refs[0]);
-    m.check(sva_array_depth_mb(m.handle(), fr.ptrs.data(), (int)fr.ptrs.size(), fr.W, fr.H,
-                               fr.pitch, fr.ap.data(), (int)fr.ap.size(), fr.group_start.data(),
-                               ng, c0.f, c0.pixel_size, uniqueness, depth.data(),
-                               maps ? all.data() : nullptr, nullptr, nullptr));
-    if (maps) *maps = fr.split(all);
-    return fr.split(depth);
+    return detail::arrayDepth(fr, cameras, pairs.size(), true, maps,
+                              [&](double f, double pixel_size, double* depth, uint16_t* all) {
+        m.check(fr.call(sva_array_depth_mb, m.handle(), f, pixel_size, uniqueness, depth, all,
+                        nullptr, nullptr));
+    });
 }
-
-// ---- mixed-baseline Mode S -----------------------------
 
 // computeDisparityMulti for pairs of UNEQUAL baselines (sva_disparity_sgm_mixed):
 // disparity counts pixels of a pair whose PairStep::k is unit_k, and pair i
@@ -638,39 +670,8 @@ inline std::vector<uint16_t> computeDisparityMixed(
     const std::vector<PairStep>& steps, int unit_k, const sva_sgm_params& p, int uniqueness = 0,
     std::vector<float>* subpix = nullptr, std::vector<uint16_t>* cost_min = nullptr,
     std::vector<uint16_t>* cost_second = nullptr) {
-    if (others.empty() || others.size() != steps.size())
-        throw Error(SVA_ERR_INVALID_ARG, "computeDisparityMixed: need one step per matched image");
-    if (unit_k < 1) throw Error(SVA_ERR_INVALID_ARG, "computeDisparityMixed: unit_k must be >= 1");
-    std::vector<const uint8_t*> ptrs;
-    std::vector<int32_t> st, ratios;
-    for (size_t i = 0; i < others.size(); i++) {
-        const ImageView& o = others[i];
-        if (o.width != ref.width || o.height != ref.height || o.pitch != ref.pitch)
-            throw Error(SVA_ERR_INVALID_ARG, "computeDisparityMixed: images differ in size");
-        int a = steps[i].k, b = unit_k;
-        while (b) { const int r = a % b; a = b; b = r; }
-        if (a < 1) throw Error(SVA_ERR_INVALID_ARG, "computeDisparityMixed: a step with k = 0");
-        ptrs.push_back(o.data);
-        st.push_back(steps[i].dir);
-        st.push_back(steps[i].dir_y);
-        ratios.push_back(steps[i].k / a);
-        ratios.push_back(unit_k / a);
-    }
-    const size_t np = (size_t)ref.width * ref.height;
-    std::vector<uint16_t> disp(np);
-    float* sp = nullptr;
-    if (subpix && p.subpixel) {
-        subpix->resize(np);
-        sp = subpix->data();
-    }
-    if (cost_min) cost_min->resize(np);
-    if (cost_second) cost_second->resize(np);
-    eng.check(sva_disparity_sgm_mixed(eng.handle(), ref.data, ptrs.data(), st.data(),
-                                      ratios.data(), (int)ptrs.size(), ref.width, ref.height,
-                                      ref.pitch, &p, uniqueness, disp.data(), sp,
-                                      cost_min ? cost_min->data() : nullptr,
-                                      cost_second ? cost_second->data() : nullptr));
-    return disp;
+    return detail::disparityMulti(eng, "computeDisparityMixed", ref, others, steps, true, unit_k,
+                                  p, uniqueness, subpix, cost_min, cost_second);
 }
 
 // computeArrayDepthMulti for groups of unequal baselines (sva_array_depth_mixed):
@@ -685,26 +686,21 @@ inline std::vector<std::vector<double>> computeArrayDepthMixed(
     if (unit_k < 0) throw Error(SVA_ERR_INVALID_ARG, "computeArrayDepthMixed: unit_k must be >= 0");
     const detail::ArrayFrame fr = detail::arrayFrame(images, cameras, pairs, p, pitch,
                                                      "computeArrayDepthMixed");
-    const size_t np = (size_t)fr.W * fr.H;
-    const int ng = (int)fr.refs.size();
-    std::vector<double> unit(ng);
-    for (int g = 0; g < ng; g++) {
+    std::vector<double> unit(fr.refs.size());
+    for (size_t g = 0; g < unit.size(); g++) {
         double u = unit_k * pitch;
         if (!unit_k)
             for (int j = fr.group_start[g]; j < fr.group_start[g + 1]; j++)
                 u = std::max(u, fr.ap[j].baseline);
         unit[g] = u;
     }
-    std::vector<double> depth(np * ng);
-    std::vector<uint16_t> all(maps ? np * ng : 0);
-    const Camera& c0 = cameras.at(fr.refs[0]);
-    m.check(sva_array_depth_mixed(m.handle(), fr.ptrs.data(), (int)fr.ptrs.size(), fr.W, fr.H,
-                                  fr.pitch, fr.ap.data(), (int)fr.ap.size(), fr.group_start.data(),
-                                  ng, unit.data(), c0.f, c0.pixel_size, uniqueness, depth.data(),
-                                  maps ? all.data() : nullptr, nullptr, nullptr));
-    if (maps) *maps = fr.split(all);
-    return fr.split(depth);
+    return detail::arrayDepth(fr, cameras, pairs.size(), true, maps,
+                              [&](double f, double pixel_size, double* depth, uint16_t* all) {
+        m.check(fr.call(sva_array_depth_mixed, m.handle(), (const double*)unit.data(), f,
+                        pixel_size, uniqueness, depth, all, nullptr, nullptr));
+    });
 }
+
 
 // ---- refinement and 3-D output ----
 // The reference's names and argument meaning; cv::Mat becomes ImageView (u8)

@@ -325,6 +325,39 @@ def _i32_pairs(pairs):
     return (ct.c_int32 * max(2, 2 * len(pairs)))(*[int(v) for s in pairs for v in s])
 
 
+def _ptr_table(arrays):
+    """The data pointers of a list of arrays as a C array."""
+    return (ct.c_void_p * max(1, len(arrays)))(*[_ptr(a) for a in arrays])
+
+
+def _pair_table(pairs):
+    """A list of (left_ptr, right_ptr, SgmParams) as a C sva_pair_d array."""
+    jobs = (PairD * len(pairs))()
+    for i, (l, r, p) in enumerate(pairs):
+        jobs[i] = PairD(_ptr(l), _ptr(r), p)
+    return jobs
+
+
+class _ArrayFrame:
+    """The C form of one array frame (sva_array_depth*).  images: HxW u8 views;
+    pairs: (ref, other, SgmParams, baseline) each; group_start: G + 1 offsets.
+    head: the arguments from `images` to `n_groups`."""
+
+    def __init__(self, images, pairs, group_start):
+        self.imgs = [np.ascontiguousarray(a, dtype=np.uint8) for a in images]
+        self.H, self.W = self.imgs[0].shape
+        self.P, self.G = len(pairs), len(group_start) - 1
+        jp = (ArrayPair * self.P)()
+        for i, (a, b, p, base) in enumerate(pairs):
+            jp[i] = ArrayPair(a, b, p, base)
+        self.head = (_ptr_table(self.imgs), len(self.imgs), self.W, self.H, self.W, jp, self.P,
+                     (ct.c_int32 * len(group_start))(*group_start), self.G)
+
+    def planes(self, n, dtype, want=True):
+        """An [n, H, W] output, or None for one not asked for."""
+        return np.zeros((n, self.H, self.W), dtype) if want else None
+
+
 class Context:
     """One device + one stream (``sva_create``)."""
 
@@ -449,76 +482,65 @@ class Context:
                                                ct.byref(params), int(uniqueness), _ptr(disp),
                                                _ptr(sub), _ptr(cost_min), _ptr(cost_second)))
 
-    # -- multi-baseline Mode S: one reference image, n matched images
+    # -- multi-baseline Mode S: one reference image, n matched images,
+    # -- and its mixed-baseline form: pairs of unequal baselines in one volume (§2.2d).
+    # `ratios` below is () or (the C ratio table,): the one argument the mixed calls add
+    def _sgm_multi_d(self, fn, ref, others, steps, ratios, W, H, pitch, params, uniqueness, disp,
+                     sub, cost_min, cost_second):
+        self._chk(fn(self.h, _ptr(ref), _ptr_table(others), _i32_pairs(steps), *ratios,
+                     len(others), W, H, pitch, ct.byref(params), int(uniqueness), _ptr(disp),
+                     _ptr(sub), _ptr(cost_min), _ptr(cost_second)))
+
+    def _sgm_multi(self, fn, ref, others, steps, ratios, params, uniqueness):
+        ref = np.ascontiguousarray(ref, dtype=np.uint8)
+        oth = [np.ascontiguousarray(a, dtype=np.uint8) for a in others]
+        assert len(oth) == len(steps) and all(a.shape == ref.shape for a in oth)
+        H, W = ref.shape
+        disp = np.zeros((H, W), np.uint16)
+        sub = np.zeros((H, W), np.float32) if params.subpixel else None
+        cmin = np.zeros((H, W), np.uint16)
+        csec = np.zeros((H, W), np.uint16)
+        self._sgm_multi_d(fn, ref, oth, steps, ratios, W, H, W, params, uniqueness, disp, sub,
+                          cmin, csec)
+        return disp, sub, cmin, csec
+
     def disparity_sgm_multi(self, ref: np.ndarray, others, steps, params: SgmParams,
                             uniqueness: int = 0):
         """(disp, sub, cost_min, cost_second): sva_disparity_sgm_multi.  others: n
         HxW u8 images, steps: n (dir, dir_y) steps; the n cost volumes are fused
         (mean over the pairs whose matched pixel is inside the image) before one
         aggregation.  params.dir / dir_y are ignored."""
-        ref = np.ascontiguousarray(ref, dtype=np.uint8)
-        oth = [np.ascontiguousarray(a, dtype=np.uint8) for a in others]
-        assert len(oth) == len(steps) and all(a.shape == ref.shape for a in oth)
-        H, W = ref.shape
-        ptrs = (ct.c_void_p * max(1, len(oth)))(*[_ptr(a) for a in oth])
-        st = (ct.c_int32 * max(2, 2 * len(steps)))(*[int(v) for s in steps for v in s])
-        disp = np.zeros((H, W), np.uint16)
-        sub = np.zeros((H, W), np.float32) if params.subpixel else None
-        cmin = np.zeros((H, W), np.uint16)
-        csec = np.zeros((H, W), np.uint16)
-        self._chk(lib.sva_disparity_sgm_multi(self.h, _ptr(ref), ptrs, st, len(oth), W, H, W,
-                                              ct.byref(params), int(uniqueness), _ptr(disp),
-                                              _ptr(sub), _ptr(cmin), _ptr(csec)))
-        return disp, sub, cmin, csec
+        return self._sgm_multi(lib.sva_disparity_sgm_multi, ref, others, steps, (), params,
+                               uniqueness)
 
     def disparity_sgm_multi_d(self, ref, others, steps, W, H, pitch, params, uniqueness, disp,
                               sub=None, cost_min=None, cost_second=None):
         """Device pointers; others: n image pointers, steps: n (dir, dir_y)."""
-        ptrs = (ct.c_void_p * max(1, len(others)))(*[_ptr(a) for a in others])
-        st = (ct.c_int32 * max(2, 2 * len(steps)))(*[int(v) for s in steps for v in s])
-        self._chk(lib.sva_disparity_sgm_multi_d(self.h, _ptr(ref), ptrs, st, len(others), W, H,
-                                                pitch, ct.byref(params), int(uniqueness),
-                                                _ptr(disp), _ptr(sub), _ptr(cost_min),
-                                                _ptr(cost_second)))
+        self._sgm_multi_d(lib.sva_disparity_sgm_multi_d, ref, others, steps, (), W, H, pitch,
+                          params, uniqueness, disp, sub, cost_min, cost_second)
 
     def cost_fuse_d(self, volumes, stride, steps, W, H, D, dreal, dmin, fused):
         """sva_cost_fuse_d: len(steps) device volumes [H][W][D] u8, `stride` bytes
         apart, fused into `fused`."""
-        st = (ct.c_int32 * max(2, 2 * len(steps)))(*[int(v) for s in steps for v in s])
         self._chk(lib.sva_cost_fuse_d(self.h, _ptr(volumes), stride, len(steps), W, H, D, dreal,
-                                      dmin, st, _ptr(fused)))
+                                      dmin, _i32_pairs(steps), _ptr(fused)))
 
-    # -- mixed-baseline Mode S: pairs of unequal baselines in one volume (DESIGN.md §2.2d)
     def disparity_sgm_mixed(self, ref: np.ndarray, others, steps, ratios, params: SgmParams,
                             uniqueness: int = 0):
         """(disp, sub, cost_min, cost_second): sva_disparity_sgm_mixed.  As
         disparity_sgm_multi, with ratios: n (num, den) -- pair i's major-axis
         baseline over the group's unit baseline, each in 1..8 (None = a null
         pointer, which the library refuses)."""
-        ref = np.ascontiguousarray(ref, dtype=np.uint8)
-        oth = [np.ascontiguousarray(a, dtype=np.uint8) for a in others]
-        assert len(oth) == len(steps) and all(a.shape == ref.shape for a in oth)
-        H, W = ref.shape
-        ptrs = (ct.c_void_p * max(1, len(oth)))(*[_ptr(a) for a in oth])
-        disp = np.zeros((H, W), np.uint16)
-        sub = np.zeros((H, W), np.float32) if params.subpixel else None
-        cmin = np.zeros((H, W), np.uint16)
-        csec = np.zeros((H, W), np.uint16)
-        self._chk(lib.sva_disparity_sgm_mixed(self.h, _ptr(ref), ptrs, _i32_pairs(steps),
-                                              _i32_pairs(ratios), len(oth), W, H, W,
-                                              ct.byref(params), int(uniqueness), _ptr(disp),
-                                              _ptr(sub), _ptr(cmin), _ptr(csec)))
-        return disp, sub, cmin, csec
+        return self._sgm_multi(lib.sva_disparity_sgm_mixed, ref, others, steps,
+                               (_i32_pairs(ratios),), params, uniqueness)
 
     def disparity_sgm_mixed_d(self, ref, others, steps, ratios, W, H, pitch, params, uniqueness,
                               disp, sub=None, cost_min=None, cost_second=None):
         """Device pointers; others: n image pointers, steps: n (dir, dir_y),
         ratios: n (num, den)."""
-        ptrs = (ct.c_void_p * max(1, len(others)))(*[_ptr(a) for a in others])
-        self._chk(lib.sva_disparity_sgm_mixed_d(self.h, _ptr(ref), ptrs, _i32_pairs(steps),
-                                                _i32_pairs(ratios), len(others), W, H, pitch,
-                                                ct.byref(params), int(uniqueness), _ptr(disp),
-                                                _ptr(sub), _ptr(cost_min), _ptr(cost_second)))
+        self._sgm_multi_d(lib.sva_disparity_sgm_mixed_d, ref, others, steps,
+                          (_i32_pairs(ratios),), W, H, pitch, params, uniqueness, disp, sub,
+                          cost_min, cost_second)
 
     def cost_mixed_d(self, census_ref, census_oth, W, H, D, dreal, dmin, step, ratio, C):
         """sva_cost_mixed_d: the cost volume [H][W][D] u8 of one pair at ratio =
@@ -535,6 +557,7 @@ class Context:
                                             dreal, dmin, _i32_pairs(steps), _i32_pairs(ratios),
                                             _ptr(fused)))
 
+
     def wta_conf_d(self, S, W, H, params, uniqueness, disp, sub=None, cost_min=None,
                    cost_second=None):
         self._chk(lib.sva_wta_conf_d(self.h, _ptr(S), W, H, ct.byref(params), int(uniqueness),
@@ -543,23 +566,18 @@ class Context:
     def disparity_sgm_batch_d(self, pairs, W, H, pitch, maps, sub=None):
         """pairs: list of (left_ptr, right_ptr, SgmParams) on this context's device;
         maps: [n][H][W] u16 device, sub: [n][H][W] f32 device or None."""
-        jobs = (PairD * len(pairs))()
-        for i, (l, r, p) in enumerate(pairs):
-            jobs[i] = PairD(_ptr(l), _ptr(r), p)
-        self._chk(lib.sva_disparity_sgm_batch_d(self.h, jobs, len(pairs), W, H, pitch,
-                                                _ptr(maps), _ptr(sub)))
+        self._chk(lib.sva_disparity_sgm_batch_d(self.h, _pair_table(pairs), len(pairs), W, H,
+                                                pitch, _ptr(maps), _ptr(sub)))
 
     def disparity_sgm_batch_conf_d(self, pairs, W, H, pitch, uniqueness, maps, sub=None,
                                    cost_min=None, cost_second=None):
         """disparity_sgm_batch_d through the confidence instance: cost_min /
         cost_second are [n][H][W] u16 device planes or None; the pairs also
         share params.invalid."""
-        jobs = (PairD * len(pairs))()
-        for i, (l, r, p) in enumerate(pairs):
-            jobs[i] = PairD(_ptr(l), _ptr(r), p)
-        self._chk(lib.sva_disparity_sgm_batch_conf_d(self.h, jobs, len(pairs), W, H, pitch,
-                                                     int(uniqueness), _ptr(maps), _ptr(sub),
+        self._chk(lib.sva_disparity_sgm_batch_conf_d(self.h, _pair_table(pairs), len(pairs), W, H,
+                                                     pitch, int(uniqueness), _ptr(maps), _ptr(sub),
                                                      _ptr(cost_min), _ptr(cost_second)))
+
 
     def census_d(self, img, W, H, pitch, out):
         self._chk(lib.sva_census_d(self.h, _ptr(img), W, H, pitch, _ptr(out)))
@@ -882,22 +900,16 @@ class Multi:
 
     def batch_sgm_d(self, pairs, W, H, pitch, maps, sub=None):
         """pairs: list of (left_ptr, right_ptr, SgmParams) on their owner devices."""
-        jobs = (PairD * len(pairs))()
-        for i, (l, r, p) in enumerate(pairs):
-            jobs[i] = PairD(_ptr(l), _ptr(r), p)
-        self._chk(lib.sva_batch_sgm_d(self.h, jobs, len(pairs), W, H, pitch, _ptr(maps),
-                                      _ptr(sub)))
+        self._chk(lib.sva_batch_sgm_d(self.h, _pair_table(pairs), len(pairs), W, H, pitch,
+                                      _ptr(maps), _ptr(sub)))
 
     def batch_sgm_conf_d(self, pairs, W, H, pitch, uniqueness, maps, sub=None, cost_min=None,
                          cost_second=None):
         """batch_sgm_d with every pair through sva_disparity_sgm_conf_d; cost_min /
         cost_second: [n][H][W] u16 on devices[0] or None (only those given are
         gathered)."""
-        jobs = (PairD * len(pairs))()
-        for i, (l, r, p) in enumerate(pairs):
-            jobs[i] = PairD(_ptr(l), _ptr(r), p)
-        self._chk(lib.sva_batch_sgm_conf_d(self.h, jobs, len(pairs), W, H, pitch, int(uniqueness),
-                                           _ptr(maps), _ptr(sub), _ptr(cost_min),
+        self._chk(lib.sva_batch_sgm_conf_d(self.h, _pair_table(pairs), len(pairs), W, H, pitch,
+                                           int(uniqueness), _ptr(maps), _ptr(sub), _ptr(cost_min),
                                            _ptr(cost_second)))
 
     def array_depth_conf(self, images, pairs, group_start, f, pixel_size, uniqueness=0,
@@ -906,25 +918,25 @@ class Multi:
         picked by mode (SVA_FUSE_MIN_COST, SVA_FUSE_MAX_MARGIN, SVA_FUSE_MEDIAN).
         Returns (depth, n_valid, winner [G,H,W] u8 or None with MEDIAN, maps,
         cost_min, cost_second), the last three [P,H,W] u16 or None."""
-        imgs = [np.ascontiguousarray(a, dtype=np.uint8) for a in images]
-        H, W = imgs[0].shape
-        ptrs = (ct.c_void_p * len(imgs))(*[_ptr(a) for a in imgs])
-        jp = (ArrayPair * len(pairs))()
-        for i, (a, b, p, base) in enumerate(pairs):
-            jp[i] = ArrayPair(a, b, p, base)
-        gs = (ct.c_int32 * len(group_start))(*group_start)
-        G = len(group_start) - 1
-        depth = np.zeros((G, H, W), np.float64)
-        nv = np.zeros((G, H, W), np.uint8)
-        win = np.zeros((G, H, W), np.uint8) if mode != SVA_FUSE_MEDIAN else None
-        maps = np.zeros((len(pairs), H, W), np.uint16) if want_maps else None
-        cmin = np.zeros((len(pairs), H, W), np.uint16) if want_costs else None
-        csec = np.zeros((len(pairs), H, W), np.uint16) if want_costs else None
-        self._chk(lib.sva_array_depth_conf(self.h, ptrs, len(imgs), W, H, W, jp, len(pairs), gs,
-                                           G, f, pixel_size, int(uniqueness), int(mode),
-                                           _ptr(depth), _ptr(nv), _ptr(win), _ptr(maps),
+        fr = _ArrayFrame(images, pairs, group_start)
+        depth, nv = fr.planes(fr.G, np.float64), fr.planes(fr.G, np.uint8)
+        win = fr.planes(fr.G, np.uint8, mode != SVA_FUSE_MEDIAN)
+        maps = fr.planes(fr.P, np.uint16, want_maps)
+        cmin, csec = fr.planes(fr.P, np.uint16, want_costs), fr.planes(fr.P, np.uint16, want_costs)
+        self._chk(lib.sva_array_depth_conf(self.h, *fr.head, f, pixel_size, int(uniqueness),
+                                           int(mode), _ptr(depth), _ptr(nv), _ptr(win), _ptr(maps),
                                            _ptr(cmin), _ptr(csec)))
         return depth, nv, win, maps, cmin, csec
+
+    def _array_depth_groups(self, fn, fr, scale, uniqueness, want_maps, want_costs):
+        """The group routes: one map and one pair of cost planes per group.
+        scale: the arguments from f to pixel_size."""
+        depth = fr.planes(fr.G, np.float64)
+        maps = fr.planes(fr.G, np.uint16, want_maps)
+        cmin, csec = fr.planes(fr.G, np.uint16, want_costs), fr.planes(fr.G, np.uint16, want_costs)
+        self._chk(fn(self.h, *fr.head, *scale, int(uniqueness), _ptr(depth), _ptr(maps),
+                     _ptr(cmin), _ptr(csec)))
+        return depth, maps, cmin, csec
 
     def array_depth_mb(self, images, pairs, group_start, f, pixel_size, uniqueness=0,
                        want_maps=False, want_costs=False):
@@ -932,62 +944,28 @@ class Multi:
         (one reference view, equal baselines) are fused at the cost level and
         aggregated once.  Returns (depth [G,H,W] f64, maps, cost_min,
         cost_second), the last three [G,H,W] u16 or None."""
-        imgs = [np.ascontiguousarray(a, dtype=np.uint8) for a in images]
-        H, W = imgs[0].shape
-        ptrs = (ct.c_void_p * len(imgs))(*[_ptr(a) for a in imgs])
-        jp = (ArrayPair * len(pairs))()
-        for i, (a, b, p, base) in enumerate(pairs):
-            jp[i] = ArrayPair(a, b, p, base)
-        gs = (ct.c_int32 * len(group_start))(*group_start)
-        G = len(group_start) - 1
-        depth = np.zeros((G, H, W), np.float64)
-        maps = np.zeros((G, H, W), np.uint16) if want_maps else None
-        cmin = np.zeros((G, H, W), np.uint16) if want_costs else None
-        csec = np.zeros((G, H, W), np.uint16) if want_costs else None
-        self._chk(lib.sva_array_depth_mb(self.h, ptrs, len(imgs), W, H, W, jp, len(pairs), gs, G,
-                                         f, pixel_size, int(uniqueness), _ptr(depth), _ptr(maps),
-                                         _ptr(cmin), _ptr(csec)))
-        return depth, maps, cmin, csec
+        fr = _ArrayFrame(images, pairs, group_start)
+        return self._array_depth_groups(lib.sva_array_depth_mb, fr, (f, pixel_size), uniqueness,
+                                        want_maps, want_costs)
 
     def array_depth_mixed(self, images, pairs, group_start, unit_baseline, f, pixel_size,
                           uniqueness=0, want_maps=False, want_costs=False):
         """sva_array_depth_mixed: array_depth_mb for groups of unequal baselines.
         unit_baseline: one per group; each pair's baseline must be num/den (1..8
         each) of it, and the group's depth is unit_baseline * f / (d * pixel_size)."""
-        imgs = [np.ascontiguousarray(a, dtype=np.uint8) for a in images]
-        H, W = imgs[0].shape
-        ptrs = (ct.c_void_p * len(imgs))(*[_ptr(a) for a in imgs])
-        jp = (ArrayPair * len(pairs))()
-        for i, (a, b, p, base) in enumerate(pairs):
-            jp[i] = ArrayPair(a, b, p, base)
-        gs = (ct.c_int32 * len(group_start))(*group_start)
-        G = len(group_start) - 1
-        assert len(unit_baseline) == G
-        ub = (ct.c_double * G)(*[float(v) for v in unit_baseline])
-        depth = np.zeros((G, H, W), np.float64)
-        maps = np.zeros((G, H, W), np.uint16) if want_maps else None
-        cmin = np.zeros((G, H, W), np.uint16) if want_costs else None
-        csec = np.zeros((G, H, W), np.uint16) if want_costs else None
-        self._chk(lib.sva_array_depth_mixed(self.h, ptrs, len(imgs), W, H, W, jp, len(pairs), gs,
-                                            G, ub, f, pixel_size, int(uniqueness), _ptr(depth),
-                                            _ptr(maps), _ptr(cmin), _ptr(csec)))
-        return depth, maps, cmin, csec
+        fr = _ArrayFrame(images, pairs, group_start)
+        assert len(unit_baseline) == fr.G
+        ub = (ct.c_double * fr.G)(*[float(v) for v in unit_baseline])
+        return self._array_depth_groups(lib.sva_array_depth_mixed, fr, (ub, f, pixel_size),
+                                        uniqueness, want_maps, want_costs)
 
     def array_depth(self, images, pairs, group_start, f, pixel_size, want_maps=False):
         """images: list of HxW u8 numpy views; pairs: list of (ref, other,
         SgmParams, baseline); group_start: n_groups + 1 offsets.  Returns
         (depth [G,H,W] f64, n_valid [G,H,W] u8, maps [P,H,W] u16 or None)."""
-        imgs = [np.ascontiguousarray(a, dtype=np.uint8) for a in images]
-        H, W = imgs[0].shape
-        ptrs = (ct.c_void_p * len(imgs))(*[_ptr(a) for a in imgs])
-        jp = (ArrayPair * len(pairs))()
-        for i, (a, b, p, base) in enumerate(pairs):
-            jp[i] = ArrayPair(a, b, p, base)
-        gs = (ct.c_int32 * len(group_start))(*group_start)
-        G = len(group_start) - 1
-        depth = np.zeros((G, H, W), np.float64)
-        nv = np.zeros((G, H, W), np.uint8)
-        maps = np.zeros((len(pairs), H, W), np.uint16) if want_maps else None
-        self._chk(lib.sva_array_depth(self.h, ptrs, len(imgs), W, H, W, jp, len(pairs), gs, G,
-                                      f, pixel_size, _ptr(depth), _ptr(nv), _ptr(maps)))
+        fr = _ArrayFrame(images, pairs, group_start)
+        depth, nv = fr.planes(fr.G, np.float64), fr.planes(fr.G, np.uint8)
+        maps = fr.planes(fr.P, np.uint16, want_maps)
+        self._chk(lib.sva_array_depth(self.h, *fr.head, f, pixel_size, _ptr(depth), _ptr(nv),
+                                      _ptr(maps)))
         return depth, nv, maps

@@ -1,0 +1,153 @@
+// array_args.h -- the arguments of one camera-array frame (sva_array_depth,
+// _conf, _mb and _mixed) and their validation, shared by
+// multi.cpp and a host test program (tests/test_array_args_cpu.py compiles this
+// header with a C++ compiler under the sanitizers).  Plain C++: no HIP header.
+#pragma once
+
+#include <algorithm>
+#include <cmath>
+#include <cstddef>
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#include "cost_mixed_math.h"
+#include "sva.h"
+#include "sva_native_d.h"
+
+namespace sva {
+
+// What a job of the frame is: a pair (every pair matched on its own, each
+// group's maps fused into depth), or a reference camera's whole group fused at
+// the cost level, of equal or of mixed baselines (§2.2d).
+enum class ArrayRoute { Pairs, Groups, GroupsMixed };
+
+struct ArrayArgs {
+    const uint8_t* const* images = nullptr;   // n_images host views [H][pitch]
+    int n_images = 0, W = 0, H = 0;
+    size_t pitch = 0;
+    const sva_array_pair* pairs = nullptr;
+    const int32_t* group_start = nullptr;     // n_groups + 1 offsets into pairs
+    int n_pairs = 0, n_groups = 0;
+    double f = 0, pixel_size = 0;
+    ArrayRoute route = ArrayRoute::Pairs;
+    // conf: the jobs run through the confidence instance with this uniqueness,
+    // and `mode` picks the fusion of a group's maps (the group routes: always
+    // on, one map per group, SVA_FUSE_MEDIAN)
+    bool conf = false;
+    int uniqueness = 0, mode = SVA_FUSE_MEDIAN;
+    const double* unit_baseline = nullptr;    // per group; GroupsMixed only
+    // host outputs, all but depth nullable: per group, then per job
+    double* depth = nullptr;
+    uint8_t *n_valid = nullptr, *winner = nullptr;
+    uint16_t *maps = nullptr, *cost_min = nullptr, *cost_second = nullptr;
+};
+
+inline int check_params(const sva_sgm_params& p) {
+    if (!padded_D(p.D) || p.dmin < 0 || (p.dir == 0 && p.dir_y == 0))
+        return SVA_ERR_INVALID_ARG;
+    return SVA_OK;
+}
+
+// The ratio num/den (both in 1..kMaxRatio) that baseline / unit equals within
+// 1e-9 relative: den ascending, the first hit (so the reduced form).  False if
+// none.
+inline bool baseline_ratio(double baseline, double unit, int32_t* num, int32_t* den) {
+    if (!(unit > 0) || !(baseline > 0)) return false;
+    const double r = baseline / unit;
+    for (int d = 1; d <= mb::kMaxRatio; d++)
+        for (int n = 1; n <= mb::kMaxRatio; n++)
+            if (std::fabs(r * d - n) <= 1e-9 * n) {
+                *num = n;
+                *den = d;
+                return true;
+            }
+    return false;
+}
+
+// Checks a frame's arguments, in this order for every route:
+// the route's options; the sizes and pointers; the ends of group_start; every
+// group's size -- all groups, before any pairs[j] is read through group_start;
+// every pair; every group's shared values; the mixed route's ratios.  Returns
+// the status and the message of the first rule broken.  ratio (GroupsMixed):
+// receives every pair's reduced (num, den).
+inline int check_array_args(const ArrayArgs& a, std::string& msg, std::vector<int32_t>& ratio) {
+    auto fail = [&](int code, const std::string& m) {
+        msg = m;
+        return code;
+    };
+    const bool group = a.route != ArrayRoute::Pairs, mixed = a.route == ArrayRoute::GroupsMixed;
+    if (a.conf) {
+        if (a.mode != SVA_FUSE_MIN_COST && a.mode != SVA_FUSE_MAX_MARGIN &&
+            a.mode != SVA_FUSE_MEDIAN)
+            return fail(SVA_ERR_INVALID_ARG, "unknown fusion mode");
+        if (a.uniqueness < 0 || a.uniqueness > 100)
+            return fail(SVA_ERR_INVALID_ARG, "uniqueness must be 0..100");
+        if (a.winner && a.mode == SVA_FUSE_MEDIAN)
+            return fail(SVA_ERR_INVALID_ARG, "the median has no winner map");
+    }
+    if (mixed && !a.unit_baseline) return fail(SVA_ERR_INVALID_ARG, "null unit_baseline");
+    if (!a.images || a.n_images <= 0 || !a.pairs || a.n_pairs <= 0 || !a.group_start ||
+        a.n_groups <= 0 || !a.depth || a.W <= 0 || a.H <= 0 || a.pitch < (size_t)a.W)
+        return fail(SVA_ERR_INVALID_ARG, "bad array arguments");
+    const int32_t* gs = a.group_start;
+    if (gs[0] != 0 || gs[a.n_groups] != a.n_pairs)
+        return fail(SVA_ERR_INVALID_ARG, "group_start must run from 0 to n_pairs");
+    // sizes of 1..32 from 0 to n_pairs: group_start is increasing and inside pairs[]
+    for (int g = 0; g < a.n_groups; g++) {
+        const long long n = (long long)gs[g + 1] - gs[g];
+        if (n <= 0 || n > 32) return fail(SVA_ERR_UNSUPPORTED, "groups of 1..32 pairs");
+    }
+    for (int j = 0; j < a.n_pairs; j++) {
+        const sva_array_pair& q = a.pairs[j];
+        if (q.ref < 0 || q.ref >= a.n_images || q.other < 0 || q.other >= a.n_images ||
+            !a.images[q.ref] || !a.images[q.other] || check_params(q.params))
+            return fail(SVA_ERR_INVALID_ARG, "bad pair " + std::to_string(j));
+        if (group && q.params.lr_check)
+            return fail(SVA_ERR_UNSUPPORTED, "the multi-baseline route has no L/R check");
+    }
+    for (int g = 0; g < a.n_groups; g++) {
+        const std::string of_group = "the pairs of group " + std::to_string(g);
+        const sva_array_pair& p0 = a.pairs[gs[g]];
+        for (int j = gs[g] + 1; j < gs[g + 1]; j++) {
+            const sva_array_pair& q = a.pairs[j];
+            if (!group) {
+                // the fusion rejects one `invalid` value per group
+                if (q.params.invalid != p0.params.invalid)
+                    return fail(SVA_ERR_INVALID_ARG,
+                                "params.invalid differs within group " + std::to_string(g));
+                continue;
+            }
+            // one reference view, one disparity range, one depth scale per group
+            if (q.ref != p0.ref) return fail(SVA_ERR_INVALID_ARG, of_group + " do not share ref");
+            if (q.params.D != p0.params.D || q.params.dmin != p0.params.dmin ||
+                q.params.P1 != p0.params.P1 || q.params.P2 != p0.params.P2 ||
+                q.params.invalid != p0.params.invalid)
+                return fail(SVA_ERR_INVALID_ARG,
+                            of_group + " must share D, dmin, P1, P2 and invalid");
+            const double big = std::max(std::fabs(q.baseline), std::fabs(p0.baseline));
+            if (!mixed && !(std::fabs(q.baseline - p0.baseline) <= 1e-9 * big))
+                return fail(SVA_ERR_INVALID_ARG, of_group + " have different major-axis baselines");
+        }
+    }
+    if (!mixed) return SVA_OK;
+    // every pair's baseline as a ratio of its group's unit
+    ratio.assign(2 * (size_t)a.n_pairs, 0);
+    for (int g = 0; g < a.n_groups; g++)
+        for (int j = gs[g]; j < gs[g + 1]; j++) {
+            int32_t* rj = &ratio[2 * (size_t)j];
+            if (!baseline_ratio(a.pairs[j].baseline, a.unit_baseline[g], rj, rj + 1))
+                return fail(SVA_ERR_INVALID_ARG,
+                            "the baseline of pair " + std::to_string(j) +
+                                " is no num/den (1..8 each) of its group's unit baseline");
+            // t(s) >= s / kMaxRatio - 1: past this s it is too far whatever the
+            // ratio, and up to it mixed_distance's product stays in 32 bits
+            const long long s = (long long)a.pairs[j].params.dmin + a.pairs[j].params.D - 1;
+            if (s > 65537ll * mb::kMaxRatio || mb::mixed_distance((int)s, rj[0], rj[1]) > 65535)
+                return fail(SVA_ERR_INVALID_ARG,
+                            "the match distance of pair " + std::to_string(j) + " exceeds 16 bits");
+        }
+    return SVA_OK;
+}
+
+}  // namespace sva

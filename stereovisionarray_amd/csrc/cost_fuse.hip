@@ -70,65 +70,39 @@ struct FuseRatios {
 
 }  // namespace
 
+// ratios null: cost_fuse_kernel.  Else the mixed instance (§2.2d): ratios[i] =
+// (num, den) of pair i, each in 1..8.
 hipError_t launch_cost_fuse(Ctx& c, const uint8_t* volumes, size_t stride, int n, int W, int H,
-                            int D, int dreal, int dmin, const int32_t* steps, uint8_t* fused) {
+                            int D, int dreal, int dmin, const int32_t* steps,
+                            const int32_t* ratios, uint8_t* fused) {
     if (n < 1 || n > 32 || !paths_supported(D)) return hipErrorInvalidValue;
-    if (dreal <= 0) dreal = D;
-    ScopedKernelTimer t(c, "cost_fuse");
-    FuseSteps k{};
-    for (int i = 0; i < n; i++) {
-        k.sx[i] = (short)steps[2 * i];
-        k.sy[i] = (short)steps[2 * i + 1];
-    }
-    const int nc = D / 16;
-    const unsigned nlanes = (unsigned)((size_t)W * H * nc);   // W*H*D < 2^32 (check_sgm)
-    const dim3 grid((nlanes + 255u) / 256u);
-#define SVA_CF(NC, NM)                                                                          \
-    hipLaunchKernelGGL((cost_fuse_kernel<NC, NM>), grid, dim3(256), 0, c.stream, volumes, stride, \
-                       n, W, H, nlanes, dmin, dreal, k, fused)
-#define SVA_CF_N(NC)                      \
-    do {                                  \
-        if (n <= 4) SVA_CF(NC, 4);        \
-        else if (n <= 8) SVA_CF(NC, 8);   \
-        else if (n <= 16) SVA_CF(NC, 16); \
-        else SVA_CF(NC, 32);              \
-    } while (0)
-    switch (nc) {
-        case 4: SVA_CF_N(4); break;
-        case 8: SVA_CF_N(8); break;
-        case 12: SVA_CF_N(12); break;
-        case 16: SVA_CF_N(16); break;
-        default: return hipErrorInvalidValue;
-    }
-#undef SVA_CF_N
-#undef SVA_CF
-    return hipGetLastError();
-}
-
-// The mixed instance (§2.2d): ratios[i] = (num, den) of pair i, each in 1..8.
-hipError_t launch_cost_fuse_mixed(Ctx& c, const uint8_t* volumes, size_t stride, int n, int W,
-                                  int H, int D, int dreal, int dmin, const int32_t* steps,
-                                  const int32_t* ratios, uint8_t* fused) {
-    if (n < 1 || n > 32 || !paths_supported(D) || !ratios) return hipErrorInvalidValue;
     if (dreal <= 0) dreal = D;
     FuseSteps k{};
     FuseRatios r{};
     for (int i = 0; i < n; i++) {
+        k.sx[i] = (short)steps[2 * i];
+        k.sy[i] = (short)steps[2 * i + 1];
+        if (!ratios) continue;
         const int num = ratios[2 * i], den = ratios[2 * i + 1];
         if (num < 1 || num > mb::kMaxRatio || den < 1 || den > mb::kMaxRatio)
             return hipErrorInvalidValue;
-        k.sx[i] = (short)steps[2 * i];
-        k.sy[i] = (short)steps[2 * i + 1];
         r.num[i] = (unsigned char)num;
         r.den[i] = (unsigned char)den;
     }
-    ScopedKernelTimer t(c, "cost_fuse");
     const int nc = D / 16;
+    if (nc != 4 && nc != 8 && nc != 12 && nc != 16) return hipErrorInvalidValue;
+    ScopedKernelTimer t(c, "cost_fuse");
     const unsigned nlanes = (unsigned)((size_t)W * H * nc);   // W*H*D < 2^32 (check_sgm)
     const dim3 grid((nlanes + 255u) / 256u);
-#define SVA_CF(NC, NM)                                                                       \
-    hipLaunchKernelGGL((cost_fuse_mixed_kernel<NC, NM>), grid, dim3(256), 0, c.stream, volumes, \
-                       stride, n, W, H, nlanes, dmin, dreal, k, r, fused)
+#define SVA_CF(NC, NM)                                                                          \
+    do {                                                                                        \
+        if (ratios)                                                                             \
+            hipLaunchKernelGGL((cost_fuse_mixed_kernel<NC, NM>), grid, dim3(256), 0, c.stream,  \
+                               volumes, stride, n, W, H, nlanes, dmin, dreal, k, r, fused);     \
+        else                                                                                    \
+            hipLaunchKernelGGL((cost_fuse_kernel<NC, NM>), grid, dim3(256), 0, c.stream,        \
+                               volumes, stride, n, W, H, nlanes, dmin, dreal, k, fused);        \
+    } while (0)
 #define SVA_CF_N(NC)                      \
     do {                                  \
         if (n <= 4) SVA_CF(NC, 4);        \
@@ -140,8 +114,7 @@ hipError_t launch_cost_fuse_mixed(Ctx& c, const uint8_t* volumes, size_t stride,
         case 4: SVA_CF_N(4); break;
         case 8: SVA_CF_N(8); break;
         case 12: SVA_CF_N(12); break;
-        case 16: SVA_CF_N(16); break;
-        default: return hipErrorInvalidValue;
+        default: SVA_CF_N(16); break;
     }
 #undef SVA_CF_N
 #undef SVA_CF

@@ -12,10 +12,12 @@
 // through the public per-context entry points (sva_disparity_sgm_d,
 // sva_fuse_depth_d, and sva_disparity_sgm_conf_d / sva_fuse_depth_conf_d for
 // the confidence forms, whose cost planes are gathered like the maps); there
-// is no CPU path.  sva_array_depth_mb shards GROUPS instead (one
-// sva_disparity_sgm_multi_d per reference camera) through the
-// same plan, slots and gather (run_jobs); sva_array_depth_mixed is that route
-// with sva_disparity_sgm_mixed_d per group (§2.2d).
+// is no CPU path.  The four sva_array_depth* entry points fill one ArrayArgs
+// (array_args.h: the arguments and their checks, in one order) and run one
+// array_frame(): its jobs are pairs, or -- sva_array_depth_mb -- GROUPS (one
+// sva_disparity_sgm_multi_d per reference camera, DESIGN.md §2.2c;
+// sva_array_depth_mixed: sva_disparity_sgm_mixed_d, §2.2d), through the same
+// plan, slots and gather (run_jobs), depth step and staged download.
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
@@ -30,6 +32,7 @@
 #include <thread>
 #include <vector>
 
+#include "array_args.h"
 #include "sva_internal.h"
 
 using namespace sva;
@@ -377,12 +380,6 @@ int run_pairs(Multi* m, const Plan& P, const std::vector<const uint8_t*>& left,
                       : sva_disparity_sgm_d(cx, left[j], right[j], W, H, pitch, &prm[j], od, os);
         },
         "pair");
-}
-
-int check_params(const sva_sgm_params& p) {
-    if (!padded_D(p.D) || p.dmin < 0 || (p.dir == 0 && p.dir_y == 0))
-        return SVA_ERR_INVALID_ARG;
-    return SVA_OK;
 }
 
 // ------------------------------------------- host batch (sva_batch_sgm) --
@@ -782,319 +779,197 @@ int upload_views(Multi* m, const uint8_t* const* images, int n_images, int W, in
     return SVA_OK;
 }
 
-// sva_array_depth (conf false: plain matching, median fusion) and
-// sva_array_depth_conf (every pair through the uniqueness filter; `mode` picks
-// the fusion; winner, cost_min, cost_second: nullable host outputs).
-int array_depth(void* mp, const uint8_t* const* images, int n_images, int W, int H, size_t pitch,
-                const sva_array_pair* pairs, int n_pairs, const int32_t* group_start,
-                int n_groups, double f, double pixel_size, bool conf, int uniqueness, int mode,
-                double* depth, uint8_t* n_valid, uint8_t* winner, uint16_t* maps,
-                uint16_t* cost_min, uint16_t* cost_second) {
+// The staged download of a frame's outputs.  Each plane asked for (dst
+// non-null) is registered as (device source, host destination, bytes) with the
+// step it follows and gets the next place in stage_out; queue() copies a
+// step's planes there on down[0], finish() synchronises and copies them out.
+struct Download {
+    struct Plane { const void* src; void* dst; size_t bytes, off; int step; };
+    std::vector<Plane> planes;
+    size_t total = 0;
+
+    void add(int step, const void* src, void* dst, size_t bytes) {
+        if (!dst) return;
+        planes.push_back({src, dst, bytes, total, step});
+        total += bytes;
+    }
+    int queue(Multi* m, int step) const {
+        for (const Plane& p : planes)
+            if (p.step == step)
+                MHIP(m, hipMemcpyAsync((uint8_t*)m->stage_out.ptr + p.off, p.src, p.bytes,
+                                       hipMemcpyDeviceToHost, m->down[0]),
+                     "download");
+        return SVA_OK;
+    }
+    int finish(Multi* m) const {
+        MHIP(m, hipStreamSynchronize(m->down[0]), "synchronize");
+        for (const Plane& p : planes)
+            std::memcpy(p.dst, (const uint8_t*)m->stage_out.ptr + p.off, p.bytes);
+        return SVA_OK;
+    }
+};
+
+// One camera-array frame: sva_array_depth, _conf, _mb and _mixed (array_args.h
+// has their arguments and checks).  A job is a pair (ArrayRoute::Pairs: every
+// pair through sva_disparity_sgm_d or, with conf, sva_disparity_sgm_conf_d; a
+// group's maps are fused by `mode`) or a GROUP (group g's
+// pairs go through one sva_disparity_sgm_multi_d on device g mod n_devices,
+// and its one map becomes depth at the group's baseline; GroupsMixed, §2.2d:
+// sva_disparity_sgm_mixed_d, and the depth scale is the unit baseline).
+int array_frame(void* mp, const ArrayArgs& a) {
     Multi* m = as_multi(mp);
     if (!m) return SVA_ERR_INVALID_ARG;
-    if (conf) {
-        if (mode != SVA_FUSE_MIN_COST && mode != SVA_FUSE_MAX_MARGIN && mode != SVA_FUSE_MEDIAN)
-            return m->fail(SVA_ERR_INVALID_ARG, "unknown fusion mode");
-        if (uniqueness < 0 || uniqueness > 100)
-            return m->fail(SVA_ERR_INVALID_ARG, "uniqueness must be 0..100");
-        if (winner && mode == SVA_FUSE_MEDIAN)
-            return m->fail(SVA_ERR_INVALID_ARG, "the median has no winner map");
-    }
-    if (!images || n_images <= 0 || !pairs || n_pairs <= 0 || !group_start || n_groups <= 0 ||
-        !depth || W <= 0 || H <= 0 || pitch < (size_t)W)
-        return m->fail(SVA_ERR_INVALID_ARG, "bad array arguments");
-    if (group_start[0] != 0 || group_start[n_groups] != n_pairs)
-        return m->fail(SVA_ERR_INVALID_ARG, "group_start must run from 0 to n_pairs");
-    for (int g = 0; g < n_groups; g++) {
-        const int n = group_start[g + 1] - group_start[g];
-        if (n <= 0 || n > 32) return m->fail(SVA_ERR_UNSUPPORTED, "groups of 1..32 pairs");
-        // the fusion rejects one `invalid` value per group
-        for (int j = group_start[g] + 1; j < group_start[g + 1]; j++)
-            if (pairs[j].params.invalid != pairs[group_start[g]].params.invalid)
-                return m->fail(SVA_ERR_INVALID_ARG,
-                               "params.invalid differs within group " + std::to_string(g));
-    }
-    for (int j = 0; j < n_pairs; j++) {
-        const sva_array_pair& q = pairs[j];
-        if (q.ref < 0 || q.ref >= n_images || q.other < 0 || q.other >= n_images ||
-            !images[q.ref] || !images[q.other] || check_params(q.params))
-            return m->fail(SVA_ERR_INVALID_ARG, "bad pair " + std::to_string(j));
-    }
+    std::string msg;
+    std::vector<int32_t> ratio;   // GroupsMixed: every pair's (num, den)
+    if (int st = check_array_args(a, msg, ratio)) return m->fail(st, msg);
+    const bool group = a.route != ArrayRoute::Pairs;
+    const int W = a.W, H = a.H, n_pairs = a.n_pairs, n_groups = a.n_groups;
+    const int n_jobs = group ? n_groups : n_pairs;
+    const sva_array_pair* pairs = a.pairs;
+    const int32_t* gs = a.group_start;
     ev_reset(m);
     const size_t np = (size_t)W * H;
     Plan P;
-    make_plan(m->nd(), m->spd, n_pairs, P);
+    make_plan(m->nd(), m->spd, n_jobs, P);
+    // job k is pairs[first[k] .. first[k + 1])
+    std::vector<int32_t> first(n_jobs + 1), dev_of(n_pairs);
+    for (int k = 0; k <= n_jobs; k++) first[k] = group ? gs[k] : k;
+    for (int k = 0; k < n_jobs; k++)
+        for (int j = first[k]; j < first[k + 1]; j++) dev_of[j] = P.dev[k];
     // 1-2. the views each device needs, uploaded on its copy stream
     std::vector<std::vector<int>> slot_of;
     std::vector<std::vector<hipEvent_t>> up_ev;
-    if (int st = upload_views(m, images, n_images, W, H, pitch, pairs, n_pairs, P.dev, slot_of, up_ev))
+    if (int st = upload_views(m, a.images, a.n_images, W, H, a.pitch, pairs, n_pairs, dev_of,
+                              slot_of, up_ev))
         return st;
-    // 3. pairs + gather into maps0 on device 0
+    // 3. jobs + gather into maps0 on device 0
     MHIP(m, hipSetDevice(m->devices[0]), "hipSetDevice");
     MHIP(m, hipStreamSynchronize(m->st(0, 0)), "synchronize");   // maps0/depth0 reuse
-    MHIP(m, m->maps0.ensure(np * 2 * n_pairs), "map workspace");
+    const size_t plane = np * 2 * n_jobs;
+    MHIP(m, m->maps0.ensure(plane), "map workspace");
     MHIP(m, m->depth0.ensure(np * 8 * n_groups), "depth workspace");
-    MHIP(m, m->nvalid0.ensure(np * n_groups), "depth workspace");
+    if (!group) MHIP(m, m->nvalid0.ensure(np * n_groups), "depth workspace");
     // the cost planes the fusion mode reads, and those the caller asked for
-    const bool want_min = conf && (mode != SVA_FUSE_MEDIAN || cost_min);
-    const bool want_sec = conf && (mode == SVA_FUSE_MAX_MARGIN || cost_second);
-    const size_t plane = np * 2 * n_pairs;
+    const bool want_min = a.conf && (a.mode != SVA_FUSE_MEDIAN || a.cost_min);
+    const bool want_sec = a.conf && (a.mode == SVA_FUSE_MAX_MARGIN || a.cost_second);
     if (want_min || want_sec)
         MHIP(m, m->conf0.ensure(plane * ((want_min ? 1 : 0) + (want_sec ? 1 : 0))), "cost planes");
-    if (winner) MHIP(m, m->winner0.ensure(np * n_groups), "winner workspace");
-    uint16_t* cmin0 = want_min ? (uint16_t*)m->conf0.ptr : nullptr;
-    uint16_t* csec0 = want_sec ? (uint16_t*)m->conf0.ptr + (want_min ? np * n_pairs : 0) : nullptr;
-    uint8_t* win0 = winner ? (uint8_t*)m->winner0.ptr : nullptr;
-    std::vector<const uint8_t*> l(n_pairs), r(n_pairs);
-    std::vector<sva_sgm_params> prm(n_pairs);
-    std::vector<std::vector<hipEvent_t>> waits(n_pairs);
-    for (int j = 0; j < n_pairs; j++) {
-        const int d = P.dev[j];
-        const uint8_t* base = (const uint8_t*)m->images[d].ptr;
-        l[j] = base + (size_t)slot_of[d][pairs[j].ref] * np;
-        r[j] = base + (size_t)slot_of[d][pairs[j].other] * np;
-        prm[j] = pairs[j].params;
-        prm[j].subpixel = 0;
-        waits[j] = {up_ev[d][pairs[j].ref], up_ev[d][pairs[j].other]};
-    }
+    if (a.winner) MHIP(m, m->winner0.ensure(np * n_groups), "winner workspace");
     uint16_t* maps0 = (uint16_t*)m->maps0.ptr;
     ConfPlanes cp;
-    cp.uniqueness = uniqueness;
-    cp.cost_min = cmin0;
-    cp.cost_second = csec0;
-    int st = run_pairs(m, P, l, r, prm, waits, W, H, W, maps0, nullptr, conf ? &cp : nullptr);
+    cp.uniqueness = a.uniqueness;
+    cp.cost_min = want_min ? (uint16_t*)m->conf0.ptr : nullptr;
+    cp.cost_second = want_sec ? (uint16_t*)m->conf0.ptr + (want_min ? np * n_jobs : 0) : nullptr;
+    // per job: its reference view, its matched views and steps, its uploads
+    std::vector<const uint8_t*> ref(n_jobs);
+    std::vector<std::vector<const uint8_t*>> others(n_jobs);
+    std::vector<std::vector<int32_t>> steps(n_jobs);
+    std::vector<sva_sgm_params> prm(n_jobs);
+    std::vector<std::vector<hipEvent_t>> waits(n_jobs);
+    for (int k = 0; k < n_jobs; k++) {
+        const int d = P.dev[k], j0 = first[k];
+        const uint8_t* base = (const uint8_t*)m->images[d].ptr;
+        ref[k] = base + (size_t)slot_of[d][pairs[j0].ref] * np;
+        waits[k].push_back(up_ev[d][pairs[j0].ref]);
+        for (int j = j0; j < first[k + 1]; j++) {
+            others[k].push_back(base + (size_t)slot_of[d][pairs[j].other] * np);
+            steps[k].push_back(pairs[j].params.dir);
+            steps[k].push_back(pairs[j].params.dir_y);
+            waits[k].push_back(up_ev[d][pairs[j].other]);
+        }
+        prm[k] = pairs[j0].params;
+        prm[k].subpixel = 0;
+    }
+    int st = run_jobs(
+        m, P, waits, W, H, maps0, nullptr, std::vector<char>(n_jobs, 0), a.conf ? &cp : nullptr,
+        [&](int k, void* cx, uint16_t* od, float*, uint16_t* omin, uint16_t* osec) {
+            const int n = (int)others[k].size();
+            switch (a.route) {
+                case ArrayRoute::GroupsMixed:
+                    return sva_disparity_sgm_mixed_d(cx, ref[k], others[k].data(), steps[k].data(),
+                                                     &ratio[2 * (size_t)first[k]], n, W, H, W,
+                                                     &prm[k], a.uniqueness, od, nullptr, omin, osec);
+                case ArrayRoute::Groups:
+                    return sva_disparity_sgm_multi_d(cx, ref[k], others[k].data(), steps[k].data(),
+                                                     n, W, H, W, &prm[k], a.uniqueness, od, nullptr,
+                                                     omin, osec);
+                default:
+                    return a.conf ? sva_disparity_sgm_conf_d(cx, ref[k], others[k][0], W, H, W,
+                                                             &prm[k], a.uniqueness, od, nullptr,
+                                                             omin, osec)
+                                  : sva_disparity_sgm_d(cx, ref[k], others[k][0], W, H, W, &prm[k],
+                                                        od, nullptr);
+            }
+        },
+        group ? "group" : "pair");
     if (st) return st;
-    // 4. fusion per group on device 0, each group's download as soon as it is fused
+    // 4. depth per group on device 0 -- the fusion of its pairs' maps, or the
+    // depth of its one map (the median of one is the map's own depth) -- each
+    // group's download as soon as it is done, the per-job planes at the end
     MHIP(m, hipSetDevice(m->devices[0]), "hipSetDevice");
-    // pinned staging: depth, n_valid, winner per group, then the per-pair planes
-    const size_t o_nv = np * 8 * n_groups, o_win = o_nv + (n_valid ? np * n_groups : 0);
-    const size_t o_maps = o_win + (winner ? np * n_groups : 0);
-    const size_t o_min = o_maps + (maps ? plane : 0), o_sec = o_min + (cost_min ? plane : 0);
-    MHIP(m, m->stage_out.ensure(o_sec + (cost_second ? plane : 0)), "pinned staging");
-    uint8_t* pout = (uint8_t*)m->stage_out.ptr;
     double* depth0 = (double*)m->depth0.ptr;
-    uint8_t* nv0 = (uint8_t*)m->nvalid0.ptr;
+    uint8_t* nv0 = group ? nullptr : (uint8_t*)m->nvalid0.ptr;
+    uint8_t* win0 = a.winner ? (uint8_t*)m->winner0.ptr : nullptr;
+    Download dl;
+    for (int g = 0; g < n_groups; g++) {
+        const size_t o = (size_t)g * np;
+        dl.add(g, depth0 + o, a.depth + o, np * 8);
+        if (nv0 && a.n_valid) dl.add(g, nv0 + o, a.n_valid + o, np);
+        if (win0) dl.add(g, win0 + o, a.winner + o, np);
+    }
+    dl.add(n_groups, maps0, a.maps, plane);
+    dl.add(n_groups, cp.cost_min, a.cost_min, plane);
+    dl.add(n_groups, cp.cost_second, a.cost_second, plane);
+    MHIP(m, m->stage_out.ensure(dl.total), "pinned staging");
     std::vector<double> bases(n_pairs);
     for (int j = 0; j < n_pairs; j++) bases[j] = pairs[j].baseline;
     for (int g = 0; g < n_groups; g++) {
-        const int j0 = group_start[g], n = group_start[g + 1] - j0;
-        if (conf && mode != SVA_FUSE_MEDIAN)
-            st = sva_fuse_depth_conf_d(m->ctx[0], maps0 + (size_t)j0 * np, cmin0 + (size_t)j0 * np,
-                                       csec0 ? csec0 + (size_t)j0 * np : nullptr, n, W, H,
-                                       &bases[j0], f, pixel_size, pairs[j0].params.invalid, mode,
-                                       depth0 + (size_t)g * np, nv0 + (size_t)g * np,
-                                       win0 ? win0 + (size_t)g * np : nullptr);
+        const int j0 = gs[g];
+        const size_t o = (size_t)g * np, o_maps = (size_t)(group ? g : j0) * np;
+        const int n_maps = group ? 1 : gs[g + 1] - j0;
+        const double* base =
+            a.route == ArrayRoute::GroupsMixed ? &a.unit_baseline[g] : &bases[j0];
+        if (a.conf && a.mode != SVA_FUSE_MEDIAN)
+            st = sva_fuse_depth_conf_d(m->ctx[0], maps0 + o_maps, cp.cost_min + o_maps,
+                                       cp.cost_second ? cp.cost_second + o_maps : nullptr, n_maps,
+                                       W, H, base, a.f, a.pixel_size, pairs[j0].params.invalid,
+                                       a.mode, depth0 + o, nv0 ? nv0 + o : nullptr,
+                                       win0 ? win0 + o : nullptr);
         else
-            st = sva_fuse_depth_d(m->ctx[0], maps0 + (size_t)j0 * np, n, W, H, &bases[j0], f,
-                                  pixel_size, pairs[j0].params.invalid, depth0 + (size_t)g * np,
-                                  nv0 + (size_t)g * np);
-        if (st) return m->ctx_fail(st, m->ctx[0], "fuse");
+            st = sva_fuse_depth_d(m->ctx[0], maps0 + o_maps, n_maps, W, H, base, a.f, a.pixel_size,
+                                  pairs[j0].params.invalid, depth0 + o, nv0 ? nv0 + o : nullptr);
+        if (st) return m->ctx_fail(st, m->ctx[0], group ? "depth" : "fuse");
         if ((st = stream_after(m, 0, m->st(0, 0), m->down[0]))) return st;
-        MHIP(m, hipMemcpyAsync(pout + (size_t)g * np * 8, depth0 + (size_t)g * np, np * 8,
-                               hipMemcpyDeviceToHost, m->down[0]),
-             "download");
-        if (n_valid)
-            MHIP(m, hipMemcpyAsync(pout + o_nv + (size_t)g * np, nv0 + (size_t)g * np, np,
-                                   hipMemcpyDeviceToHost, m->down[0]),
-                 "download");
-        if (winner)
-            MHIP(m, hipMemcpyAsync(pout + o_win + (size_t)g * np, win0 + (size_t)g * np, np,
-                                   hipMemcpyDeviceToHost, m->down[0]),
-                 "download");
+        if ((st = dl.queue(m, g))) return st;
     }
-    if (maps)
-        MHIP(m, hipMemcpyAsync(pout + o_maps, maps0, plane, hipMemcpyDeviceToHost, m->down[0]),
-             "download");
-    if (cost_min)
-        MHIP(m, hipMemcpyAsync(pout + o_min, cmin0, plane, hipMemcpyDeviceToHost, m->down[0]),
-             "download");
-    if (cost_second)
-        MHIP(m, hipMemcpyAsync(pout + o_sec, csec0, plane, hipMemcpyDeviceToHost, m->down[0]),
-             "download");
-    MHIP(m, hipStreamSynchronize(m->down[0]), "synchronize");
-    std::memcpy(depth, pout, np * 8 * n_groups);
-    if (n_valid) std::memcpy(n_valid, pout + o_nv, np * n_groups);
-    if (winner) std::memcpy(winner, pout + o_win, np * n_groups);
-    if (maps) std::memcpy(maps, pout + o_maps, plane);
-    if (cost_min) std::memcpy(cost_min, pout + o_min, plane);
-    if (cost_second) std::memcpy(cost_second, pout + o_sec, plane);
-    return SVA_OK;
+    if ((st = dl.queue(m, n_groups))) return st;
+    return dl.finish(m);
 }
 
-// The ratio num/den (both in 1..8) that baseline / unit equals within 1e-9
-// relative: den ascending, the first hit (so the reduced form).  False if none.
-bool baseline_ratio(double baseline, double unit, int32_t* num, int32_t* den) {
-    if (!(unit > 0) || !(baseline > 0)) return false;
-    const double r = baseline / unit;
-    for (int d = 1; d <= 8; d++)
-        for (int n = 1; n <= 8; n++)
-            if (std::fabs(r * d - n) <= 1e-9 * n) {
-                *num = n;
-                *den = d;
-                return true;
-            }
-    return false;
-}
-
-// sva_array_depth_mb: the multi-baseline array route.  The
-// job is the GROUP: group g's pairs go through one sva_disparity_sgm_multi_d
-// on device g mod n_devices, and one map per group is gathered and turned
-// into depth.  unit_baseline set: sva_array_depth_mixed (§2.2d) -- a group's
-// baselines are rational multiples of unit_baseline[g], its call is
-// sva_disparity_sgm_mixed_d, and its depth scale is the unit baseline.
-int array_depth_mb(void* mp, const uint8_t* const* images, int n_images, int W, int H, size_t pitch,
-                   const sva_array_pair* pairs, int n_pairs, const int32_t* group_start,
-                   int n_groups, double f, double pixel_size, int uniqueness,
-                   const double* unit_baseline, bool mixed, double* depth, uint16_t* maps,
-                   uint16_t* cost_min, uint16_t* cost_second) {
-    Multi* m = as_multi(mp);
-    if (!m) return SVA_ERR_INVALID_ARG;
-    if (mixed && !unit_baseline) return m->fail(SVA_ERR_INVALID_ARG, "null unit_baseline");
-    if (uniqueness < 0 || uniqueness > 100)
-        return m->fail(SVA_ERR_INVALID_ARG, "uniqueness must be 0..100");
-    if (!images || n_images <= 0 || !pairs || n_pairs <= 0 || !group_start || n_groups <= 0 ||
-        !depth || W <= 0 || H <= 0 || pitch < (size_t)W)
-        return m->fail(SVA_ERR_INVALID_ARG, "bad array arguments");
-    if (group_start[0] != 0 || group_start[n_groups] != n_pairs)
-        return m->fail(SVA_ERR_INVALID_ARG, "group_start must run from 0 to n_pairs");
-    for (int j = 0; j < n_pairs; j++) {
-        const sva_array_pair& q = pairs[j];
-        if (q.ref < 0 || q.ref >= n_images || q.other < 0 || q.other >= n_images ||
-            !images[q.ref] || !images[q.other] || check_params(q.params))
-            return m->fail(SVA_ERR_INVALID_ARG, "bad pair " + std::to_string(j));
-        if (q.params.lr_check)
-            return m->fail(SVA_ERR_UNSUPPORTED, "the multi-baseline route has no L/R check");
-    }
-    for (int g = 0; g < n_groups; g++) {
-        const int j0 = group_start[g], n = group_start[g + 1] - j0;
-        if (n <= 0 || n > 32) return m->fail(SVA_ERR_UNSUPPORTED, "groups of 1..32 pairs");
-        // one reference view, one disparity range, one depth scale per group
-        const sva_array_pair& a = pairs[j0];
-        for (int j = j0 + 1; j < j0 + n; j++) {
-            const sva_array_pair& q = pairs[j];
-            if (q.ref != a.ref)
-                return m->fail(SVA_ERR_INVALID_ARG,
-                               "the pairs of group " + std::to_string(g) + " do not share ref");
-            if (q.params.D != a.params.D || q.params.dmin != a.params.dmin ||
-                q.params.P1 != a.params.P1 || q.params.P2 != a.params.P2 ||
-                q.params.invalid != a.params.invalid)
-                return m->fail(SVA_ERR_INVALID_ARG, "the pairs of group " + std::to_string(g) +
-                                                        " must share D, dmin, P1, P2 and invalid");
-            const double big = std::max(std::fabs(q.baseline), std::fabs(a.baseline));
-            if (!mixed && !(std::fabs(q.baseline - a.baseline) <= 1e-9 * big))
-                return m->fail(SVA_ERR_INVALID_ARG, "the pairs of group " + std::to_string(g) +
-                                                        " have different major-axis baselines");
-        }
-    }
-    // mixed: every pair's baseline as a ratio of its group's unit
-    std::vector<int32_t> ratio(mixed ? 2 * (size_t)n_pairs : 0);
-    if (mixed)
-        for (int g = 0; g < n_groups; g++)
-            for (int j = group_start[g]; j < group_start[g + 1]; j++) {
-                int32_t* r = &ratio[2 * (size_t)j];
-                if (!baseline_ratio(pairs[j].baseline, unit_baseline[g], r, r + 1))
-                    return m->fail(SVA_ERR_INVALID_ARG,
-                                   "the baseline of pair " + std::to_string(j) +
-                                       " is no num/den (1..8 each) of its group's unit baseline");
-                const sva_sgm_params& q = pairs[j].params;
-                if ((2ll * (q.dmin + q.D - 1) * r[0] + r[1]) / (2 * r[1]) > 65535)
-                    return m->fail(SVA_ERR_INVALID_ARG, "the match distance of pair " +
-                                                            std::to_string(j) + " exceeds 16 bits");
-            }
-    ev_reset(m);
-    const size_t np = (size_t)W * H;
-    Plan P;
-    make_plan(m->nd(), m->spd, n_groups, P);
-    std::vector<int32_t> dev_of(n_pairs);
-    for (int g = 0; g < n_groups; g++)
-        for (int j = group_start[g]; j < group_start[g + 1]; j++) dev_of[j] = P.dev[g];
-    std::vector<std::vector<int>> slot_of;
-    std::vector<std::vector<hipEvent_t>> up_ev;
-    if (int st = upload_views(m, images, n_images, W, H, pitch, pairs, n_pairs, dev_of, slot_of,
-                              up_ev))
-        return st;
-    MHIP(m, hipSetDevice(m->devices[0]), "hipSetDevice");
-    MHIP(m, hipStreamSynchronize(m->st(0, 0)), "synchronize");   // maps0/depth0 reuse
-    const size_t plane = np * 2 * n_groups;
-    MHIP(m, m->maps0.ensure(plane), "map workspace");
-    MHIP(m, m->depth0.ensure(np * 8 * n_groups), "depth workspace");
-    if (cost_min || cost_second)
-        MHIP(m, m->conf0.ensure(plane * ((cost_min ? 1 : 0) + (cost_second ? 1 : 0))),
-             "cost planes");
-    uint16_t* maps0 = (uint16_t*)m->maps0.ptr;
-    ConfPlanes cp;
-    cp.uniqueness = uniqueness;
-    cp.cost_min = cost_min ? (uint16_t*)m->conf0.ptr : nullptr;
-    cp.cost_second =
-        cost_second ? (uint16_t*)m->conf0.ptr + (cost_min ? np * n_groups : 0) : nullptr;
-    // per group: its reference view, its matched views and steps, its uploads
-    std::vector<std::vector<const uint8_t*>> others(n_groups);
-    std::vector<std::vector<int32_t>> steps(n_groups);
-    std::vector<const uint8_t*> ref(n_groups);
-    std::vector<sva_sgm_params> prm(n_groups);
-    std::vector<std::vector<hipEvent_t>> waits(n_groups);
-    for (int g = 0; g < n_groups; g++) {
-        const int d = P.dev[g], j0 = group_start[g];
-        const uint8_t* base = (const uint8_t*)m->images[d].ptr;
-        ref[g] = base + (size_t)slot_of[d][pairs[j0].ref] * np;
-        waits[g].push_back(up_ev[d][pairs[j0].ref]);
-        for (int j = j0; j < group_start[g + 1]; j++) {
-            others[g].push_back(base + (size_t)slot_of[d][pairs[j].other] * np);
-            steps[g].push_back(pairs[j].params.dir);
-            steps[g].push_back(pairs[j].params.dir_y);
-            waits[g].push_back(up_ev[d][pairs[j].other]);
-        }
-        prm[g] = pairs[j0].params;
-        prm[g].subpixel = 0;
-    }
-    int st = run_jobs(
-        m, P, waits, W, H, maps0, nullptr, std::vector<char>(n_groups, 0), &cp,
-        [&](int g, void* cx, uint16_t* od, float*, uint16_t* omin, uint16_t* osec) {
-            const int n = (int)others[g].size();
-            return mixed ? sva_disparity_sgm_mixed_d(cx, ref[g], others[g].data(), steps[g].data(),
-                                                     &ratio[2 * (size_t)group_start[g]], n, W, H, W,
-                                                     &prm[g], uniqueness, od, nullptr, omin, osec)
-                         : sva_disparity_sgm_multi_d(cx, ref[g], others[g].data(), steps[g].data(),
-                                                     n, W, H, W, &prm[g], uniqueness, od, nullptr,
-                                                     omin, osec);
-        },
-        "group");
-    if (st) return st;
-    // depth per group on device 0 (one map: the median of one is the map's own
-    // depth), each group's download as soon as it is done
-    MHIP(m, hipSetDevice(m->devices[0]), "hipSetDevice");
-    const size_t o_maps = np * 8 * n_groups, o_min = o_maps + (maps ? plane : 0);
-    const size_t o_sec = o_min + (cost_min ? plane : 0);
-    MHIP(m, m->stage_out.ensure(o_sec + (cost_second ? plane : 0)), "pinned staging");
-    uint8_t* pout = (uint8_t*)m->stage_out.ptr;
-    double* depth0 = (double*)m->depth0.ptr;
-    for (int g = 0; g < n_groups; g++) {
-        const sva_array_pair& a = pairs[group_start[g]];
-        st = sva_fuse_depth_d(m->ctx[0], maps0 + (size_t)g * np, 1, W, H,
-                              mixed ? &unit_baseline[g] : &a.baseline, f,
-                              pixel_size, a.params.invalid, depth0 + (size_t)g * np, nullptr);
-        if (st) return m->ctx_fail(st, m->ctx[0], "depth");
-        if ((st = stream_after(m, 0, m->st(0, 0), m->down[0]))) return st;
-        MHIP(m, hipMemcpyAsync(pout + (size_t)g * np * 8, depth0 + (size_t)g * np, np * 8,
-                               hipMemcpyDeviceToHost, m->down[0]),
-             "download");
-    }
-    if (maps)
-        MHIP(m, hipMemcpyAsync(pout + o_maps, maps0, plane, hipMemcpyDeviceToHost, m->down[0]),
-             "download");
-    if (cost_min)
-        MHIP(m, hipMemcpyAsync(pout + o_min, cp.cost_min, plane, hipMemcpyDeviceToHost, m->down[0]),
-             "download");
-    if (cost_second)
-        MHIP(m, hipMemcpyAsync(pout + o_sec, cp.cost_second, plane, hipMemcpyDeviceToHost,
-                               m->down[0]),
-             "download");
-    MHIP(m, hipStreamSynchronize(m->down[0]), "synchronize");
-    std::memcpy(depth, pout, np * 8 * n_groups);
-    if (maps) std::memcpy(maps, pout + o_maps, plane);
-    if (cost_min) std::memcpy(cost_min, pout + o_min, plane);
-    if (cost_second) std::memcpy(cost_second, pout + o_sec, plane);
-    return SVA_OK;
+// What the four entry points share; as it stands, sva_array_depth's: the pair
+// route, plain matching, median fusion.
+ArrayArgs frame_args(const uint8_t* const* images, int n_images, int W, int H, size_t pitch,
+                     const sva_array_pair* pairs, int n_pairs, const int32_t* group_start,
+                     int n_groups, double f, double pixel_size, int uniqueness, double* depth,
+                     uint16_t* maps, uint16_t* cost_min, uint16_t* cost_second) {
+    ArrayArgs a;
+    a.images = images;
+    a.n_images = n_images;
+    a.W = W;
+    a.H = H;
+    a.pitch = pitch;
+    a.pairs = pairs;
+    a.n_pairs = n_pairs;
+    a.group_start = group_start;
+    a.n_groups = n_groups;
+    a.f = f;
+    a.pixel_size = pixel_size;
+    a.uniqueness = uniqueness;
+    a.depth = depth;
+    a.maps = maps;
+    a.cost_min = cost_min;
+    a.cost_second = cost_second;
+    return a;
 }
 }  // namespace
 
@@ -1119,9 +994,10 @@ int sva_array_depth(void* mp, const uint8_t* const* images, int n_images, int W,
                     size_t pitch, const sva_array_pair* pairs, int n_pairs,
                     const int32_t* group_start, int n_groups, double f, double pixel_size,
                     double* depth, uint8_t* n_valid, uint16_t* maps) {
-    return array_depth(mp, images, n_images, W, H, pitch, pairs, n_pairs, group_start, n_groups, f,
-                       pixel_size, false, 0, SVA_FUSE_MEDIAN, depth, n_valid, nullptr, maps,
-                       nullptr, nullptr);
+    ArrayArgs a = frame_args(images, n_images, W, H, pitch, pairs, n_pairs, group_start, n_groups,
+                             f, pixel_size, 0, depth, maps, nullptr, nullptr);
+    a.n_valid = n_valid;
+    return array_frame(mp, a);
 }
 
 int sva_array_depth_conf(void* mp, const uint8_t* const* images, int n_images, int W, int H,
@@ -1130,9 +1006,13 @@ int sva_array_depth_conf(void* mp, const uint8_t* const* images, int n_images, i
                          int uniqueness, int mode, double* depth, uint8_t* n_valid,
                          uint8_t* winner, uint16_t* maps, uint16_t* cost_min,
                          uint16_t* cost_second) {
-    return array_depth(mp, images, n_images, W, H, pitch, pairs, n_pairs, group_start, n_groups, f,
-                       pixel_size, true, uniqueness, mode, depth, n_valid, winner, maps, cost_min,
-                       cost_second);
+    ArrayArgs a = frame_args(images, n_images, W, H, pitch, pairs, n_pairs, group_start, n_groups,
+                             f, pixel_size, uniqueness, depth, maps, cost_min, cost_second);
+    a.conf = true;
+    a.mode = mode;
+    a.n_valid = n_valid;
+    a.winner = winner;
+    return array_frame(mp, a);
 }
 
 int sva_array_depth_mb(void* mp, const uint8_t* const* images, int n_images, int W, int H,
@@ -1140,9 +1020,11 @@ int sva_array_depth_mb(void* mp, const uint8_t* const* images, int n_images, int
                        const int32_t* group_start, int n_groups, double f, double pixel_size,
                        int uniqueness, double* depth, uint16_t* maps, uint16_t* cost_min,
                        uint16_t* cost_second) {
-    return array_depth_mb(mp, images, n_images, W, H, pitch, pairs, n_pairs, group_start, n_groups,
-                          f, pixel_size, uniqueness, nullptr, false, depth, maps, cost_min,
-                          cost_second);
+    ArrayArgs a = frame_args(images, n_images, W, H, pitch, pairs, n_pairs, group_start, n_groups,
+                             f, pixel_size, uniqueness, depth, maps, cost_min, cost_second);
+    a.route = ArrayRoute::Groups;
+    a.conf = true;
+    return array_frame(mp, a);
 }
 
 int sva_array_depth_mixed(void* mp, const uint8_t* const* images, int n_images, int W, int H,
@@ -1150,9 +1032,12 @@ int sva_array_depth_mixed(void* mp, const uint8_t* const* images, int n_images, 
                           const int32_t* group_start, int n_groups, const double* unit_baseline,
                           double f, double pixel_size, int uniqueness, double* depth,
                           uint16_t* maps, uint16_t* cost_min, uint16_t* cost_second) {
-    return array_depth_mb(mp, images, n_images, W, H, pitch, pairs, n_pairs, group_start, n_groups,
-                          f, pixel_size, uniqueness, unit_baseline, true, depth, maps, cost_min,
-                          cost_second);
+    ArrayArgs a = frame_args(images, n_images, W, H, pitch, pairs, n_pairs, group_start, n_groups,
+                             f, pixel_size, uniqueness, depth, maps, cost_min, cost_second);
+    a.route = ArrayRoute::GroupsMixed;
+    a.conf = true;
+    a.unit_baseline = unit_baseline;
+    return array_frame(mp, a);
 }
 
 }  // extern "C"

@@ -1111,17 +1111,13 @@ int run_sgm_multi_device(Ctx* c, const uint8_t* ref, const uint8_t* const* other
                                        C + (size_t)i * nv, cl, cr, true, &what);
         if (e != hipSuccess) return hip_fail(c, e, what);
     }
-    uint8_t* Cf = C + (size_t)n * nv;
-    if (!mixed) {
-        SVA_HIP(c, launch_cost_fuse(*c, C, nv, n, W, H, Dp, p->D, p->dmin, steps, Cf),
-                "fuse launch");
-        return paths_wta(c, Cf, W, H, p, Dp, disp, sub, cf);
-    }
     // The other pairs, after every unit pair: a split-route unit pair fills both
     // census maps itself, so the reference map that the mixed pairs share is
     // formed only once none of those is left to run (one stream: in order).
-    SVA_HIP(c, census_maps(), "census workspace");
-    SVA_HIP(c, launch_census(*c, ref, W, H, pitch, cl), "census launch");
+    if (mixed) {
+        SVA_HIP(c, census_maps(), "census workspace");
+        SVA_HIP(c, launch_census(*c, ref, W, H, pitch, cl), "census launch");
+    }
     for (int i = 0; i < n; i++) {
         if (unit(i)) continue;
         SVA_HIP(c, launch_census(*c, others[i], W, H, pitch, cr), "census launch");
@@ -1129,7 +1125,11 @@ int run_sgm_multi_device(Ctx* c, const uint8_t* ref, const uint8_t* const* other
                                      ratios[2 * i], ratios[2 * i + 1], C + (size_t)i * nv, p->D),
                 "cost launch");
     }
-    SVA_HIP(c, launch_cost_fuse_mixed(*c, C, nv, n, W, H, Dp, p->D, p->dmin, steps, ratios, Cf),
+    // a group whose ratios are all 1/1 is an equal-baseline group
+    uint8_t* Cf = C + (size_t)n * nv;
+    SVA_HIP(c,
+            launch_cost_fuse(*c, C, nv, n, W, H, Dp, p->D, p->dmin, steps, mixed ? ratios : nullptr,
+                             Cf),
             "fuse launch");
     return paths_wta(c, Cf, W, H, p, Dp, disp, sub, cf);
 }
@@ -1225,9 +1225,8 @@ int cost_fuse_d(void* ctx, const uint8_t* volumes, size_t stride, int n, int W, 
     if (n > 1 && stride < (size_t)W * H * (size_t)D)
         return fail(c, SVA_ERR_INVALID_ARG, "stride smaller than one volume");
     SVA_HIP(c,
-            mixed ? launch_cost_fuse_mixed(*c, volumes, stride, n, W, H, D, dreal, dmin, steps, red,
-                                           fused)
-                  : launch_cost_fuse(*c, volumes, stride, n, W, H, D, dreal, dmin, steps, fused),
+            launch_cost_fuse(*c, volumes, stride, n, W, H, D, dreal, dmin, steps,
+                             mixed ? red : nullptr, fused),
             "fuse launch");
     return SVA_OK;
 }

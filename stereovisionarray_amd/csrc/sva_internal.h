@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "sva.h"
+#include "sva_native_d.h"
 #include "sva_tuning.h"
 
 namespace sva {
@@ -210,11 +211,6 @@ struct TileGeom {
 };
 TileGeom tile_geom(int W, int H, int D);
 bool paths_supported(int D);
-// Native volume width of a frame with D disparities: 64, 128, 192 or 256
-// (the smallest >= D), 0 when D is outside 1..256.
-inline int padded_D(int D) {
-    return D <= 0 ? 0 : D <= 64 ? 64 : D <= 128 ? 128 : D <= 192 ? 192 : D <= 256 ? 256 : 0;
-}
 // wta_hv.hip -- the tile pipeline's final kernel: horizontal + vertical
 // recompute from the checkpoints of launch_paths(.., CK, CKV), sum with the
 // four diagonal volumes L4, WTA.  dreal < D: a padded frame (DESIGN.md
@@ -254,15 +250,14 @@ hipError_t launch_cost2(Ctx& c, const uint64_t* cl, const uint64_t* cr, int W, i
 // volumes [H][W][D] (native D), volume i at volumes + i * stride, of one
 // reference image matched along steps[i] = (sx, sy), into `fused`: per cell the
 // mean (rounded half up) over the pairs whose matched pixel is inside the
-// image, 62 where none is, 255 at d >= dreal (0 = D).
+// image, 62 where none is, 255 at d >= dreal (0 = D).  ratios null: equal
+// baselines.  Else the mixed-baseline instance: pair i's
+// major-axis baseline is ratios[2i] / ratios[2i+1] of the group's unit baseline
+// (each in 1..8), and it is visible where its matched pixel at distance
+// t(dmin + d) is inside.
 hipError_t launch_cost_fuse(Ctx& c, const uint8_t* volumes, size_t stride, int n, int W, int H,
-                            int D, int dreal, int dmin, const int32_t* steps, uint8_t* fused);
-// The mixed-baseline instance: pair i's major-axis baseline
-// is ratios[2i] / ratios[2i+1] of the group's unit baseline (each in 1..8), and
-// it is visible where its matched pixel at distance t(dmin + d) is inside.
-hipError_t launch_cost_fuse_mixed(Ctx& c, const uint8_t* volumes, size_t stride, int n, int W,
-                                  int H, int D, int dreal, int dmin, const int32_t* steps,
-                                  const int32_t* ratios, uint8_t* fused);
+                            int D, int dreal, int dmin, const int32_t* steps,
+                            const int32_t* ratios, uint8_t* fused);
 // cost_mixed.hip -- the cost volume of one such pair from two census maps
 // (DESIGN.md §2.2d, §4.20): C(p, d) against the matched pixel at distance
 // t(dmin + d) = (dmin + d) * num / den rounded half up along (sx, sy).  Native
