@@ -18,6 +18,26 @@
  *     sva_synchronize() (or synchronise the stream yourself) before reading.
  *   - Images are 8-bit grayscale, row-major, row pitch in bytes (>= width).
  *     Every other array is dense (pitch = width).
+ *   - An image's base address and its pitch need no alignment (a sub-rectangle
+ *     of a larger image, base = parent + y0 * P + x0 with pitch = P, is a valid
+ *     image, on the host and on the device), and a plane of `height` rows must
+ *     be readable -- an output plane that carries a pitch: writable -- for
+ *     height * pitch bytes from its base: the bytes between the rows may be
+ *     read, never change a result and keep their values.  (Who needs the whole
+ *     extent: the refinement's box kernel, whose loads range over height *
+ *     pitch bytes, and the host forms sva_shift_perspective,
+ *     sva_improve_with_disparity and sva_resize_half, which upload their input
+ *     planes whole; the first two also upload the output plane and copy it
+ *     back whole, so its bytes between the rows are rewritten with their own
+ *     values, while sva_resize_half copies back the pixels only.  Every other
+ *     entry, host or device, touches only the width bytes of each row.)  A
+ *     crop that reaches its parent's last row therefore needs x0 more bytes
+ *     after it for those calls.  Mode R and the refinement load
+ *     aligned 4-byte words, so up to 3 bytes before the base or after that
+ *     extent may be read together with a byte inside it; such a word never
+ *     crosses a page, which asks nothing of the caller.  (tests/
+ *     test_image_views_gpu.py runs every entry at every base and pitch residue
+ *     modulo 4.)
  *   - A context owns one device and one stream and is not re-entrant; calls on
  *     different contexts may run concurrently from different host threads.
  *   - There is no CPU fallback: if no HIP device is usable every compute call

@@ -1953,7 +1953,11 @@ int sva_resize_half(void* ctx, const uint8_t* src, int W, int H, size_t pitch, u
     uint8_t* dd = g.out<uint8_t>(c->out_a, db);
     if (g.st) return g.st;
     SVA_HIP(c, launch_resize_half(*c, ds, W, H, pitch, dd, dst_pitch), "resize launch");
-    g.down(dst, dd, db);
+    // only the pixels go back: the bytes between the caller's rows are not touched
+    int dw, dh;
+    resize_half_size(W, H, &dw, &dh);
+    g.note(hipMemcpy2DAsync(dst, dst_pitch, dd, dst_pitch, (size_t)dw, (size_t)dh,
+                            hipMemcpyDeviceToHost, c->stream), "download");
     return g.sync();
 }
 
