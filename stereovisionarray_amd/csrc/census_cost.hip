@@ -247,7 +247,7 @@ __global__ __launch_bounds__(CC_BLOCK) void census_cost_mma_kernel(
 
 }  // namespace
 
-bool census_cost_supported(int D) { return D == 64 || D == 128 || D == 192 || D == 256; }
+bool census_cost_supported(int D) { return is_native_d(D); }
 
 hipError_t launch_census_cost(Ctx& c, const uint8_t* left, const uint8_t* right, int W, int H,
                               size_t pitch, int D, int dmin, int dir, uint8_t* C, int dreal) {

@@ -233,7 +233,7 @@ void reduce_step(int sx, int sy, int* bx, int* by) {
 }  // namespace
 
 bool census_cost2_supported(int D, int sx, int sy) {
-    if (!(D == 64 || D == 128 || D == 192 || D == 256) || sy == 0) return false;
+    if (!is_native_d(D) || sy == 0) return false;
     int bx, by;
     reduce_step(sx, sy, &bx, &by);
     const int abx = bx < 0 ? -bx : bx;

@@ -314,8 +314,7 @@ __device__ __forceinline__ void sgm_step(const unsigned (&cw)[DPL / 4], unsigned
 // placed by pixel: byte i belongs to the segment's pixel i for directions 0
 // and 2, to pixel 7 - i for directions 1 and 3, so step i of wta_hv's
 // recurrences takes byte i in a ragged segment too (its bytes of pixels
-// outside the image are never read).
-constexpr int kMinimaSeg = 8;
+// outside the image are never read).  (kMinimaSeg = 8: agg_plan.h.)
 
 // The last eight entering minima of a line, newest in the top byte.
 struct MinWindow {

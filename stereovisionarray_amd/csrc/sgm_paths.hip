@@ -191,107 +191,52 @@ __global__ __launch_bounds__(PATH_BLOCK) void sgm_paths_kernel(const uint8_t* __
     }
 }
 
-// (a pair instance exists only for the D classes whose pair route is enabled,
-// a minima instance only for those with tune::kPathMinima*; launch_paths has
-// refused the others)
-template <int DPL, bool EN, bool MN>
-void paths_launch_mn(bool pair, dim3 grid, hipStream_t s, hipEvent_t start, hipEvent_t stop,
-                     const uint8_t* C, uint8_t* L8, uint8_t* CK, uint8_t* CKV, uint8_t* MNP,
-                     const PathGeom& g) {
-    if constexpr (EN) {
-        if (pair) {
-            hipExtLaunchKernelGGL((sgm_paths_kernel<DPL, true, MN>), grid, dim3(PATH_BLOCK), 0, s,
-                                  start, stop, 0, C, L8, CK, CKV, MNP, g);
-            return;
-        }
-    }
-    hipExtLaunchKernelGGL((sgm_paths_kernel<DPL, false, MN>), grid, dim3(PATH_BLOCK), 0, s, start,
-                          stop, 0, C, L8, CK, CKV, MNP, g);
-}
-template <int DPL, bool EN, bool MNEN>
-void paths_launch(bool pair, dim3 grid, hipStream_t s, hipEvent_t start, hipEvent_t stop,
-                  const uint8_t* C, uint8_t* L8, uint8_t* CK, uint8_t* CKV, uint8_t* MNP,
-                  const PathGeom& g) {
-    if constexpr (MNEN) {
-        if (MNP) {
-            paths_launch_mn<DPL, EN, true>(pair, grid, s, start, stop, C, L8, CK, CKV, MNP, g);
-            return;
-        }
-    }
-    paths_launch_mn<DPL, EN, false>(pair, grid, s, start, stop, C, L8, CK, CKV, nullptr, g);
+// The kernel's geometry argument, from the plan.
+PathGeom path_geom(const AggPlan& p) {
+    PathGeom g;
+    g.W = p.W; g.H = p.H; g.D = p.D; g.P1 = p.P1; g.P2 = p.P2;
+    g.blk_h = (p.H + LINES_PER_BLOCK - 1) / LINES_PER_BLOCK;
+    g.blk_w = (p.W + LINES_PER_BLOCK - 1) / LINES_PER_BLOCK;
+    g.vol = p.vol;
+    g.ckpt = p.route == AggRoute::Eight ? 0 : 2;
+    g.ns = p.tg.nsx;
+    g.ckvol = p.tg.hck_bytes / 2;
+    g.nsy = p.tg.nty;
+    g.ckvvol = p.tg.vck_bytes / 2;        // one row-checkpoint plane
+    g.npair = p.frames;
+    g.cstr = p.c_stride;
+    g.lstr = p.vol_stride;
+    g.ckstr = p.hck_stride;
+    g.ckvstr = p.vck_stride;
+    g.pair = p.route == AggRoute::Pair ? 1 : 0;
+    g.dreal = p.dreal;
+    return g;
 }
 
 }  // namespace
 
-bool paths_supported(int D) { return D == 64 || D == 128 || D == 192 || D == 256; }
+bool paths_supported(int D) { return is_native_d(D); }
 
-TileGeom tile_geom(int W, int H, int D) {
-    TileGeom t;
-    t.seg_log2 = D <= 128 ? tune::kWtahvTileLog2 : tune::kWtahvTileLog2Wide;
-    const int seg = 1 << t.seg_log2;
-    t.ntx = (W + 15) >> 4;
-    t.nty = (H + seg - 1) >> t.seg_log2;
-    t.nsx = (W + seg - 1) >> t.seg_log2;
-    t.hck_bytes = 2 * (size_t)H * t.nsx * D;
-    t.vck_bytes = 2 * (size_t)t.nty * W * D;
-    t.hmn_bytes = 2 * (size_t)H * t.nsx * sgm::kMinimaSeg;
-    t.vmn_bytes = 2 * (size_t)t.nty * W * sgm::kMinimaSeg;
-    return t;
-}
-
-bool path_minima_enabled(int D) {
-    return (D == 64 && tune::kPathMinima4) || (D == 128 && tune::kPathMinima8) ||
-           (D == 192 && tune::kPathMinima12) || (D == 256 && tune::kPathMinima16);
-}
-
-bool diag_pair_enabled(int D) {
-    return (D == 64 && tune::kDiagPair4) || (D == 128 && tune::kDiagPair8) ||
-           (D == 192 && tune::kDiagPair12) || (D == 256 && tune::kDiagPair16);
-}
-
-hipError_t launch_paths(Ctx& c, const uint8_t* C, int W, int H, int D, int P1, int P2,
-                        uint8_t* L8, uint8_t* CK, uint8_t* CKV, int npair, bool pair, int dreal,
-                        uint8_t* MN) {
+// (a pair instance exists only for the D classes whose pair route is enabled,
+// a minima instance only for those with tune::kPathMinima*; plan_valid has
+// refused the others)
+hipError_t launch_paths(Ctx& c, const AggPlan& p, const AggBuffers& b) {
     DispatchTimer t(c, "sgm_paths");
-    PathGeom g;
-    g.W = W; g.H = H; g.D = D; g.P1 = P1; g.P2 = P2;
-    g.blk_h = (H + LINES_PER_BLOCK - 1) / LINES_PER_BLOCK;
-    g.blk_w = (W + LINES_PER_BLOCK - 1) / LINES_PER_BLOCK;
-    g.vol = (size_t)W * H * D;
-    if ((CK == nullptr) != (CKV == nullptr)) return hipErrorInvalidValue;
-    g.ckpt = CK ? 2 : 0;
-    const TileGeom tg = tile_geom(W, H, D);
-    g.nsy = tg.nty;
-    g.ckvvol = tg.vck_bytes / 2;        // one row-checkpoint plane
-    g.ns = tg.nsx;
-    g.ckvol = tg.hck_bytes / 2;
-    if (g.vol >= (size_t)1 << 32) return hipErrorInvalidValue;  // 32-bit buffer offsets
-    // a batch: npair frames, each with its buffers packed one after another
-    if (npair < 1 || (npair > 1 && !CK)) return hipErrorInvalidValue;
-    g.npair = npair;
-    g.cstr = g.vol;
-    g.lstr = (size_t)kDiagVolumes * g.vol;
-    g.ckstr = tg.hck_bytes;
-    g.ckvstr = tg.vck_bytes;
-    // the pair route: one frame of the tile pipeline, u8 pair sums (2 * P2 <= 255),
-    // its two diagonal planes of CKV (pair_layout) taken by the caller
-    if (pair && (!CK || npair != 1 || 2 * P2 > 255 || !diag_pair_enabled(D)))
-        return hipErrorInvalidValue;
-    g.pair = pair ? 1 : 0;
-    // path minima: one frame of the tile pipeline, 8-pixel segments
-    if (MN && (!CK || npair != 1 || !path_minima_enabled(D) || (1 << tg.seg_log2) != sgm::kMinimaSeg))
-        return hipErrorInvalidValue;
-    g.dreal = dreal > 0 && dreal < D ? dreal : D;
+    if (!plan_valid(p) || !buffers_fit(p, b)) return hipErrorInvalidValue;
+    const PathGeom g = path_geom(p);
     // (pair: 2 * 2 * blk_w blocks of 8 pair lines + 2 * blk_w vertical blocks)
-    dim3 grid((unsigned)((2 * g.blk_h + 6 * g.blk_w) * npair));
+    const dim3 grid((unsigned)((2 * g.blk_h + 6 * g.blk_w) * p.frames));
     t.used = true;
-    switch (D) {
-        case 64: paths_launch<4, tune::kDiagPair4 != 0, tune::kPathMinima4 != 0>(pair, grid, c.stream, t.start, t.stop, C, L8, CK, CKV, MN, g); break;
-        case 128: paths_launch<8, tune::kDiagPair8 != 0, tune::kPathMinima8 != 0>(pair, grid, c.stream, t.start, t.stop, C, L8, CK, CKV, MN, g); break;
-        case 192: paths_launch<12, tune::kDiagPair12 != 0, tune::kPathMinima12 != 0>(pair, grid, c.stream, t.start, t.stop, C, L8, CK, CKV, MN, g); break;
-        case 256: paths_launch<16, tune::kDiagPair16 != 0, tune::kPathMinima16 != 0>(pair, grid, c.stream, t.start, t.stop, C, L8, CK, CKV, MN, g); break;
-        default: t.used = false; return hipErrorInvalidValue;
-    }
+    for_native_d(p.D, [&](auto k) {
+        using K = decltype(k);
+        with_flag<K::kPair>(p.route == AggRoute::Pair, [&](auto pair) {
+            with_flag<K::kMinima>(p.minima, [&](auto mn) {
+                hipExtLaunchKernelGGL((sgm_paths_kernel<K::DPL, decltype(pair)::value, decltype(mn)::value>),
+                                      grid, dim3(PATH_BLOCK), 0, c.stream, t.start, t.stop, 0, b.C,
+                                      b.volumes, b.CK, b.CKV, b.MN, g);
+            });
+        });
+    });
     return hipGetLastError();
 }
 

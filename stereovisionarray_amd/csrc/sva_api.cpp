@@ -148,7 +148,7 @@ int check_sgm(Ctx* c, const sva_sgm_params* p, int W, int H, bool native = false
     if (p->D <= 0) return fail(c, SVA_ERR_INVALID_ARG, "D must be positive");
     const int Dp = padded_D(p->D);
     if (!Dp) return fail(c, SVA_ERR_UNSUPPORTED, "GPU path built for D in 1..256");
-    if (native && !paths_supported(p->D))
+    if (native && !is_native_d(p->D))
         return fail(c, SVA_ERR_UNSUPPORTED,
                     "stage entry points take D in {64,128,192,256} (whole frames: any D <= 256)");
     if (p->dir < -255 || p->dir > 255 || p->dir_y < -255 || p->dir_y > 255 ||
@@ -174,46 +174,26 @@ int check_sgm(Ctx* c, const sva_sgm_params* p, int W, int H, bool native = false
 // picks d*.  Dp is the native volume width, p->D <= Dp the caller's
 // disparities (§4.7).  (The round-2 route of §4.6 -- six volumes, finished
 // by wta_h -- was slower at every frame size measured and left in ABI v5.)
-// Checkpoint bytes of the pair route: the horizontal and vertical planes plus
-// one row-checkpoint plane per diagonal pair.
-size_t pair_ckpt_bytes(const TileGeom& tg) { return tg.hck_bytes + tg.vck_bytes + tg.vck_bytes; }
-// Checkpoint bytes of a frame on either diagonal route; the minima planes of
-// the horizontal and vertical lines follow them in the
-// context's checkpoint allocation where this D has them.
-size_t frame_ckpt_bytes(const TileGeom& tg, bool pair) {
-    return pair ? pair_ckpt_bytes(tg) : tg.hck_bytes + tg.vck_bytes;
-}
-size_t frame_minima_bytes(const TileGeom& tg, int Dp) {
-    return path_minima_enabled(Dp) ? tg.hmn_bytes + tg.vmn_bytes : 0;
+// The aggregation's shape for the plans of agg_plan.h.
+AggShape agg_shape(int W, int H, int Dp, const sva_sgm_params* p) {
+    return AggShape{W, H, Dp, p->D, p->P1, p->P2, p->dmin};
 }
 
+// The route, the sizes and the layout are frame_plan's (agg_plan.h); the
+// pixel threshold of the pair route is the tuned one or its debug override.
 // cf set: wta_hv's confidence instance instead of the plain one.
 int paths_wta(Ctx* c, const uint8_t* C, int W, int H, const sva_sgm_params* p, int Dp,
               uint16_t* disp, float* sub, const ConfOut* cf = nullptr) {
-    if (!wta_hv_supported(Dp)) return fail(c, SVA_ERR_UNSUPPORTED, "no tile pipeline for this D");
-    const size_t nv = (size_t)W * H * (size_t)Dp;
-    const TileGeom tg = tile_geom(W, H, Dp);
-    // The pair route where this D has it and the pair sums
-    // fit a u8: two pair-sum volumes and two more row-checkpoint planes
-    // (pair_ckpt_bytes) instead of four volumes, for frames large enough that
-    // the pair waves' chain is not the bound (tune::kDiagPairMinPixels).  Else
-    // today's four volumes.
+    if (!is_native_d(Dp)) return fail(c, SVA_ERR_UNSUPPORTED, "no tile pipeline for this D");
     const long long minpx = c->dbg_pair_min_pixels >= 0 ? (long long)c->dbg_pair_min_pixels
                                                         : tune::kDiagPairMinPixels;
-    const bool pair = diag_pair_ok(Dp, p->P2) && (long long)W * H >= minpx;
-    SVA_HIP(c, c->paths.ensure(nv * (pair ? 2 : kDiagVolumes)), "path workspace");
-    const size_t ckb = frame_ckpt_bytes(tg, pair), mnb = frame_minima_bytes(tg, Dp);
-    SVA_HIP(c, c->ckpt.ensure(ckb + mnb), "checkpoint workspace");
-    uint8_t* L4 = (uint8_t*)c->paths.ptr;
-    uint8_t* CK = (uint8_t*)c->ckpt.ptr;
-    uint8_t* CKV = CK + tg.hck_bytes;
-    uint8_t* MN = mnb ? CK + ckb : nullptr;     // (ckb is a multiple of D: 8-byte aligned)
-    SVA_HIP(c, launch_paths(*c, C, W, H, Dp, p->P1, p->P2, L4, CK, CKV, 1, pair, p->D, MN),
-            "paths launch");
-    SVA_HIP(c, launch_wta_hv(*c, C, L4, CK, CKV, W, H, Dp, p->P1, p->P2, p->dmin, disp, sub, p->D, 1,
-                             pair, MN, cf),
-            "wta launch");
-    c->last_diag_route = pair ? 1 : 0;
+    const AggPlan plan = frame_plan(agg_shape(W, H, Dp, p), minpx);
+    SVA_HIP(c, c->paths.ensure(plan.paths_bytes), "path workspace");
+    SVA_HIP(c, c->ckpt.ensure(plan.ckpt_bytes), "checkpoint workspace");
+    const AggBuffers b = carve(plan, C, c->paths.ptr, c->ckpt.ptr);
+    SVA_HIP(c, launch_paths(*c, plan, b), "paths launch");
+    SVA_HIP(c, launch_wta_hv(*c, plan, b, disp, sub, cf), "wta launch");
+    c->last_diag_route = plan.route == AggRoute::Pair ? 1 : 0;
     return SVA_OK;
 }
 
@@ -221,15 +201,15 @@ int paths_wta(Ctx* c, const uint8_t* C, int W, int H, const sva_sgm_params* p, i
 sva_tile_layout tile_layout(int W, int H, int D) {
     sva_tile_layout l;
     std::memset(&l, 0, sizeof(l));
-    const TileGeom tg = tile_geom(W, H, D);
-    l.seg = 1 << tg.seg_log2;
-    l.nsx = tg.nsx;
-    l.nsy = tg.nty;
-    l.cost_bytes = (size_t)W * H * (size_t)D;
+    const AggPlan plan = stage_plan(AggShape{W, H, D});
+    l.seg = 1 << plan.tg.seg_log2;
+    l.nsx = plan.tg.nsx;
+    l.nsy = plan.tg.nty;
+    l.cost_bytes = plan.vol;
     l.diag_volumes = kDiagVolumes;
-    l.diag_bytes = (size_t)kDiagVolumes * l.cost_bytes;
-    l.hckpt_bytes = tg.hck_bytes;
-    l.vckpt_bytes = tg.vck_bytes;
+    l.diag_bytes = plan.paths_bytes;
+    l.hckpt_bytes = plan.tg.hck_bytes;
+    l.vckpt_bytes = plan.tg.vck_bytes;
     return l;
 }
 
@@ -361,14 +341,15 @@ int run_sgm_batch(Ctx* c, const sva_pair_d* jobs, int n, int W, int H, size_t pi
     const sva_sgm_params* p = &jobs[0].params;
     const int Dp = padded_D(p->D);
     const size_t np = (size_t)W * H, nv = np * (size_t)Dp;
-    const TileGeom tg = tile_geom(W, H, Dp);
-    const size_t ckb = frame_ckpt_bytes(tg, false);
     const int sb = tune::kBatchSubFrames > 0 ? std::min(n, tune::kBatchSubFrames) : n;
     const int nsub = (n + sb - 1) / sb;
     SVA_HIP(c, c->cost.ensure(nv * n), "cost workspace");
-    // the aggregation workspaces serve one sub-batch at a time (same stream)
-    SVA_HIP(c, c->paths.ensure(nv * kDiagVolumes * sb), "path workspace");
-    SVA_HIP(c, c->ckpt.ensure(ckb * sb), "checkpoint workspace");
+    // the aggregation workspaces serve one sub-batch at a time (same stream):
+    // full sub-batches of sb frames, then the rest
+    const AggPlan full = batch_plan(agg_shape(W, H, Dp, p), sb);
+    const AggPlan rest = batch_plan(agg_shape(W, H, Dp, p), n - (nsub - 1) * sb);
+    SVA_HIP(c, c->paths.ensure(full.paths_bytes), "path workspace");
+    SVA_HIP(c, c->ckpt.ensure(full.ckpt_bytes), "checkpoint workspace");
     uint8_t* C = (uint8_t*)c->cost.ptr;
     const int ns = std::min(n, tune::kBatchCostStreams);
     if (ns > 1) {
@@ -423,20 +404,16 @@ int run_sgm_batch(Ctx* c, const sva_pair_d* jobs, int n, int W, int H, size_t pi
             }
         }
         if (e != hipSuccess) { st = hip_fail(c, e, "join"); break; }
-        uint8_t* L4 = (uint8_t*)c->paths.ptr;
-        uint8_t* CK = (uint8_t*)c->ckpt.ptr;
-        // horizontal planes of the sub-batch's frames, then their vertical planes
-        uint8_t* CKV = CK + tg.hck_bytes * m;
-        const uint8_t* Cj = C + (size_t)i0 * nv;
-        if ((e = launch_paths(*c, Cj, W, H, Dp, p->P1, p->P2, L4, CK, CKV, m)) != hipSuccess) {
+        const AggPlan& plan = m == sb ? full : rest;
+        const AggBuffers b = carve(plan, C + (size_t)i0 * nv, c->paths.ptr, c->ckpt.ptr);
+        if ((e = launch_paths(*c, plan, b)) != hipSuccess) {
             st = hip_fail(c, e, "paths launch");
             break;
         }
         const ConfOut cfj = conf_at(cf, (size_t)i0 * np);
-        if ((e = launch_wta_hv(*c, Cj, L4, CK, CKV, W, H, Dp, p->P1, p->P2, p->dmin,
-                               maps + (size_t)i0 * np,
-                               p->subpixel && sub ? sub + (size_t)i0 * np : nullptr, p->D, m, false,
-                               nullptr, cf ? &cfj : nullptr)) != hipSuccess) {
+        if ((e = launch_wta_hv(*c, plan, b, maps + (size_t)i0 * np,
+                               p->subpixel && sub ? sub + (size_t)i0 * np : nullptr,
+                               cf ? &cfj : nullptr)) != hipSuccess) {
             st = hip_fail(c, e, "wta launch");
             break;
         }
@@ -697,10 +674,9 @@ namespace {
 // context's current cost / path / checkpoint buffers.  The volumes hold
 // whatever they hold: the kernel's work does not depend on the values.
 int time_stage_set(Ctx* c, int W, int H, int D, int64_t* ns) {
-    const TileGeom tg = tile_geom(W, H, D);
-    const uint8_t* C = (const uint8_t*)c->cost.ptr;
-    uint8_t* L4 = (uint8_t*)c->paths.ptr;
-    uint8_t* CK = (uint8_t*)c->ckpt.ptr;
+    // (the plan of a frame with the default penalties)
+    const AggPlan plan = frame_plan(AggShape{W, H, D, 0, 10, 120}, tune::kDiagPairMinPixels);
+    const AggBuffers buf = carve(plan, (const uint8_t*)c->cost.ptr, c->paths.ptr, c->ckpt.ptr);
     hipEvent_t a = nullptr, b = nullptr;
     SVA_HIP(c, hipEventCreate(&a), "placement event");
     if (hipEventCreate(&b) != hipSuccess) {
@@ -711,11 +687,7 @@ int time_stage_set(Ctx* c, int W, int H, int D, int64_t* ns) {
     float best = 0.f;
     for (int r = 0; r < 4 && e == hipSuccess; r++) {
         e = hipEventRecord(a, c->stream);
-        // (the route a frame with the default penalties takes)
-        const bool pair = diag_pair_ok(D, 120) && (long long)W * H >= tune::kDiagPairMinPixels;
-        if (e == hipSuccess)
-            e = launch_paths(*c, C, W, H, D, 10, 120, L4, CK, CK + tg.hck_bytes, 1, pair, 0,
-                             frame_minima_bytes(tg, D) ? CK + frame_ckpt_bytes(tg, pair) : nullptr);
+        if (e == hipSuccess) e = launch_paths(*c, plan, buf);
         if (e == hipSuccess) e = hipEventRecord(b, c->stream);
         if (e == hipSuccess) e = hipEventSynchronize(b);
         float ms = 0.f;
@@ -807,18 +779,15 @@ int sva_reserve(void* ctx, int W, int H, int D) {
     SVA_HIP(c, c->census_l.ensure(np * 8), "reserve");
     SVA_HIP(c, c->census_r.ensure(np * 8), "reserve");
     SVA_HIP(c, c->cost.ensure(nv), "reserve");
-    // the frame route's path volumes: the 4 diagonal directions (tile pipeline)
-    const TileGeom tg = tile_geom(W, H, D);
-    // (the larger of the two diagonal routes' layouts: four volumes, and the
-    // pair route's two more row-checkpoint planes)
-    const size_t ckb = frame_ckpt_bytes(tg, diag_pair_enabled(D)) + frame_minima_bytes(tg, D);
-    SVA_HIP(c, c->paths.ensure(nv * kDiagVolumes), "reserve");
-    SVA_HIP(c, c->ckpt.ensure(ckb), "reserve");
+    // the frame route's workspaces, for either diagonal route (tile pipeline)
+    const AggReserve r = reserve_plan(W, H, D);
+    SVA_HIP(c, c->paths.ensure(r.paths_bytes), "reserve");
+    SVA_HIP(c, c->ckpt.ensure(r.ckpt_bytes), "reserve");
     // (once per allocation: a repeated reserve of a size the buffers already
     // hold keeps the set the last check chose)
     const int trials = c->placement_trials > 0 ? c->placement_trials : tune::kPlacementTrials;
-    if (trials > 1 && wta_hv_supported(D) && nv < ((size_t)1 << 32) &&
-        nv + nv * kDiagVolumes + ckb >= tune::kPlacementMinBytes && c->paths.ptr != c->placement_paths)
+    if (trials > 1 && is_native_d(D) && nv < ((size_t)1 << 32) &&
+        nv + r.paths_bytes + r.ckpt_bytes >= tune::kPlacementMinBytes && c->paths.ptr != c->placement_paths)
         return place_stage_buffers(c, W, H, D, trials);
     return SVA_OK;
 }
@@ -996,13 +965,14 @@ int sgm_batch_d(void* ctx, const sva_pair_d* jobs, int n, int W, int H, size_t p
             return fail(c, SVA_ERR_INVALID_ARG, "a confidence batch's pairs must share invalid");
         if (q->lr_check) return fail(c, SVA_ERR_UNSUPPORTED, "the batch route has no L/R check");
     }
-    if (!wta_hv_supported(padded_D(p0->D)))
+    if (!is_native_d(padded_D(p0->D)))
         return fail(c, SVA_ERR_UNSUPPORTED, "no tile pipeline for this D");
     // chunks of at most tune::kBatchMaxPairs frames, whose workspaces stay
     // under tune::kBatchMaxBytes
     const int Dp = padded_D(p0->D);
     const size_t np = (size_t)W * H;
-    const size_t per = np * (size_t)Dp * (1 + kDiagVolumes) + frame_ckpt_bytes(tile_geom(W, H, Dp), false);
+    const AggPlan one = batch_plan(agg_shape(W, H, Dp, p0), 1);
+    const size_t per = one.vol + one.paths_bytes + one.ckpt_bytes;
     int chunk = tune::kBatchMaxPairs;
     while (chunk > 1 && per * (size_t)chunk > tune::kBatchMaxBytes) chunk--;
     for (int i0 = 0; i0 < n; i0 += chunk) {
@@ -1047,7 +1017,7 @@ int check_sgm_multi(Ctx* c, const uint8_t* ref, const uint8_t* const* others, co
     if (p->lr_check)
         return fail(c, SVA_ERR_UNSUPPORTED, "the multi-baseline route has no L/R check");
     if (!disp) return fail(c, SVA_ERR_INVALID_ARG, "null disparity output");
-    if (!wta_hv_supported(padded_D(p->D)))
+    if (!is_native_d(padded_D(p->D)))
         return fail(c, SVA_ERR_UNSUPPORTED, "no tile pipeline for this D");
     return SVA_OK;
 }
@@ -1197,7 +1167,7 @@ int sgm_multi_host(void* ctx, const uint8_t* ref, const uint8_t* const* others,
 // sva_cost_mixed_d: a native-D volume with 32-bit offsets.
 int check_stage_volume(Ctx* c, int W, int H, int D, int dreal, int dmin) {
     if (W <= 0 || H <= 0) return fail(c, SVA_ERR_INVALID_ARG, "image size must be positive");
-    if (!paths_supported(D))
+    if (!is_native_d(D))
         return fail(c, SVA_ERR_UNSUPPORTED, "stage entry points take D in {64,128,192,256}");
     if (dreal < 1 || dreal > D) return fail(c, SVA_ERR_INVALID_ARG, "dreal must be 1..D");
     if (dmin < 0 || dmin + D > 65535)
@@ -1386,7 +1356,9 @@ int sva_paths_d(void* ctx, const uint8_t* C, int W, int H, const sva_sgm_params*
     int s;
     if ((s = check_sgm(c, p, W, H, true))) return s;
     if (!C || !L8 || W <= 0 || H <= 0) return fail(c, SVA_ERR_INVALID_ARG, "bad argument");
-    SVA_HIP(c, launch_paths(*c, C, W, H, p->D, p->P1, p->P2, L8), "paths launch");
+    const AggPlan plan = eight_plan(agg_shape(W, H, p->D, p));
+    const AggBuffers b = carve(plan, C, L8, nullptr);
+    SVA_HIP(c, launch_paths(*c, plan, b), "paths launch");
     return SVA_OK;
 }
 
@@ -1397,23 +1369,23 @@ int sva_aggregate_d(void* ctx, const uint8_t* C, int W, int H, const sva_sgm_par
     int s;
     if ((s = check_sgm(c, p, W, H, true))) return s;
     if (!C || !S || W <= 0 || H <= 0) return fail(c, SVA_ERR_INVALID_ARG, "bad argument");
-    const size_t nv = (size_t)W * H * (size_t)p->D;
-    SVA_HIP(c, c->paths.ensure(nv * 8), "path workspace");
-    uint8_t* L8 = (uint8_t*)c->paths.ptr;
-    SVA_HIP(c, launch_paths(*c, C, W, H, p->D, p->P1, p->P2, L8), "paths launch");
-    SVA_HIP(c, launch_sum(*c, L8, W, H, p->D, S), "sum launch");
+    const AggPlan plan = eight_plan(agg_shape(W, H, p->D, p));
+    SVA_HIP(c, c->paths.ensure(plan.paths_bytes), "path workspace");
+    const AggBuffers b = carve(plan, C, c->paths.ptr, nullptr);
+    SVA_HIP(c, launch_paths(*c, plan, b), "paths launch");
+    SVA_HIP(c, launch_sum(*c, b.volumes, W, H, p->D, S), "sum launch");
     return SVA_OK;
 }
 
 int sva_tile_layout_of(int W, int H, int D, sva_tile_layout* out) {
-    if (!out || W <= 0 || H <= 0 || !paths_supported(D)) return SVA_ERR_INVALID_ARG;
+    if (!out || W <= 0 || H <= 0 || !is_native_d(D)) return SVA_ERR_INVALID_ARG;
     *out = tile_layout(W, H, D);
     return SVA_OK;
 }
 
 int sva_tile_check(int W, int H, int D, size_t C_bytes, size_t diag_bytes, size_t hckpt_bytes,
                    size_t vckpt_bytes) {
-    if (W <= 0 || H <= 0 || !paths_supported(D)) return SVA_ERR_INVALID_ARG;
+    if (W <= 0 || H <= 0 || !is_native_d(D)) return SVA_ERR_INVALID_ARG;
     const char one = 0;   // any non-null address: sizes only
     return check_tile_buffers(nullptr, W, H, D, &one, C_bytes, &one, diag_bytes, &one, hckpt_bytes,
                               &one, vckpt_bytes);
@@ -1429,7 +1401,9 @@ int sva_paths_tile_d(void* ctx, const uint8_t* C, size_t C_bytes, int W, int H,
     if ((s = check_tile_buffers(c, W, H, p->D, C, C_bytes, diag, diag_bytes, hckpt, hckpt_bytes,
                                 vckpt, vckpt_bytes)))
         return s;
-    SVA_HIP(c, launch_paths(*c, C, W, H, p->D, p->P1, p->P2, diag, hckpt, vckpt), "paths launch");
+    SVA_HIP(c, launch_paths(*c, stage_plan(agg_shape(W, H, p->D, p)),
+                            AggBuffers{C, diag, hckpt, vckpt, nullptr}),
+            "paths launch");
     return SVA_OK;
 }
 
@@ -1445,8 +1419,11 @@ int sva_wta_hv_d(void* ctx, const uint8_t* C, size_t C_bytes, const uint8_t* dia
                                 vckpt, vckpt_bytes)))
         return s;
     if (!disp) return fail(c, SVA_ERR_INVALID_ARG, "null disparity output");
-    SVA_HIP(c, launch_wta_hv(*c, C, diag, hckpt, vckpt, W, H, p->D, p->P1, p->P2, p->dmin, disp,
-                             p->subpixel ? sub : nullptr),
+    // (the kernel only reads the caller's volumes and checkpoints)
+    SVA_HIP(c, launch_wta_hv(*c, stage_plan(agg_shape(W, H, p->D, p)),
+                             AggBuffers{C, const_cast<uint8_t*>(diag), const_cast<uint8_t*>(hckpt),
+                                        const_cast<uint8_t*>(vckpt), nullptr},
+                             disp, p->subpixel ? sub : nullptr),
             "wta launch");
     return SVA_OK;
 }

@@ -12,6 +12,7 @@
 #include <string>
 #include <vector>
 
+#include "agg_plan.h"
 #include "sva.h"
 #include "sva_native_d.h"
 #include "sva_tuning.h"
@@ -174,68 +175,27 @@ hipError_t launch_census_cost2(Ctx& c, const uint8_t* left, const uint8_t* right
                                int dreal = 0);
 hipError_t launch_cost(Ctx& c, const uint64_t* cl, const uint64_t* cr, int W, int H, int D,
                        int dmin, int dir, uint8_t* C, int dreal = 0);
-// sgm_paths.hip -- all 8 directions in one launch.  CK == CKV == nullptr:
-// L8 = [8][H][W][D] u8.  CK and CKV set (the tile pipeline):
-// L8 = [4][H][W][D] (directions 4..7), CK = [2][H][nsx][D] and CKV =
-// [2][nty][W][D], the vertical checkpoints (tile_geom below).  npair > 1 (tile
-// pipeline only): a batch of frames in one launch, each buffer holding npair
-// such planes back to back.
-// pair (one frame of the tile pipeline, diag_pair_ok): the pair route of
-// DESIGN.md §4.15, L8 = [2][H][W][D] pair sums (4+5, 6+7) and CKV = the two
-// vertical planes plus two wave-private row-checkpoint planes (pair_layout);
-// dreal as for launch_wta_hv.
-// MN (one frame of the tile pipeline, path_minima_enabled): the horizontal and
-// vertical lines also store their entering minima, hmn_bytes + vmn_bytes of
-// tile_geom, for launch_wta_hv(.., MN).
-hipError_t launch_paths(Ctx& c, const uint8_t* C, int W, int H, int D, int P1, int P2,
-                        uint8_t* L8, uint8_t* CK = nullptr, uint8_t* CKV = nullptr,
-                        int npair = 1, bool pair = false, int dreal = 0, uint8_t* MN = nullptr);
-// Path minima: compiled in for this native D (tune::kPathMinima*).
-bool path_minima_enabled(int D);
-// The pair route: compiled in for this native D (tune::kDiagPair*), and usable
-// for a frame with these penalties (the u8 pair sum holds 2 * P2).
-bool diag_pair_enabled(int D);
-inline bool diag_pair_ok(int D, int P2) { return diag_pair_enabled(D) && 2 * P2 <= 255; }
-// Tile pipeline geometry: tiles of 16 columns x seg rows (seg = 2^seg_log2),
-// checkpoints every seg columns (horizontal lines) and every seg rows
-// (vertical lines).
-constexpr int kDiagVolumes = 4;   // [4][H][W][D]: the diagonal directions 4..7
-struct TileGeom {
-    int seg_log2;
-    int ntx, nty;             // tiles per row / per column (nty = vertical segments)
-    int nsx;                  // horizontal segments per row
-    size_t hck_bytes;         // [2][H][nsx][D]
-    size_t vck_bytes;         // [2][nty][W][D]: directions 2, 3
-    size_t hmn_bytes;         // [2][H][nsx][8]: entering minima of directions 0, 1 (§4.17)
-    size_t vmn_bytes;         // [2][nty][W][8]: of directions 2, 3
-};
-TileGeom tile_geom(int W, int H, int D);
-bool paths_supported(int D);
-// wta_hv.hip -- the tile pipeline's final kernel: horizontal + vertical
-// recompute from the checkpoints of launch_paths(.., CK, CKV), sum with the
-// four diagonal volumes L4, WTA.  dreal < D: a padded frame (DESIGN.md
-// §4.7), WTA over d < dreal only.
-bool wta_hv_supported(int D);
+// sgm_paths.hip and wta_hv.hip -- the aggregation, described by an AggPlan
+// (agg_plan.h: route, sizes, plane offsets and the legality rules; layout table
+// in DESIGN.md §4.9a).  launch_paths runs all 8 directions in one launch: eight
+// volumes, or the tile pipeline's diagonal volumes plus checkpoints (and minima
+// planes), from which launch_wta_hv recomputes the other four directions per
+// tile, sums and picks d* into disp / sub (W*H each per frame).  A plan that is
+// not plan_valid, or buffers that do not fit it, are hipErrorInvalidValue.
+hipError_t launch_paths(Ctx& c, const AggPlan& p, const AggBuffers& b);
+bool paths_supported(int D);   // is_native_d
 // The WTA's confidence outputs, a kernel argument of the
-// confidence instances: W*H u16 planes (each nullable; a batch launch: npair
-// such planes back to back, like disp), the uniqueness percentage 0..100
-// (0 = no filter) and the disparity a rejected pixel gets, both one value per
-// launch.
+// confidence instances: W*H u16 planes (each nullable; a batch launch: one per
+// frame back to back, like disp), the uniqueness percentage 0..100 (0 = no
+// filter) and the disparity a rejected pixel gets, both one value per launch.
 struct ConfOut {
     uint16_t* cost_min = nullptr;
     uint16_t* cost_second = nullptr;
     int uniqueness = 0;
     unsigned invalid = 0xffffu;
 };
-// pair: L4 holds the pair route's two pair-sum volumes (one frame).
-// MN: the minima planes of launch_paths(.., MN) for the same frame; the
-// recurrences read each step's m there (one frame, path_minima_enabled).
-// cf set: the confidence instance of the same kernel (one frame or a batch,
-// DESIGN.md §4.10).
-hipError_t launch_wta_hv(Ctx& c, const uint8_t* C, const uint8_t* L4, const uint8_t* CK,
-                         const uint8_t* CKV, int W, int H, int D, int P1, int P2, int dmin,
-                         uint16_t* disp, float* sub, int dreal = 0, int npair = 1,
-                         bool pair = false, const uint8_t* MN = nullptr,
+// cf set: the confidence instance of the same kernel.
+hipError_t launch_wta_hv(Ctx& c, const AggPlan& p, const AggBuffers& b, uint16_t* disp, float* sub,
                          const ConfOut* cf = nullptr);
 // wta.hip
 hipError_t launch_sum(Ctx& c, const uint8_t* L8, int W, int H, int D, uint16_t* S);

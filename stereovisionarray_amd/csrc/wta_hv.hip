@@ -71,101 +71,56 @@ template <int DPL, bool PAIR> constexpr int pf_vol() {
 #include "wta_hv_tile.inc"
 #undef SVA_WTAHV_CONF
 
-// (PAIR instances exist only for the D classes whose pair route is enabled,
-// minima instances only for those with tune::kPathMinima*; launch_wta_hv has
-// refused pair = true or a minima plane for the others)
-template <int DPL, int TYL, bool PAIR, bool MN>
-void wtahv_launch_mn(bool pad, dim3 grid, hipStream_t s, hipEvent_t start, hipEvent_t stop,
-                     const uint8_t* C, const uint8_t* L4, const uint8_t* CK, const uint8_t* CKV,
-                     const uint8_t* MNP, const WtaHvGeom& g, uint16_t* disp, float* sub,
-                     const ConfOut* cf) {
-    if (cf) {   // the confidence instance (the entry point asked for it)
-        if (pad)
-            hipExtLaunchKernelGGL((wta_hv_conf_kernel<DPL, TYL, true, PAIR, MN>), grid, dim3(TB), 0,
-                                  s, start, stop, 0, C, L4, CK, CKV, MNP, g, disp, sub, *cf);
-        else
-            hipExtLaunchKernelGGL((wta_hv_conf_kernel<DPL, TYL, false, PAIR, MN>), grid, dim3(TB), 0,
-                                  s, start, stop, 0, C, L4, CK, CKV, MNP, g, disp, sub, *cf);
-        return;
-    }
-    if (pad)
-        hipExtLaunchKernelGGL((wta_hv_kernel<DPL, TYL, true, PAIR, MN>), grid, dim3(TB), 0, s, start,
-                              stop, 0, C, L4, CK, CKV, MNP, g, disp, sub);
-    else
-        hipExtLaunchKernelGGL((wta_hv_kernel<DPL, TYL, false, PAIR, MN>), grid, dim3(TB), 0, s, start,
-                              stop, 0, C, L4, CK, CKV, MNP, g, disp, sub);
-}
-template <int DPL, int TYL, bool PAIR, bool MNEN>
-void wtahv_launch(bool pad, dim3 grid, hipStream_t s, hipEvent_t start, hipEvent_t stop,
-                  const uint8_t* C, const uint8_t* L4, const uint8_t* CK, const uint8_t* CKV,
-                  const uint8_t* MNP, const WtaHvGeom& g, uint16_t* disp, float* sub,
-                  const ConfOut* cf) {
-    if constexpr (MNEN) {
-        if (MNP) {
-            wtahv_launch_mn<DPL, TYL, PAIR, true>(pad, grid, s, start, stop, C, L4, CK, CKV, MNP, g,
-                                                  disp, sub, cf);
-            return;
-        }
-    }
-    wtahv_launch_mn<DPL, TYL, PAIR, false>(pad, grid, s, start, stop, C, L4, CK, CKV, nullptr, g,
-                                           disp, sub, cf);
+// The kernel's geometry argument, from the plan.
+WtaHvGeom wta_hv_geom(const AggPlan& p) {
+    WtaHvGeom g;
+    g.W = p.W; g.H = p.H; g.D = p.D; g.P1 = p.P1; g.P2 = p.P2; g.dmin = p.dmin;
+    g.ntx = p.tg.ntx;
+    g.nty = p.tg.nty;
+    g.nsx = p.tg.nsx;
+    g.dreal = p.dreal;
+    g.vol = (unsigned)p.vol;
+    g.hck = (unsigned)(p.tg.hck_bytes / 2);
+    g.vck = (unsigned)(p.tg.vck_bytes / 2);
+    g.tiles = g.ntx * g.nty;
+    return g;
 }
 
 }  // namespace
 
-bool wta_hv_supported(int D) { return D == 64 || D == 128 || D == 192 || D == 256; }
-
-hipError_t launch_wta_hv(Ctx& c, const uint8_t* C, const uint8_t* L4, const uint8_t* CK,
-                         const uint8_t* CKV, int W, int H, int D, int P1, int P2, int dmin,
-                         uint16_t* disp, float* sub, int dreal, int npair, bool pair,
-                         const uint8_t* MN, const ConfOut* cf) {
+// (PAIR instances exist only for the D classes whose pair route is enabled,
+// minima instances only for those with tune::kPathMinima*; plan_valid has
+// refused the others.  A batch: cf's planes hold a plane per frame, like disp
+// and sub.)
+hipError_t launch_wta_hv(Ctx& c, const AggPlan& p, const AggBuffers& b, uint16_t* disp, float* sub,
+                         const ConfOut* cf) {
     DispatchTimer t(c, "wta_hv");
-    if (!wta_hv_supported(D)) return hipErrorInvalidValue;
-    const TileGeom tg = tile_geom(W, H, D);
-    WtaHvGeom g;
-    g.W = W; g.H = H; g.D = D; g.P1 = P1; g.P2 = P2; g.dmin = dmin;
-    g.dreal = dreal > 0 && dreal < D ? dreal : D;
-    g.ntx = tg.ntx;
-    g.nty = tg.nty;
-    g.nsx = tg.nsx;
-    const size_t vol = (size_t)W * H * D;
-    if (vol >= (size_t)1 << 32) return hipErrorInvalidValue;
-    g.vol = (unsigned)vol;
-    g.hck = (unsigned)(tg.hck_bytes / 2);
-    g.vck = (unsigned)(tg.vck_bytes / 2);
-    const bool pad = g.dreal < D;
-    if (npair < 1) return hipErrorInvalidValue;
-    // (a batch, npair > 1: cf's planes hold npair frames, like disp and sub)
-    if (cf && (cf->uniqueness < 0 || cf->uniqueness > 100)) return hipErrorInvalidValue;
-    g.tiles = g.ntx * g.nty;
-    const dim3 grid((unsigned)(g.tiles * npair));
-#define SVA_WTAHV(DPL_, TYL_, MN_)                                                            \
-    wtahv_launch<DPL_, TYL_, false, (MN_) != 0>(pad, grid, c.stream, t.start, t.stop, C, L4,  \
-                                                CK, CKV, MN, g, disp, sub, cf);               \
-    t.used = true
-#define SVA_WTAHV_P(DPL_, TYL_, EN_, MN_)                                                     \
-    if (pair) {                                                                               \
-        wtahv_launch<DPL_, TYL_, (EN_) != 0, (MN_) != 0>(pad, grid, c.stream, t.start,        \
-                                                         t.stop, C, L4, CK, CKV, MN, g, disp, \
-                                                         sub, cf);                            \
-        t.used = true;                                                                        \
-    } else {                                                                                  \
-        SVA_WTAHV(DPL_, TYL_, MN_);                                                           \
-    }
-    constexpr int TYL = tune::kWtahvTileLog2, TYLW = tune::kWtahvTileLog2Wide;
-    if (tg.seg_log2 != (D <= 128 ? TYL : TYLW)) return hipErrorInvalidValue;
-    if (pair && (npair != 1 || !diag_pair_ok(D, P2))) return hipErrorInvalidValue;
-    if (MN && (npair != 1 || !path_minima_enabled(D) || (1 << tg.seg_log2) != sgm::kMinimaSeg))
+    if (!plan_valid(p) || p.route == AggRoute::Eight || !buffers_fit(p, b) ||
+        (cf && (cf->uniqueness < 0 || cf->uniqueness > 100)))
         return hipErrorInvalidValue;
-    switch (D) {
-        case 64: SVA_WTAHV_P(4, TYL, tune::kDiagPair4, tune::kPathMinima4); break;
-        case 128: SVA_WTAHV_P(8, TYL, tune::kDiagPair8, tune::kPathMinima8); break;
-        case 192: SVA_WTAHV_P(12, TYLW, tune::kDiagPair12, tune::kPathMinima12); break;
-        case 256: SVA_WTAHV_P(16, TYLW, tune::kDiagPair16, tune::kPathMinima16); break;
-        default: return hipErrorInvalidValue;
-    }
-#undef SVA_WTAHV_P
-#undef SVA_WTAHV
+    const WtaHvGeom g = wta_hv_geom(p);
+    const dim3 grid((unsigned)(g.tiles * p.frames));
+    const uint8_t *L4 = b.volumes, *CK = b.CK, *CKV = b.CKV, *MNP = b.MN;
+    t.used = true;
+    for_native_d(p.D, [&](auto k) {
+        using K = decltype(k);
+        with_flag<true>(g.dreal < p.D, [&](auto pad) {
+            with_flag<K::kPair>(p.route == AggRoute::Pair, [&](auto pair) {
+                with_flag<K::kMinima>(p.minima, [&](auto mn) {
+                    constexpr bool PAD = decltype(pad)::value, PAIR = decltype(pair)::value,
+                                   MN = decltype(mn)::value;
+                    if (cf)   // the confidence instance (the entry point asked for it)
+                        hipExtLaunchKernelGGL((wta_hv_conf_kernel<K::DPL, K::kTileLog2, PAD, PAIR, MN>),
+                                              grid, dim3(TB), 0, c.stream, t.start, t.stop, 0, b.C,
+                                              L4, CK, CKV, MNP, g, disp, sub, *cf);
+                    else
+                        hipExtLaunchKernelGGL((wta_hv_kernel<K::DPL, K::kTileLog2, PAD, PAIR, MN>),
+                                              grid, dim3(TB), 0, c.stream, t.start, t.stop, 0, b.C,
+                                              L4, CK, CKV, MNP, g, disp, sub);
+                });
+            });
+        });
+    });
     return hipGetLastError();
 }
 
