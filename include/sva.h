@@ -163,7 +163,7 @@ int sva_kernel_time(void* ctx, const char* name, double* total_ms, int64_t* coun
  * SVA_PLANE_SPLIT environment variable, so the environment never changes
  * how production work is dispatched).  Every key defaults to 0 = off.
  *   SVA_DEBUG_PLANE_SPLIT    set: split every Mode R tile into 1..16 workgroup
- *                            shares (0 = the automatic count, refpath.hip
+ *                            shares (0 = the automatic count, ref_plan.h
  *                            plane_shares), so the parity tests cover every
  *                            share count at every size.
  *   SVA_DEBUG_FAIL_COST_AT   set: the next sva_disparity_sgm_batch_d or

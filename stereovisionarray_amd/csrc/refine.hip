@@ -568,12 +568,6 @@ hipError_t launch_shift_perspective(Ctx& c, const sva_camera& in, const sva_came
     return hipGetLastError();
 }
 
-#define SVA_REFINE_CASE(ND)                                                                    \
-    case ND:                                                                                   \
-        hipLaunchKernelGGL(refine_kernel<ND>, grid, dim3(64, 4), 0, c.stream, disp, center,     \
-                           shifted, mask, W, H, pitch, k, ddx, ddy, out, fault);               \
-        break;
-
 // Candidate tables per group and the workspace they need (include/sva.h states
 // the same formula).
 struct SatPlan {
@@ -674,13 +668,12 @@ hipError_t launch_refine(Ctx& c, const uint8_t* disp, const uint8_t* center,
     // k = 0, and k <= 16 on planes too large for the box kernel's 32-bit offsets
     c.last_refine_route = 1;
     const dim3 grid((W + 63) / 64, (H + 3) / 4);
-    switch ((k + 1) / 2) {  // ND = ceil(2k / 4)
-        SVA_REFINE_CASE(0) SVA_REFINE_CASE(1) SVA_REFINE_CASE(2) SVA_REFINE_CASE(3)
-        SVA_REFINE_CASE(4) SVA_REFINE_CASE(5) SVA_REFINE_CASE(6) SVA_REFINE_CASE(7)
-        SVA_REFINE_CASE(8)
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    // ND = ceil(2k / 4) = 0..8
+    const bool launched = for_int_in<0, 8>((k + 1) / 2, [&](auto ND) {
+        hipLaunchKernelGGL(refine_kernel<decltype(ND)::value>, grid, dim3(64, 4), 0, c.stream, disp,
+                           center, shifted, mask, W, H, pitch, k, ddx, ddy, out, fault);
+    });
+    return launched ? hipGetLastError() : hipErrorInvalidValue;
 }
 
 hipError_t launch_shift_perspective2(Ctx& c, const sva_camera& in, const sva_camera& out,

@@ -15,11 +15,13 @@
 //                         or more) keep 64-bit (SAD, i) first-minimum keys.
 //   ref_pixel_kernel      k > 32 (the reference bounds k only by the image,
 //                         CameraStereoVision.cpp:49-51): one wave per pixel.
+// Line arithmetic: ref_line.h.  What launch_ref_match decides: ref_plan.h.
 #pragma clang fp contract(off)
 
-#include <cstdlib>
 #include <type_traits>
 
+#include "ref_line.h"
+#include "ref_plan.h"
 #include "sva_device.h"
 #include "sva_internal.h"
 #include "sva_tuning.h"
@@ -67,57 +69,6 @@ __global__ void ref_endpoints_kernel(int W, int H, sva_camera cref_, sva_camera 
     ok = ok && !(b0 < k || b1 < k || b0 > W - k || b1 > H - k);  // :69
     ends[p] = make_int4(a0, a1, b0, b1);
     valid[p] = ok ? 1 : 0;
-}
-
-// Closed form of functions.cpp:253-321.  The line is stored as its start
-// point, the major-axis direction and the Bresenham slope numerator/denominator
-// so candidate i is O(1):  plotLineLow emits (x0+i, y0 + yi*floor((2|dy|i + dx - 1) / (2dx))),
-// plotLineHigh the transpose.  (Proof: the error term D_i = 2|dy|(i+1) - dx -
-// 2dx*n_i stays in (-2dx, 2|dy|], which gives n_i = ceil((2|dy|i - dx)/(2dx)).)
-struct Line {
-    int x0, y0;   // first emitted point
-    int high;     // 1: plotLineHigh (y major)
-    int step;     // +-1 minor-axis step (yi / xi)
-    int a, b;     // 2*|minor delta|, 2*major delta
-    int major;    // major delta (dx for low, dy for high)
-    int n;        // number of points
-};
-
-__device__ __forceinline__ Line make_line(int p1x, int p1y, int p2x, int p2y) {
-    // bresenham(point2 = pixel1, point1 = pixel2), functions.cpp:299-321
-    const int ax = p1x, ay = p1y, bx = p2x, by = p2y;
-    int x0, y0, x1, y1;
-    Line L;
-    if (abs(ay - by) < abs(ax - bx)) {
-        if (bx > ax) { x0 = ax; y0 = ay; x1 = bx; y1 = by; }
-        else { x0 = bx; y0 = by; x1 = ax; y1 = ay; }
-        int dx = x1 - x0, dy = y1 - y0;
-        L.high = 0;
-        L.step = dy < 0 ? -1 : 1;
-        L.a = 2 * (dy < 0 ? -dy : dy);
-        L.b = 2 * dx;
-        L.major = dx;
-        L.n = dx + 1;
-    } else {
-        if (by > ay) { x0 = ax; y0 = ay; x1 = bx; y1 = by; }
-        else { x0 = bx; y0 = by; x1 = ax; y1 = ay; }
-        int dx = x1 - x0, dy = y1 - y0;
-        L.high = 1;
-        L.step = dx < 0 ? -1 : 1;
-        L.a = 2 * (dx < 0 ? -dx : dx);
-        L.b = 2 * dy;
-        L.major = dy;
-        L.n = dy + 1;   // dy >= 0 here; dy == 0 only for a single point
-    }
-    L.x0 = x0;
-    L.y0 = y0;
-    return L;
-}
-
-__device__ __forceinline__ void line_point(const Line& L, int i, int& cx, int& cy) {
-    const int minor = L.b > 0 ? (L.a * i + L.major - 1) / L.b : 0;
-    if (L.high) { cx = L.x0 + L.step * minor; cy = L.y0 + i; }
-    else { cx = L.x0 + i; cy = L.y0 + L.step * minor; }
 }
 
 __device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long v) {
@@ -230,51 +181,33 @@ __device__ __forceinline__ void match_pixel_wave(const uint8_t* __restrict__ ref
 //      whatever order the planes are visited in.
 // A tile whose offset geometry exceeds the kernel's buffers falls back to
 // match_pixel_wave.
-// largest k of the plane kernel: the ABI maximum.  Region 63 + 2k <= 127
-// columns (two per lane) and SAD <= (2k)^2 * 255 < 2^20 for the u32 key.
-constexpr int PT_MAXK = 32;
 
-// Inclusive wave64 scan in 6 DPP adds (no LDS): Hillis-Steele within each
-// 16-lane row (row_shr 1, 2, 4, 8; lanes with no source read 0), then
+// Inclusive wave64 scans in 6 DPP adds each (no LDS): Hillis-Steele within
+// each 16-lane row (row_shr 1, 2, 4, 8; lanes with no source read 0), then
 // row_bcast:15 adds lane 15 into rows 1 and 3 and row_bcast:31 adds lane 31
 // into rows 2 and 3.  (A ds_bpermute-based __shfl_up scan put 6 LDS
-// round-trips on the dependency chain of every row.)
-__device__ __forceinline__ unsigned scan64_dpp(unsigned v) {
-    v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, false);   // row_shr:1
-    v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, false);   // row_shr:2
-    v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, false);   // row_shr:4
-    v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, false);   // row_shr:8
-    v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false);   // row_bcast:15
-    v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false);   // row_bcast:31
-    return v;
-}
-
-// The same scan on N pairs of values, stage by stage: each DPP add's source
-// was written 2N instructions earlier, so no s_nop separates dependent adds.
+// round-trips on the dependency chain of every row.)  N pairs of values are
+// scanned stage by stage: each DPP add's source was written 2N instructions
+// earlier, so no s_nop separates dependent adds.
 template <int N>
 __device__ __forceinline__ void scan64_dpp_n(unsigned (&a)[N], unsigned (&b)[N]) {
-    auto stage = [&](auto ctl, int rmask) {
-        (void)rmask;
+    // DPP control and row mask are immediates: compile-time arguments
+    auto stage = [&](auto ctl, auto rmask) {
 #pragma unroll
         for (int j = 0; j < N; j++) {
             a[j] += (unsigned)__builtin_amdgcn_update_dpp(0, (int)a[j], decltype(ctl)::value,
-                                                          decltype(ctl)::value >= 0x142
-                                                              ? (decltype(ctl)::value == 0x142 ? 0xa : 0xc)
-                                                              : 0xf,
-                                                          0xf, false);
+                                                          decltype(rmask)::value, 0xf, false);
             b[j] += (unsigned)__builtin_amdgcn_update_dpp(0, (int)b[j], decltype(ctl)::value,
-                                                          decltype(ctl)::value >= 0x142
-                                                              ? (decltype(ctl)::value == 0x142 ? 0xa : 0xc)
-                                                              : 0xf,
-                                                          0xf, false);
+                                                          decltype(rmask)::value, 0xf, false);
         }
     };
-    stage(std::integral_constant<int, 0x111>{}, 0xf);   // row_shr:1
-    stage(std::integral_constant<int, 0x112>{}, 0xf);   // row_shr:2
-    stage(std::integral_constant<int, 0x114>{}, 0xf);   // row_shr:4
-    stage(std::integral_constant<int, 0x118>{}, 0xf);   // row_shr:8
-    stage(std::integral_constant<int, 0x142>{}, 0xa);   // row_bcast:15 into rows 1, 3
-    stage(std::integral_constant<int, 0x143>{}, 0xc);   // row_bcast:31 into rows 2, 3
+    using std::integral_constant;
+    stage(integral_constant<int, 0x111>{}, integral_constant<int, 0xf>{});   // row_shr:1
+    stage(integral_constant<int, 0x112>{}, integral_constant<int, 0xf>{});   // row_shr:2
+    stage(integral_constant<int, 0x114>{}, integral_constant<int, 0xf>{});   // row_shr:4
+    stage(integral_constant<int, 0x118>{}, integral_constant<int, 0xf>{});   // row_shr:8
+    stage(integral_constant<int, 0x142>{}, integral_constant<int, 0xa>{});   // row_bcast:15 into rows 1, 3
+    stage(integral_constant<int, 0x143>{}, integral_constant<int, 0xc>{});   // row_bcast:31 into rows 2, 3
 }
 
 // ---- offset-plane algorithm (v3) ---------------------------------------------
@@ -303,60 +236,9 @@ __device__ __forceinline__ void scan64_dpp_n(unsigned (&a)[N], unsigned (&b)[N])
 //     first-minimum key is the u32 (SAD << 12 | i): SAD < 2^20 for k <= 32,
 //     i < 4096 when W, H < 4096.  Larger frames take the WIDE instance, whose
 //     u64 key (SAD << 32 | i) holds any i (VERDICT r05 missing #3).
-constexpr int P3_ROWS = 32;                          // 4 waves x 8 rows
 constexpr int P3_OU_BYTES = tune::kPlaneOuKB * 1024;  // staged O chunk
 constexpr int P3_WORDS = tune::kPlaneWords;            // offset bitmap per pass: 32K bits
 constexpr int P3_MAX_OUT = 1024;                     // outer offsets per pass
-
-// Interval [lo, lo + len) of inner offsets d_in on a pixel's line at outer
-// offset d_out; the candidate index there is i = d_in + ib0.
-//   po = o_major | o_minor << 16: the pixel minus its line start along the
-//        line's major / minor axis (signed 16-bit halves);
-//   pa = a | b << 16, pn = n | major << 16 (Line fields; n = 0: no pixel);
-//   mi: the line's major axis is the inner axis; neg: minor step is -1.
-// Candidate i of a line has minor offset floor((a*i + major - 1) / b)
-// (make_line's closed form of functions.cpp:253-321).
-__device__ __forceinline__ void line_interval(int po, int pa, int pn, bool mi, bool neg,
-                                              int d_out, int& lo, int& len, int& ib0) {
-    const int o_major = (int)(short)(po & 0xffff), o_minor = po >> 16;
-    const int a = pa & 0xffff, b = (int)((unsigned)pa >> 16);
-    const int n = pn & 0xffff, mj = (int)((unsigned)pn >> 16) - 1;
-    if (mi) {
-        // i = o_major + d_in, and floor((a*i + mj) / b) must equal the
-        // candidate's minor offset tt = step * (o_minor + d_out)
-        const int u = o_minor + d_out;
-        const int tt = neg ? -u : u;
-        int ilo = 0, ihi = 0;
-        if (tt >= 0) {
-            if (a == 0) {
-                ihi = tt == 0 ? n : 0;
-            } else {
-                // i in [ceil((tt*b - mj)/a), ceil((tt*b + b - mj)/a)); the
-                // lower bound at tt = 0 is <= 0, i.e. 0 after clamping
-                // tune::kPlaneNoHoistDiv: an opaque copy keeps the compiler
-                // from hoisting each pixel's reciprocal of a out of the outer
-                // offset loop (no spill at k = 20, but the division is then
-                // redone per outer offset: +9 % on diagonal pairs)
-                unsigned A = (unsigned)a;
-                if constexpr (tune::kPlaneNoHoistDiv != 0) asm volatile("" : "+v"(A));
-                ilo = tt == 0 ? 0 : (int)(((unsigned)(tt * b - mj) + A - 1u) / A);
-                ihi = (int)(((unsigned)(tt * b + b - mj) + A - 1u) / A);
-            }
-        }
-        ihi = ihi > n ? n : ihi;
-        len = ihi > ilo ? ihi - ilo : 0;
-        lo = ilo - o_major;
-        ib0 = o_major;
-    } else {
-        // i = o_major + d_out is fixed; one inner offset is on the line
-        const int i = o_major + d_out;
-        const bool in = (unsigned)i < (unsigned)n;
-        const int t = (b > 0 && in) ? (int)((unsigned)(a * i + mj) / (unsigned)b) : 0;
-        lo = (neg ? -t : t) - o_minor;
-        len = in ? 1 : 0;
-        ib0 = i - lo;
-    }
-}
 
 template <int K, bool WIDE>
 __global__ __launch_bounds__(256, tune::kPlaneMinBlocks) void ref_plane3_kernel(
@@ -387,19 +269,19 @@ __global__ __launch_bounds__(256, tune::kPlaneMinBlocks) void ref_plane3_kernel(
     constexpr int RS4 = RS / 4;
     static_assert(24 + 4 * ND2 <= RS, "R column stride too small");
     static_assert(ND2 >= ND + 2, "entering rows");
-    static_assert(K >= 1 && K <= PT_MAXK, "k outside the ABI range");
+    static_assert(K >= 1 && K <= kRefPlaneMaxK, "k outside the ABI range");
     static_assert(4 * K * K * 255 < (1 << 20), "SAD must fit the 20-bit key field");
     __shared__ __attribute__((aligned(16))) uint8_t RT[RW * RS];
     __shared__ unsigned bits[P3_WORDS];
     __shared__ __attribute__((aligned(16))) uint8_t OUT[P3_OU_BYTES];
     __shared__ short omn[P3_MAX_OUT], omx[P3_MAX_OUT];
     __shared__ int box[6];   // dx_lo, dx_hi, dy_lo, dy_hi, #High pixels, #pixels
-    __shared__ unsigned short uniq[P3_ROWS * 64];   // pixels with a distinct relative line
+    __shared__ unsigned short uniq[kRefTileRows * 64];   // pixels with a distinct relative line
     __shared__ int nuniq;
-    // tune::kPlanePoLds: each thread's eight line offsets (po below) in LDS,
-    // [row][thread], read back once per outer offset instead of held in
-    // registers -- where that still leaves kPlaneMinBlocks workgroups per CU
-    // (the arrays above plus 256 B of alignment slack)
+    // Each thread's eight line offsets (po below) live in LDS, [row][thread],
+    // read back once per outer offset instead of held in registers -- where
+    // that still leaves kPlaneMinBlocks workgroups per CU (the arrays above
+    // plus 256 B of alignment slack)
     constexpr size_t LDS_BASE = sizeof(RT) + sizeof(bits) + sizeof(OUT) + sizeof(omn) + sizeof(omx) +
                                 sizeof(box) + sizeof(uniq) + sizeof(nuniq);
     // LDS per CU: 160 KB on gfx950, the only target this file is built for
@@ -407,8 +289,8 @@ __global__ __launch_bounds__(256, tune::kPlaneMinBlocks) void ref_plane3_kernel(
 #error "refpath.hip sizes its LDS for gfx950 (160 KB per CU)"
 #endif
     constexpr size_t LDS_PER_CU = 160 * 1024;
-    constexpr bool POLDS = tune::kPlanePoLds != 0 &&
-                           LDS_BASE + 8 * 256 * sizeof(int) + 256 <= LDS_PER_CU / tune::kPlaneMinBlocks;
+    constexpr bool POLDS =
+        LDS_BASE + 8 * 256 * sizeof(int) + 256 <= LDS_PER_CU / tune::kPlaneMinBlocks;
     __shared__ int po_lds[POLDS ? 8 * 256 : 1];
     const int t = threadIdx.x, lane = t & 63;
     const int wv = __builtin_amdgcn_readfirstlane(t >> 6);
@@ -416,7 +298,7 @@ __global__ __launch_bounds__(256, tune::kPlaneMinBlocks) void ref_plane3_kernel(
     // split band -- cost 4-5 VGPRs and 20 B of scratch at k = 20)
     const int share = (int)blockIdx.x, nshare = (int)gridDim.x;
     if (nshare == 1) keys = nullptr;     // a whole tile writes its pixels directly
-    const int tx0 = K + (int)blockIdx.y * 64, ty0 = K + (int)blockIdx.z * P3_ROWS;
+    const int tx0 = K + (int)blockIdx.y * 64, ty0 = K + (int)blockIdx.z * kRefTileRows;
     const int rx0 = tx0 - K, ry0 = ty0 - K;   // region origin (image coords)
     const int r0 = 8 * wv;
     if (t < 6) box[t] = t >= 4 ? 0 : ((t & 1) ? -0x7fffffff : 0x7fffffff);
@@ -465,8 +347,8 @@ __global__ __launch_bounds__(256, tune::kPlaneMinBlocks) void ref_plane3_kernel(
             neg[j] = L.step < 0;
             ox[j] = x - L.x0;
             oy[j] = y - L.y0;
-            pa[j] = L.a | (L.b << 16);
-            pn[j] = (ok ? L.n : 0) | (L.major << 16);
+            pa[j] = line_pa(L);
+            pn[j] = line_pn(L, ok);
             if (ok) {
                 bx0 = min(bx0, min(E[j].x, E[j].z) - x);
                 bx1 = max(bx1, max(E[j].x, E[j].z) - x);
@@ -513,7 +395,7 @@ __global__ __launch_bounds__(256, tune::kPlaneMinBlocks) void ref_plane3_kernel(
         // one outer offset's bitmap row or O column does not fit: per-pixel
         // waves for this tile
         if (share != 0) return;           // one share does the whole tile
-        for (int pi = wv; pi < 64 * P3_ROWS; pi += 4) {
+        for (int pi = wv; pi < 64 * kRefTileRows; pi += 4) {
             const int x = tx0 + (pi & 63), y = ty0 + (pi >> 6);
             if (x >= W - K || y >= H - K) continue;
             const size_t p = (size_t)y * W + x;
@@ -612,35 +494,36 @@ __global__ __launch_bounds__(256, tune::kPlaneMinBlocks) void ref_plane3_kernel(
         }
     };
 
+    // per row: line_interval's results at the current outer offset, and lb =
+    // len | (lo + ib0) << 16 (both < 65536) in one register for the plane loop.
+    // (These arrays, their zeroes and i0 / i1 below stay as written: tidier
+    // forms changed every instance, profiles/refpath_fold/isa_same.txt §4.)
     Key best[8];
     int lo[8], len[8], ib0[8];
-    unsigned lb[8];            // kPlaneStageMajor: len and lo + ib0 in one register
+    unsigned lb[8];
 #pragma unroll
     for (int j = 0; j < 8; j++) {
         best[j] = KNONE;
         lo[j] = len[j] = ib0[j] = 0;
     }
-    // line offsets along each line's own axes (see line_interval)
+    // line offsets along each line's own axes (line_po)
     int po[8];
 #pragma unroll
     for (int j = 0; j < 8; j++) {
-        const int omaj = high[j] ? oy[j] : ox[j], omin = high[j] ? ox[j] : oy[j];
-        po[j] = (omaj & 0xffff) | (omin << 16);
+        po[j] = line_po(high[j] ? oy[j] : ox[j], high[j] ? ox[j] : oy[j]);
         if constexpr (POLDS) po_lds[j * 256 + t] = po[j];
     }
     const int in_lo = cm ? dylo : dxlo, out_lo = cm ? dxlo : dylo;
     const int src = ((lane + W2 - 1) & 63) << 2;
     const int bstride = wpo * 32;
-    // this workgroup's share of the INNER offsets (all of them unsplit): the
-    // runs along the inner axis are the long ones, so every share gets a
-    // piece of every outer offset's run -- an outer-offset split left the
-    // thin bands of Low / High pairs with one or two uneven outer offsets
-    // per share
-    // (tune::kPlaneSplitInner: 1 inner, 0 outer, 2 per tile -- inner for the
-    // thin offset bands of Low / High pairs, outer for the diagonal bands,
-    // whose inner runs are short and shift with the outer offset)
-    const bool SPLIT_IN = tune::kPlaneSplitInner == 2 ? 4 * min(bw, bh) < max(bw, bh)
-                                                       : tune::kPlaneSplitInner != 0;
+    // This workgroup's share of the tile's offsets (all of them unsplit), by
+    // the tile's own offset box.  The thin bands of Low / High pairs are split
+    // along the inner axis: its runs are the long ones, so every share gets a
+    // piece of every outer offset's run, where an outer-offset split left one
+    // or two uneven outer offsets per share.  Diagonal bands, whose inner runs
+    // are short and shift with the outer offset, are split along the outer
+    // axis.  (DESIGN.md §4.2 has both measured alone.)
+    const bool SPLIT_IN = 4 * min(bw, bh) < max(bw, bh);
     const int nsplit = SPLIT_IN ? n_in : n_out;
     const int s_lo = (int)((long long)nsplit * share / nshare);
     const int s_hi = (int)((long long)nsplit * (share + 1) / nshare);
@@ -661,19 +544,18 @@ __global__ __launch_bounds__(256, tune::kPlaneMinBlocks) void ref_plane3_kernel(
             const int4 e = ends[(size_t)y * W + x];
             const Line L = make_line(e.x, e.y, e.z, e.w);
             const int bx0 = L.x0 - x - dxlo, by0 = L.y0 - y - dylo;
-            // only the points whose major-axis coordinate (b0 + i) can lie in
-            // this pass's outer range or this share's inner range, whichever
-            // axis is the line's major one: a share or a later pass no longer
-            // re-walks the whole line (tune::kPlaneWalkRange)
+            // the line's points [i0, i1), clipped to those whose major-axis
+            // coordinate (b0 + i) can lie in this pass's outer range or this
+            // share's inner range, whichever axis is the line's major one: a
+            // share or a later pass does not re-walk the whole line
+            // (ranged walk)
             int i0 = 0, i1 = L.n;
-            if constexpr (tune::kPlaneWalkRange != 0) {
-                const bool outer_major = cm != (L.high != 0);   // outer axis x (cm) is Low's major
-                const int b0 = L.high ? by0 : bx0;
-                const int lo = outer_major ? oa : i_lo;
-                const int len = outer_major ? nl : (int)i_len;
-                i0 = max(0, lo - b0);
-                i1 = min(L.n, lo + len - b0);
-            }
+            const bool outer_major = cm != (L.high != 0);   // outer axis x (cm) is Low's major
+            const int b0 = L.high ? by0 : bx0;
+            const int w_lo = outer_major ? oa : i_lo;
+            const int w_len = outer_major ? nl : (int)i_len;
+            i0 = max(i0, w_lo - b0);
+            i1 = min(i1, w_lo + w_len - b0);
             // minor offset of point i: floor((a i + major - 1) / b), then
             // advanced incrementally (it grows by at most one per step, a <= b)
             const int num0 = L.a * i0 + L.major - 1;
@@ -783,7 +665,7 @@ __global__ __launch_bounds__(256, tune::kPlaneMinBlocks) void ref_plane3_kernel(
                     line_interval(po[j], pa[j], pn[j], high[j] == cm, neg[j], d_out, lo[j],
                                   len[j], ib0[j]);
 #pragma unroll
-                for (int j = 0; j < 8; j++)   // len | first candidate index << 16 (both < 65536)
+                for (int j = 0; j < 8; j++)
                     lb[j] = (unsigned)len[j] | ((unsigned)(lo[j] + ib0[j]) << 16);
                 for (int wc = wlo >> 5; wc <= (whi >> 5); wc++) {
                     unsigned m =
@@ -798,52 +680,36 @@ __global__ __launch_bounds__(256, tune::kPlaneMinBlocks) void ref_plane3_kernel(
                         unsigned csA[8], csB[8];
                         colsums(RA, reA0, reA1, ob + ca * os, csA);
                         colsums(RB, reB0, reB1, ob + cb * os, csB);
-                        if constexpr (tune::kPlaneStageMajor != 0) {
-                            // the 16 scans stage by stage (independent DPP adds
-                            // between dependent ones: no s_nop), all 8
-                            // ds_bpermute issued before the first is consumed,
-                            // and a branch-free first-minimum update
-                            // rows in groups of G: 2G DPP chains in flight, and
-                            // fewer live registers than all 8 rows at once
-                            constexpr int G = tune::kPlaneStageMajor > 0 ? tune::kPlaneStageMajor : 1;
+                        // The box-sum scans of G rows at a time, stage by stage
+                        // (2G independent DPP chains between dependent adds: no
+                        // s_nop, and fewer live registers than all 8 rows at
+                        // once), the G ds_bpermute issued before the first is
+                        // consumed, and a branch-free first-minimum update.
+                        constexpr int G = tune::kPlaneStageMajor;
+                        static_assert(G >= 1 && 8 % G == 0, "rows per scan group");
 #pragma unroll
-                            for (int j0 = 0; j0 < 8; j0 += G) {
-                                unsigned Pa[G], V[G];
+                        for (int j0 = 0; j0 < 8; j0 += G) {
+                            unsigned Pa[G], V[G];
 #pragma unroll
-                                for (int j = 0; j < G; j++) { Pa[j] = csA[j0 + j]; V[j] = csB[j0 + j]; }
-                                scan64_dpp_n<G>(Pa, V);
+                            for (int j = 0; j < G; j++) { Pa[j] = csA[j0 + j]; V[j] = csB[j0 + j]; }
+                            scan64_dpp_n<G>(Pa, V);
 #pragma unroll
-                                for (int j = 0; j < G; j++) {
-                                    const unsigned ta = (unsigned)__builtin_amdgcn_readlane((int)Pa[j], 63);
-                                    V[j] = lane < W2 - 1 ? V[j] + ta : Pa[j];
-                                    V[j] = (unsigned)__builtin_amdgcn_ds_bpermute(src, (int)V[j]);
-                                    Pa[j] -= csA[j0 + j];          // exclusive prefix
-                                }
-#pragma unroll
-                                for (int j = 0; j < G; j++) {
-                                    const unsigned sad = V[j] - Pa[j];
-                                    const unsigned tt = (unsigned)(d_in - lo[j0 + j]);
-                                    const unsigned x = lb[j0 + j];
-                                    const Key key = WIDE ? ((Key)sad << 32) | (Key)(tt + (x >> 16))
-                                                         : (Key)((sad << 12) | (tt + (x >> 16)));
-                                    const bool on = tt < (x & 0xffffu);
-                                    best[j0 + j] = min(best[j0 + j], on ? key : KNONE);
-                                }
+                            for (int j = 0; j < G; j++) {
+                                const unsigned ta = (unsigned)__builtin_amdgcn_readlane((int)Pa[j], 63);
+                                V[j] = lane < W2 - 1 ? V[j] + ta : Pa[j];
+                                V[j] = (unsigned)__builtin_amdgcn_ds_bpermute(src, (int)V[j]);
+                                Pa[j] -= csA[j0 + j];          // exclusive prefix
                             }
-                        } else {
 #pragma unroll
-                        for (int j = 0; j < 8; j++) {
-                            const unsigned Pa = scan64_dpp(csA[j]), Pb = scan64_dpp(csB[j]);
-                            const unsigned ta = (unsigned)__builtin_amdgcn_readlane((int)Pa, 63);
-                            const unsigned V = lane < W2 - 1 ? Pb + ta : Pa;
-                            const unsigned hi =
-                                (unsigned)__builtin_amdgcn_ds_bpermute(src, (int)V);
-                            const unsigned sad = hi - Pa + csA[j];
-                            const Key key = WIDE ? ((Key)sad << 32) | (Key)(unsigned)(d_in + ib0[j])
-                                                 : (Key)((sad << 12) | (unsigned)(d_in + ib0[j]));
-                            const bool on = (unsigned)(d_in - lo[j]) < (unsigned)len[j];
-                            best[j] = on ? min(best[j], key) : best[j];
-                        }
+                            for (int j = 0; j < G; j++) {
+                                const unsigned sad = V[j] - Pa[j];
+                                const unsigned tt = (unsigned)(d_in - lo[j0 + j]);
+                                const unsigned x = lb[j0 + j];
+                                const Key key = WIDE ? ((Key)sad << 32) | (Key)(tt + (x >> 16))
+                                                     : (Key)((sad << 12) | (tt + (x >> 16)));
+                                const bool on = tt < (x & 0xffffu);
+                                best[j0 + j] = min(best[j0 + j], on ? key : KNONE);
+                            }
                         }
                     }
                 }
@@ -938,104 +804,59 @@ hipError_t launch_ref_endpoints(Ctx& c, int W, int H, const sva_camera& cref,
     return hipGetLastError();
 }
 
-// Shares per tile: about four rounds of the chip's workgroup slots in all,
-// rounded, within [kPlaneSplitMin, kPlaneSplitMax] -- 1080p (990 tiles, 768
-// slots), 1440p and 4K 3, 1280x720 and smaller 6.  Measured with every tile
-// split S ways (profiles/r05_v5/plane_walk/n*_*.log.txt, r6q/): the shares
-// fill the last round and balance the uneven tile work (a Low pair's tiles
-// near the image border carry fewer planes); more shares than that pay more
-// per-share setup than they save.
-static int plane_shares(long long tiles, int cu_count) {
-    const long long slots = (long long)cu_count * tune::kPlaneMinBlocks;
-    if (tune::kPlaneSplitMax <= 1 || slots <= 0 || tiles <= 0) return 1;
-    long long s = (tune::kPlaneSplitRounds * slots + tiles / 2) / tiles;
-    if (s > tune::kPlaneSplitMax) s = tune::kPlaneSplitMax;
-    if (s < tune::kPlaneSplitMin) s = tune::kPlaneSplitMin;
-    return (int)s;
-}
-
+// plan (ref_plan.h) -> clean keys -> match kernel -> finalize
 hipError_t launch_ref_match(Ctx& c, const uint8_t* ref, const uint8_t* other, int W, int H,
-                            size_t pitch, const uint8_t* mask, const int32_t* ends,
+                            size_t pitch, const uint8_t* mask, const int32_t* ends_,
                             const uint8_t* valid_in, int k, uint8_t* disp_u8,
                             uint16_t* disp_u16, uint8_t* valid_out) {
     ScopedKernelTimer t(c, "ref_match");
-    const long long npx = (long long)(W - 2 * k) * (H - 2 * k);
-    if (npx <= 0) return hipSuccess;
-    if (k > PT_MAXK) {
-        // windows wider than the plane kernel's region (63 + 2k <= 127
-        // columns): one wave per pixel, first minimum in a u64 wave key
-        const dim3 grid((unsigned)((W - 2 * k + 3) / 4), (unsigned)(H - 2 * k));
-        hipLaunchKernelGGL(ref_pixel_kernel, grid, dim3(256), 0, c.stream, ref, other, W, H, pitch,
-                           mask, (const int4*)ends, valid_in, k, disp_u8, disp_u16, valid_out);
+    const RefMatchPlan p = ref_match_plan(W, H, k, c.cu_count, c.dbg_plane_split);
+    const int4* ends = (const int4*)ends_;
+    if (p.route == RefRoute::None) return hipSuccess;
+    if (p.route == RefRoute::Pixel) {
+        hipLaunchKernelGGL(ref_pixel_kernel, dim3((unsigned)p.gx, (unsigned)p.gy), dim3(256), 0,
+                           c.stream, ref, other, W, H, pitch, mask, ends, valid_in, k, disp_u8,
+                           disp_u16, valid_out);
         return hipGetLastError();
     }
-    // offset-plane algorithm for k = 1..32
-    const int gx = (W - 2 * k + 63) / 64, gy = (H - 2 * k + P3_ROWS - 1) / P3_ROWS;
-    const long long tiles = (long long)gx * gy;
-    int nsh = plane_shares(tiles, c.cu_count);
-    // SVA_DEBUG_PLANE_SPLIT (sva_set_debug): every tile in n shares, so the
-    // parity tests cover every share count at every size
-    if (c.dbg_plane_split >= 1 && c.dbg_plane_split <= 16) nsh = c.dbg_plane_split;
-    const bool split = nsh > 1;
-    // a line holds at most max(W, H) - 2k + 1 candidates: 4096 or more do not
-    // fit the u32 key's 12-bit index field
-    const bool wide = W >= 4096 || H >= 4096;
-    const size_t kb = wide ? sizeof(unsigned long long) : sizeof(unsigned);
+    const bool split = p.shares > 1;
     void* keys = nullptr;
     if (split) {
-        const size_t need = (size_t)W * H * kb;
-        hipError_t e = c.ref_keys.ensure(need);
+        hipError_t e = c.ref_keys.ensure(p.key_bytes);
         if (e != hipSuccess) return e;
         keys = c.ref_keys.ptr;
         if (c.ref_keys_alloc != c.ref_keys.ptr) {   // a new allocation: nothing known clean
             c.ref_keys_alloc = c.ref_keys.ptr;
             c.ref_keys_clean = 0;
         }
-        if (c.ref_keys_clean < need) {
+        if (c.ref_keys_clean < p.key_bytes) {
             // the only memset: the first call, or a buffer past what earlier
             // finalize passes restored to all-ones
-            e = hipMemsetAsync(keys, 0xff, need, c.stream);
+            e = hipMemsetAsync(keys, 0xff, p.key_bytes, c.stream);
             if (e != hipSuccess) return e;
-            c.ref_keys_clean = need;
+            c.ref_keys_clean = p.key_bytes;
         }
         c.ref_keys_clean = 0;                        // until the finalize below is queued
     }
-    const dim3 pg3((unsigned)nsh, (unsigned)gx, (unsigned)gy);
-#define SVA_PLANE3_CASE(K_)                                                                        \
-    case K_:                                                                                       \
-        if (wide)                                                                                  \
-            hipLaunchKernelGGL((ref_plane3_kernel<K_, true>), pg3, dim3(256), 0, c.stream, ref,    \
-                               other, W, H, pitch, mask, (const int4*)ends, valid_in, disp_u8,     \
-                               disp_u16, valid_out, keys);                                         \
-        else                                                                                       \
-            hipLaunchKernelGGL((ref_plane3_kernel<K_, false>), pg3, dim3(256), 0, c.stream, ref,   \
-                               other, W, H, pitch, mask, (const int4*)ends, valid_in, disp_u8,     \
-                               disp_u16, valid_out, keys);                                         \
-        break;
-    switch (k) {
-        SVA_PLANE3_CASE(1) SVA_PLANE3_CASE(2) SVA_PLANE3_CASE(3) SVA_PLANE3_CASE(4)
-        SVA_PLANE3_CASE(5) SVA_PLANE3_CASE(6) SVA_PLANE3_CASE(7) SVA_PLANE3_CASE(8)
-        SVA_PLANE3_CASE(9) SVA_PLANE3_CASE(10) SVA_PLANE3_CASE(11) SVA_PLANE3_CASE(12)
-        SVA_PLANE3_CASE(13) SVA_PLANE3_CASE(14) SVA_PLANE3_CASE(15) SVA_PLANE3_CASE(16)
-        SVA_PLANE3_CASE(17) SVA_PLANE3_CASE(18) SVA_PLANE3_CASE(19) SVA_PLANE3_CASE(20)
-        SVA_PLANE3_CASE(21) SVA_PLANE3_CASE(22) SVA_PLANE3_CASE(23) SVA_PLANE3_CASE(24)
-        SVA_PLANE3_CASE(25) SVA_PLANE3_CASE(26) SVA_PLANE3_CASE(27) SVA_PLANE3_CASE(28)
-        SVA_PLANE3_CASE(29) SVA_PLANE3_CASE(30) SVA_PLANE3_CASE(31) SVA_PLANE3_CASE(32)
-        default: return hipErrorInvalidValue;
-    }
-#undef SVA_PLANE3_CASE
-    if (split && wide)
-        hipLaunchKernelGGL(ref_finalize_kernel<unsigned long long>,
-                           dim3((unsigned)((W + 255) / 256), (unsigned)H), dim3(256), 0, c.stream, W,
-                           H, (const int4*)ends, (unsigned long long*)keys, disp_u8, disp_u16,
-                           valid_out);
-    else if (split)
-        hipLaunchKernelGGL(ref_finalize_kernel<unsigned>, dim3((unsigned)((W + 255) / 256), (unsigned)H),
-                           dim3(256), 0, c.stream, W, H, (const int4*)ends, (unsigned*)keys,
-                           disp_u8, disp_u16, valid_out);
+    const dim3 pg3((unsigned)p.shares, (unsigned)p.gx, (unsigned)p.gy);
+    const bool launched = for_int_in<1, kRefPlaneMaxK>(k, [&](auto K) {
+        with_flag<true>(p.wide, [&](auto wide) {
+            hipLaunchKernelGGL((ref_plane3_kernel<decltype(K)::value, decltype(wide)::value>), pg3,
+                               dim3(256), 0, c.stream, ref, other, W, H, pitch, mask, ends,
+                               valid_in, disp_u8, disp_u16, valid_out, keys);
+        });
+    });
+    if (!launched) return hipErrorInvalidValue;
+    if (split)
+        with_flag<true>(p.wide, [&](auto wide) {
+            using Key = std::conditional_t<decltype(wide)::value, unsigned long long, unsigned>;
+            hipLaunchKernelGGL(ref_finalize_kernel<Key>,
+                               dim3((unsigned)((W + 255) / 256), (unsigned)H), dim3(256), 0,
+                               c.stream, W, H, ends, (Key*)keys, disp_u8, disp_u16, valid_out);
+        });
     const hipError_t err = hipGetLastError();
     // the finalize pass restores every key of the W x H region to all-ones
-    if (split && err == hipSuccess) c.ref_keys_clean = (size_t)W * H * (wide ? 8 : 4);
+    if (split && err == hipSuccess) c.ref_keys_clean = p.key_bytes;
     return err;
 }
 

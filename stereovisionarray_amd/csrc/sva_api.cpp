@@ -459,7 +459,7 @@ int check_ref_args(Ctx* c, int W, int H, int k, double t_near, double t_far) {
     if (2LL * k >= W || 2LL * k >= H) return fail(c, SVA_ERR_INVALID_ARG, "image smaller than window");
     if (!(t_near > 0.0) || !(t_far > 0.0))
         return fail(c, SVA_ERR_INVALID_ARG, "ray parameters must be positive");
-    // the plane kernel packs line geometry in 16-bit fields (refpath.hip)
+    // the plane kernel packs line geometry in 16-bit fields (ref_line.h)
     if (W > 32767 || H > 32767)
         return fail(c, SVA_ERR_UNSUPPORTED, "Mode R supports W, H <= 32767");
     return SVA_OK;

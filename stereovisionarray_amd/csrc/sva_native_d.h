@@ -1,6 +1,7 @@
-// sva_native_d.h -- the native volume widths of Mode S.  Plain C++: the host
-// argument checks (array_args.h) and the aggregation plan (agg_plan.h) compile
-// it without a HIP header.
+// sva_native_d.h -- the native volume widths of Mode S, and the launchers'
+// instance ladders (a run-time class, integer or flag as a template argument).
+// Plain C++: the host argument checks (array_args.h) and the aggregation plan
+// (agg_plan.h) compile it without a HIP header.
 #pragma once
 
 #include <type_traits>
@@ -36,6 +37,21 @@ bool for_native_d(int D, F&& f) {
         case 192: f(NativeD<12, TLW, tune::kDiagPair12 != 0, tune::kPathMinima12 != 0>{}); return true;
         case 256: f(NativeD<16, TLW, tune::kDiagPair16 != 0, tune::kPathMinima16 != 0>{}); return true;
         default: return false;
+    }
+}
+
+// f(std::integral_constant<int, n>{}) for n in [Lo, Hi], one instance per value
+// (instantiated from Lo up); false, and no call, for any other n.
+template <int Lo, int Hi, class F>
+bool for_int_in(int n, F&& f) {
+    if constexpr (Lo > Hi) {
+        return false;
+    } else {
+        if (n == Lo) {
+            f(std::integral_constant<int, Lo>{});
+            return true;
+        }
+        return for_int_in<Lo + 1, Hi>(n, f);
     }
 }
 

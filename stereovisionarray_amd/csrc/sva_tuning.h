@@ -234,47 +234,18 @@ constexpr int kCensusCost2Lines = 8;
 constexpr int kPlaneOuKB = 24;      // staged O chunk (KB)
 constexpr int kPlaneWords = 1024;   // offset bitmap per pass: 32K bits
 constexpr int kPlaneMinBlocks = 3;  // __launch_bounds__ min workgroups per CU
-// Plane loop body (round 5): the box-sum scans of G
-// rows at a time stage by stage (2G independent DPP chains: no s_nop), the
-// G ds_bpermute before their uses, a branch-free first-minimum update
-// (kPlaneStageMajor = G in {2, 4, 8}); or row by row (0).
+// Plane loop body (round 5): the box-sum scans of this
+// many rows (a divisor of 8) at a time, stage by stage: DESIGN.md §4.2.
 constexpr int kPlaneStageMajor = 2;
-// line_interval's division by each pixel's a: hoisted by the compiler (0:
-// 32 B/lane of scratch at k = 20, reloaded per outer offset) or recomputed
-// per outer offset (1: no scratch at k = 20, diagonal pairs 9 % slower).
-constexpr int kPlaneNoHoistDiv = 0;
-// Each thread's eight line offsets in LDS (8 KB per workgroup), reloaded per
-// outer offset, instead of eight VGPRs held across the plane loop (1), at
-// every k whose LDS still leaves kPlaneMinBlocks workgroups per CU.
-constexpr int kPlanePoLds = 1;
 // Every tile of the plane kernel is split into S shares of its offsets, each
 // its own workgroup; the per-pixel keys meet in global memory by atomicMin
-// (refpath.hip plane_shares, ref_finalize_kernel).  S = kPlaneSplitRounds
-// rounds of workgroup slots over the tile count, rounded, within
-// [kPlaneSplitMin, kPlaneSplitMax].  kPlaneSplitInner: shares of the inner offsets (1), of the
-// outer offsets (0), or per tile by its offset box (2).  ref_match ms,
-// in-process, unsplit / inner / outer, every tile split
-// (profiles/r05_v5/plane_split/): 960x540 12->11 0.216 / 0.157 / 0.178,
-// 12->7 0.209 / 0.153 / 0.177, 12->6 0.298 / 0.194 / 0.185, 12->18 0.278 /
-// 0.185 / 0.176; 640x480 12->11 0.147 / 0.091 / 0.104, 12->6 0.205 / 0.106 /
-// 0.098.  With the ranged bitmap walk (kPlaneWalkRange) every share count
-// S = 1 / 2 / 3 / 4 / 6, ms for 12->11 + 12->6 (profiles/r05_v5/plane_walk/
-// n*): 1080p 1.539 / 1.408 / 1.343 / 1.363 / 1.423; 1280x720 0.699 / 0.589 /
-// 0.541 / 0.563 / 0.549; 960x540 0.514 / 0.355 / 0.319 / 0.304 / 0.311;
-// 640x480 0.354 / 0.245 / 0.192 / 0.190 / 0.169.  S = 1 / 2 / 3 (r6q):
-// 2560x1440 3.383 / 3.206 / 2.832; 3840x2160 9.190 / 8.803 / 8.590 (the
-// round-based rule alone gave S = 1 at 4K, 2.3-4.7 % slower than the
-// previous split band).
+// (ref_plan.h plane_shares, refpath.hip ref_finalize_kernel).  S =
+// kPlaneSplitRounds rounds of workgroup slots over the tile count, rounded,
+// within [kPlaneSplitMin, kPlaneSplitMax]: the sweep of S = 1..6 at six frame
+// sizes (profiles/r05_v5/plane_walk/n*, r6q) is the table in DESIGN.md §4.2.
 constexpr int kPlaneSplitMin = 3;
 constexpr int kPlaneSplitMax = 6;
 constexpr int kPlaneSplitRounds = 4;
-constexpr int kPlaneSplitInner = 2;
-// The plane bitmap walk visits only a line's points whose major-axis
-// coordinate falls in the pass's outer range or the share's inner range (1),
-// or every point of every distinct line (0).  Without it every share re-walks
-// whole lines: 1080p 12->11 with 3 shares 0.728 -> 0.671 ms, 12->7 0.653 ->
-// 0.598 (profiles/r05_v5/plane_walk/r_3_*).
-constexpr int kPlaneWalkRange = 1;
 
 }  // namespace tune
 }  // namespace sva

@@ -32,7 +32,7 @@ sys.path.insert(0, os.path.join(ROOT, "oracle"))
 
 def line_offsets(x, y, a, b):
     """Offsets (cx - x, cy - y) of bresenham(pixel1 = a, pixel2 = b) in the
-    closed form of refpath.hip make_line / line_point."""
+    closed form of ref_line.h make_line / line_point."""
     ax, ay, bx, by = int(a[0]), int(a[1]), int(b[0]), int(b[1])
     pts = []
     if abs(ay - by) < abs(ax - bx):
