@@ -409,6 +409,65 @@ int sva_wta_hv_d(void* ctx, const uint8_t* C, size_t C_bytes, const uint8_t* dia
                  size_t diag_bytes, const uint8_t* hckpt, size_t hckpt_bytes,
                  const uint8_t* vckpt, size_t vckpt_bytes, int width, int height,
                  const sva_sgm_params* p, uint16_t* disp, float* subpix);
+/* The same two stages on the plan a whole frame runs: what
+ * sva_disparity_sgm* launches after its cost kernel, on the caller's buffers
+ * in place of the context's two workspaces.  The route is the frame's own:
+ * two pair-sum volumes (§4.15) where the D class has them, 2 * P2 fits a u8
+ * and width * height reaches the pixel threshold, else four volumes; minima
+ * planes (§4.17) where the D class has them.
+ *   D: the volumes have the native width layout.D = 64, 128, 192 or 256, the
+ *     smallest that holds p->D (the other stage entries take that width as
+ *     p->D; here p->D in 1..256 is the caller's disparity count, as for whole
+ *     frames, and C holds 255 at d >= p->D, as sva_census_cost_d's padded
+ *     frames and sva_cost_fuse_d's dreal do, §4.7).
+ *   sva_frame_layout_of (no device needed): the plan of this shape and these
+ *     penalties.  pair_min_pixels = -1: the built-in threshold; the two
+ *     entries use the context's (SVA_DEBUG_DIAG_PAIR_MIN_PIXELS or built in).
+ *   volumes = [n_volumes][H][W][D] u8.  route 0: L_4 .. L_7.  route 1:
+ *     E_0 = (L_4 - C) + (L_5 - C), E_1 = (L_6 - C) + (L_7 - C).
+ *   ckpt, one buffer of ckpt_bytes; at
+ *     hck_off: [2][H][nsx][D], as hckpt above;
+ *     vck_off: [2][nsy][W][D], as vckpt above;
+ *     pair_off (route 1): [2][nsy][W][D], plane j of the pair 4+5 (j = 0) or
+ *       6+7 (j = 1).  With q = (nsy / 2): row s < q - 1 holds
+ *       L_{4+2j}(x, s*seg + seg - 1), row s > q holds L_{5+2j}(x, s*seg); rows
+ *       q - 1 and q are not written (those states stay in registers, §4.16);
+ *     hmn_off (minima): [2][H][nsx][8], vmn_off: [2][nsy][W][8]: the minimum
+ *       each step of directions 0, 1 / 2, 3 entered with, 0 at a line's first
+ *       pixel, else min_k L_r of the line's previous pixel.  Byte i of a
+ *       segment is its pixel i (directions 0, 2) or 7 - i (directions 1, 3);
+ *       bytes of pixels outside the image have no meaning.
+ *     At d >= p->D the volumes and checkpoints have no meaning.
+ *   sva_wta_frame_d: cost_min = cost_second = NULL and uniqueness = 0 run the
+ *     plain instance; anything else the confidence instance, by the rule of
+ *     sva_disparity_sgm_conf_d.  subpix is written when p->subpixel is set.
+ * A buffer smaller than the layout's size is SVA_ERR_INVALID_ARG before
+ * anything is launched. */
+typedef struct sva_frame_layout {
+    int32_t route;        /* 0 four volumes, 1 pair sums (SVA_DEBUG_DIAG_ROUTE) */
+    int32_t minima;       /* 1: hmn / vmn exist                                */
+    int32_t D;            /* native width of every [..][D] plane               */
+    int32_t seg, nsx, nsy;
+    int32_t n_volumes;    /* 4 or 2                                            */
+    int32_t reserved;
+    size_t cost_bytes;    /* C [H][W][D], also one route volume                */
+    size_t volumes_bytes; /* n_volumes * cost_bytes                            */
+    size_t ckpt_bytes;
+    size_t hck_off, hck_bytes;
+    size_t vck_off, vck_bytes;
+    size_t pair_off, pair_bytes;   /* bytes 0 on route 0                       */
+    size_t hmn_off, hmn_bytes;     /* bytes 0 without minima                   */
+    size_t vmn_off, vmn_bytes;
+} sva_frame_layout;
+int sva_frame_layout_of(int width, int height, const sva_sgm_params* p, long long pair_min_pixels,
+                        sva_frame_layout* out);
+int sva_paths_frame_d(void* ctx, const uint8_t* C, size_t C_bytes, int width, int height,
+                      const sva_sgm_params* p, uint8_t* volumes, size_t volumes_bytes,
+                      uint8_t* ckpt, size_t ckpt_bytes);
+int sva_wta_frame_d(void* ctx, const uint8_t* C, size_t C_bytes, const uint8_t* volumes,
+                    size_t volumes_bytes, const uint8_t* ckpt, size_t ckpt_bytes, int width,
+                    int height, const sva_sgm_params* p, int uniqueness, uint16_t* disp,
+                    float* subpix, uint16_t* cost_min, uint16_t* cost_second);
 int sva_wta_d(void* ctx, const uint16_t* S, int width, int height, const sva_sgm_params* p,
               uint16_t* disp, float* subpix);
 /* sva_wta_d with the confidence planes and the uniqueness filter of

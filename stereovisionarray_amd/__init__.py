@@ -70,7 +70,7 @@ EXPORTED = [
     "sva_batch_sgm_conf_d", "sva_array_depth_conf", "sva_cost_fuse_d", "sva_disparity_sgm_multi",
     "sva_disparity_sgm_multi_d", "sva_array_depth_mb", "sva_cost_mixed_d",
     "sva_cost_fuse_mixed_d", "sva_disparity_sgm_mixed", "sva_disparity_sgm_mixed_d",
-    "sva_array_depth_mixed",
+    "sva_array_depth_mixed", "sva_frame_layout_of", "sva_paths_frame_d", "sva_wta_frame_d",
 ]
 SVA_FUSE_MIN_COST = 0
 SVA_FUSE_MAX_MARGIN = 1
@@ -109,6 +109,20 @@ class TileLayout(ct.Structure):
                 ("diag_volumes", ct.c_int32),
                 ("cost_bytes", ct.c_size_t), ("diag_bytes", ct.c_size_t),
                 ("hckpt_bytes", ct.c_size_t), ("vckpt_bytes", ct.c_size_t)]
+
+
+class FrameLayout(ct.Structure):
+    """Mirror of ``sva_frame_layout`` (include/sva.h): the frame plan's buffers."""
+    _fields_ = [("route", ct.c_int32), ("minima", ct.c_int32), ("D", ct.c_int32),
+                ("seg", ct.c_int32), ("nsx", ct.c_int32), ("nsy", ct.c_int32),
+                ("n_volumes", ct.c_int32), ("reserved", ct.c_int32),
+                ("cost_bytes", ct.c_size_t), ("volumes_bytes", ct.c_size_t),
+                ("ckpt_bytes", ct.c_size_t),
+                ("hck_off", ct.c_size_t), ("hck_bytes", ct.c_size_t),
+                ("vck_off", ct.c_size_t), ("vck_bytes", ct.c_size_t),
+                ("pair_off", ct.c_size_t), ("pair_bytes", ct.c_size_t),
+                ("hmn_off", ct.c_size_t), ("hmn_bytes", ct.c_size_t),
+                ("vmn_off", ct.c_size_t), ("vmn_bytes", ct.c_size_t)]
 
 
 class PairJob(ct.Structure):
@@ -199,6 +213,10 @@ def _load() -> ct.CDLL:
         "sva_paths_tile_d": (i32, [vp, vp, sz, i32, i32, P(SgmParams), vp, sz, vp, sz, vp, sz]),
         "sva_wta_hv_d": (i32, [vp, vp, sz, vp, sz, vp, sz, vp, sz, i32, i32, P(SgmParams), vp,
                                vp]),
+        "sva_frame_layout_of": (i32, [i32, i32, P(SgmParams), ct.c_longlong, P(FrameLayout)]),
+        "sva_paths_frame_d": (i32, [vp, vp, sz, i32, i32, P(SgmParams), vp, sz, vp, sz]),
+        "sva_wta_frame_d": (i32, [vp, vp, sz, vp, sz, vp, sz, i32, i32, P(SgmParams), i32, vp, vp,
+                                  vp, vp]),
         "sva_disparity_ref": (i32, [vp, vp, vp, i32, i32, sz, vp, P(Camera), P(Camera), i32,
                                     dbl, dbl, vp, vp, vp]),
         "sva_disparity_ref_d": (i32, [vp, vp, vp, i32, i32, sz, vp, P(Camera), P(Camera), i32,
@@ -299,6 +317,16 @@ def tile_layout(W: int, H: int, D: int) -> TileLayout:
     st = lib.sva_tile_layout_of(W, H, D, ct.byref(out))
     if st != SVA_OK:
         raise SvaError(st, "sva_tile_layout_of")
+    return out
+
+
+def frame_layout(W: int, H: int, params: SgmParams, pair_min_pixels: int = -1) -> FrameLayout:
+    """The plan a frame of this shape and these penalties runs (sva_frame_layout_of;
+    no device needed).  pair_min_pixels = -1: the built-in pair-route threshold."""
+    out = FrameLayout()
+    st = lib.sva_frame_layout_of(W, H, ct.byref(params), pair_min_pixels, ct.byref(out))
+    if st != SVA_OK:
+        raise SvaError(st, "sva_frame_layout_of")
     return out
 
 
@@ -606,6 +634,17 @@ class Context:
         self._chk(lib.sva_wta_hv_d(self.h, _ptr(C), C_bytes, _ptr(diag), diag_bytes, _ptr(hck),
                                    hck_bytes, _ptr(vck), vck_bytes, W, H, ct.byref(params),
                                    _ptr(disp), _ptr(sub)))
+
+    def paths_frame_d(self, C, C_bytes, W, H, params, volumes, volumes_bytes, ckpt, ckpt_bytes):
+        self._chk(lib.sva_paths_frame_d(self.h, _ptr(C), C_bytes, W, H, ct.byref(params),
+                                        _ptr(volumes), volumes_bytes, _ptr(ckpt), ckpt_bytes))
+
+    def wta_frame_d(self, C, C_bytes, volumes, volumes_bytes, ckpt, ckpt_bytes, W, H, params,
+                    uniqueness, disp, sub=None, cost_min=None, cost_second=None):
+        self._chk(lib.sva_wta_frame_d(self.h, _ptr(C), C_bytes, _ptr(volumes), volumes_bytes,
+                                      _ptr(ckpt), ckpt_bytes, W, H, ct.byref(params),
+                                      int(uniqueness), _ptr(disp), _ptr(sub), _ptr(cost_min),
+                                      _ptr(cost_second)))
 
     def wta_d(self, S, W, H, params, disp, sub=None):
         self._chk(lib.sva_wta_d(self.h, _ptr(S), W, H, ct.byref(params), _ptr(disp), _ptr(sub)))

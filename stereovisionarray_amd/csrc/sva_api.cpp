@@ -179,21 +179,70 @@ AggShape agg_shape(int W, int H, int Dp, const sva_sgm_params* p) {
     return AggShape{W, H, Dp, p->D, p->P1, p->P2, p->dmin};
 }
 
-// The route, the sizes and the layout are frame_plan's (agg_plan.h); the
-// pixel threshold of the pair route is the tuned one or its debug override.
+// A frame's aggregation, for the product (paths_wta) and for the stage
+// entries that run the same plan on a caller's buffers (sva_paths_frame_d,
+// sva_wta_frame_d, sva_frame_layout_of).  The route, the sizes and the layout
+// are frame_plan's (agg_plan.h); the pixel threshold of the pair route is the
+// tuned one unless pair_min_pixels >= 0 (the context's debug override, or the
+// layout query's argument).  Its buffers are carve's, over the context's two
+// workspaces or the caller's two buffers.
+AggPlan frame_agg_plan(long long pair_min_pixels, int W, int H, int Dp, const sva_sgm_params* p) {
+    return frame_plan(agg_shape(W, H, Dp, p),
+                      pair_min_pixels >= 0 ? pair_min_pixels : tune::kDiagPairMinPixels);
+}
+
 // cf set: wta_hv's confidence instance instead of the plain one.
 int paths_wta(Ctx* c, const uint8_t* C, int W, int H, const sva_sgm_params* p, int Dp,
               uint16_t* disp, float* sub, const ConfOut* cf = nullptr) {
     if (!is_native_d(Dp)) return fail(c, SVA_ERR_UNSUPPORTED, "no tile pipeline for this D");
-    const long long minpx = c->dbg_pair_min_pixels >= 0 ? (long long)c->dbg_pair_min_pixels
-                                                        : tune::kDiagPairMinPixels;
-    const AggPlan plan = frame_plan(agg_shape(W, H, Dp, p), minpx);
+    const AggPlan plan = frame_agg_plan(c->dbg_pair_min_pixels, W, H, Dp, p);
     SVA_HIP(c, c->paths.ensure(plan.paths_bytes), "path workspace");
     SVA_HIP(c, c->ckpt.ensure(plan.ckpt_bytes), "checkpoint workspace");
     const AggBuffers b = carve(plan, C, c->paths.ptr, c->ckpt.ptr);
     SVA_HIP(c, launch_paths(*c, plan, b), "paths launch");
     SVA_HIP(c, launch_wta_hv(*c, plan, b, disp, sub, cf), "wta launch");
     c->last_diag_route = plan.route == AggRoute::Pair ? 1 : 0;
+    return SVA_OK;
+}
+
+// sva_frame_layout of a frame plan.
+sva_frame_layout frame_layout(const AggPlan& plan) {
+    sva_frame_layout l;
+    std::memset(&l, 0, sizeof(l));
+    l.route = plan.route == AggRoute::Pair ? 1 : 0;
+    l.minima = plan.minima ? 1 : 0;
+    l.D = plan.D;
+    l.seg = 1 << plan.tg.seg_log2;
+    l.nsx = plan.tg.nsx;
+    l.nsy = plan.tg.nty;
+    l.n_volumes = (int32_t)(plan.paths_bytes / plan.vol);
+    l.cost_bytes = plan.vol;
+    l.volumes_bytes = plan.paths_bytes;
+    l.ckpt_bytes = plan.ckpt_bytes;
+    l.hck_off = plan.hck_off;
+    l.hck_bytes = plan.tg.hck_bytes;
+    l.vck_off = plan.vck_off;
+    l.vck_bytes = plan.tg.vck_bytes;
+    l.pair_off = plan.pair_off;
+    l.pair_bytes = plan.mn_off - plan.pair_off;
+    l.hmn_off = plan.mn_off;
+    l.hmn_bytes = plan.minima ? plan.tg.hmn_bytes : 0;
+    l.vmn_off = plan.mn_off + l.hmn_bytes;
+    l.vmn_bytes = plan.minima ? plan.tg.vmn_bytes : 0;
+    return l;
+}
+
+// Caller buffers of the frame stages against the plan, as check_tile_buffers
+// below: an argument error before anything reaches the device.
+int check_frame_buffers(Ctx* c, const AggPlan& plan, const void* C, size_t C_bytes,
+                        const void* volumes, size_t volumes_bytes, const void* ckpt,
+                        size_t ckpt_bytes) {
+    if (!C || !volumes || !ckpt) return fail(c, SVA_ERR_INVALID_ARG, "null stage buffer");
+    if (C_bytes < plan.vol) return fail(c, SVA_ERR_INVALID_ARG, "cost buffer smaller than [H][W][D]");
+    if (volumes_bytes < plan.paths_bytes)
+        return fail(c, SVA_ERR_INVALID_ARG, "volume buffer smaller than the layout's volumes_bytes");
+    if (ckpt_bytes < plan.ckpt_bytes)
+        return fail(c, SVA_ERR_INVALID_ARG, "checkpoint buffer smaller than the layout's ckpt_bytes");
     return SVA_OK;
 }
 
@@ -1424,6 +1473,51 @@ int sva_wta_hv_d(void* ctx, const uint8_t* C, size_t C_bytes, const uint8_t* dia
                              AggBuffers{C, const_cast<uint8_t*>(diag), const_cast<uint8_t*>(hckpt),
                                         const_cast<uint8_t*>(vckpt), nullptr},
                              disp, p->subpixel ? sub : nullptr),
+            "wta launch");
+    return SVA_OK;
+}
+
+int sva_frame_layout_of(int W, int H, const sva_sgm_params* p, long long pair_min_pixels,
+                        sva_frame_layout* out) {
+    if (!out || W <= 0 || H <= 0 || check_sgm(nullptr, p, W, H) != SVA_OK) return SVA_ERR_INVALID_ARG;
+    *out = frame_layout(frame_agg_plan(pair_min_pixels, W, H, padded_D(p->D), p));
+    return SVA_OK;
+}
+
+int sva_paths_frame_d(void* ctx, const uint8_t* C, size_t C_bytes, int W, int H,
+                      const sva_sgm_params* p, uint8_t* volumes, size_t volumes_bytes,
+                      uint8_t* ckpt, size_t ckpt_bytes) {
+    Ctx* c = as_ctx(ctx);
+    SVA_CHECK_CTX(c);
+    int s;
+    if ((s = check_sgm(c, p, W, H))) return s;
+    if (W <= 0 || H <= 0) return fail(c, SVA_ERR_INVALID_ARG, "bad argument");
+    const AggPlan plan = frame_agg_plan(c->dbg_pair_min_pixels, W, H, padded_D(p->D), p);
+    if ((s = check_frame_buffers(c, plan, C, C_bytes, volumes, volumes_bytes, ckpt, ckpt_bytes)))
+        return s;
+    SVA_HIP(c, launch_paths(*c, plan, carve(plan, C, volumes, ckpt)), "paths launch");
+    return SVA_OK;
+}
+
+int sva_wta_frame_d(void* ctx, const uint8_t* C, size_t C_bytes, const uint8_t* volumes,
+                    size_t volumes_bytes, const uint8_t* ckpt, size_t ckpt_bytes, int W, int H,
+                    const sva_sgm_params* p, int uniqueness, uint16_t* disp, float* sub,
+                    uint16_t* cost_min, uint16_t* cost_second) {
+    Ctx* c = as_ctx(ctx);
+    SVA_CHECK_CTX(c);
+    int s;
+    if ((s = check_sgm(c, p, W, H)) || (s = check_uniqueness(c, uniqueness))) return s;
+    if (W <= 0 || H <= 0) return fail(c, SVA_ERR_INVALID_ARG, "bad argument");
+    const AggPlan plan = frame_agg_plan(c->dbg_pair_min_pixels, W, H, padded_D(p->D), p);
+    if ((s = check_frame_buffers(c, plan, C, C_bytes, volumes, volumes_bytes, ckpt, ckpt_bytes)))
+        return s;
+    if (!disp) return fail(c, SVA_ERR_INVALID_ARG, "null disparity output");
+    const ConfOut cf{cost_min, cost_second, uniqueness, p->invalid};
+    const bool conf = cost_min || cost_second || uniqueness;
+    // (the kernel only reads the caller's volumes and checkpoints)
+    SVA_HIP(c, launch_wta_hv(*c, plan, carve(plan, C, const_cast<uint8_t*>(volumes),
+                                             const_cast<uint8_t*>(ckpt)),
+                             disp, p->subpixel ? sub : nullptr, conf ? &cf : nullptr),
             "wta launch");
     return SVA_OK;
 }

@@ -14,11 +14,10 @@ import numpy as np
 import pytest
 import torch
 
+from stage_expect import check_stages
 from stereovisionarray_amd import synth
 
 pytestmark = pytest.mark.gpu
-
-SUB_TOL = 1e-5
 
 
 def dev(a, d):
@@ -50,32 +49,6 @@ def run_tiles(ctx, sva, torch_dev, C, p):
 def oracle_cost(oracle, H, W, D, dmin, seed):
     L, R, _ = synth.stereo_pair(H, W, D, dmin, -1, seed=seed, stripes=5, step=7)
     return oracle.cost(oracle.census(L), oracle.census(R), D, dmin, -1)
-
-
-def check_stages(oracle, C, dmin, res, P1=10, P2=120):
-    H, W, D = C.shape
-    diag, hck, vck, disp, sub, lay = res
-    seg = lay.seg
-    vols = [oracle.path(C, r, P1, P2) for r in range(8)]
-    vol_dirs = [4, 5, 6, 7]            # the four diagonal volumes, in direction order
-    for slot, r in enumerate(vol_dirs):
-        assert np.array_equal(diag[slot], vols[r]), f"direction {r}"
-    for s in range(lay.nsx):
-        if s * seg + seg < W:          # L_0 at the segment's last column
-            assert np.array_equal(hck[0, :, s], vols[0][:, s * seg + seg - 1]), ("h0", s)
-        if s > 0:                      # L_1 at the segment's first column
-            assert np.array_equal(hck[1, :, s], vols[1][:, s * seg]), ("h1", s)
-    for s in range(lay.nsy):
-        if s * seg + seg < H:          # L_2 at the segment's last row
-            assert np.array_equal(vck[0, s], vols[2][s * seg + seg - 1]), ("v0", s)
-        if s > 0:                      # L_3 at the segment's first row
-            assert np.array_equal(vck[1, s], vols[3][s * seg]), ("v1", s)
-    S = np.zeros(C.shape, np.uint16)
-    for v in vols:
-        S += v
-    od, osub = oracle.wta(S, dmin, True)
-    assert np.array_equal(disp, od)
-    assert np.max(np.abs(sub - osub)) <= SUB_TOL
 
 
 @pytest.mark.parametrize("D", [64, 128, 192, 256])
