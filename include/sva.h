@@ -640,6 +640,33 @@ int sva_fuse_depth_conf(void* ctx, const uint16_t* disps, const uint16_t* cost_m
                         const double* baselines, double f, double pixel_size, uint16_t invalid,
                         int mode, double* depth, uint8_t* n_valid, uint8_t* winner);
 
+/* Sub-pixel fusion: the four calls above with the depth of a
+ * map taken from its f32 sub-pixel disparity, baseline_i * f / ((double)
+ * subpix_i * pixel_size), so that depth is no longer quantised to whole
+ * disparities.  subpix: [n_maps][H][W] f32 (device / host), the sub-pixel maps
+ * the matchers write next to disps (NaN where a pixel was rejected).  Map i is
+ * valid at a pixel where disp_i != invalid, disp_i > 0 and subpix_i > 0.0f
+ * (false for NaN).  The winner of the cost-aware modes is chosen as above among
+ * those maps.  Where subpix_i == (float)disp_i everywhere, every output equals
+ * that of the u16 call bit for bit.  A NULL subpix returns SVA_ERR_INVALID_ARG;
+ * every other rule is that of the u16 call. */
+int sva_fuse_depth_sub_d(void* ctx, const uint16_t* disps, const float* subpix, int n_maps,
+                         int width, int height, const double* baselines, double f,
+                         double pixel_size, uint16_t invalid, double* depth, uint8_t* n_valid);
+int sva_fuse_depth_sub(void* ctx, const uint16_t* disps, const float* subpix, int n_maps,
+                       int width, int height, const double* baselines, double f,
+                       double pixel_size, uint16_t invalid, double* depth, uint8_t* n_valid);
+int sva_fuse_depth_conf_sub_d(void* ctx, const uint16_t* disps, const float* subpix,
+                              const uint16_t* cost_min, const uint16_t* cost_second, int n_maps,
+                              int width, int height, const double* baselines, double f,
+                              double pixel_size, uint16_t invalid, int mode, double* depth,
+                              uint8_t* n_valid, uint8_t* winner);
+int sva_fuse_depth_conf_sub(void* ctx, const uint16_t* disps, const float* subpix,
+                            const uint16_t* cost_min, const uint16_t* cost_second, int n_maps,
+                            int width, int height, const double* baselines, double f,
+                            double pixel_size, uint16_t invalid, int mode, double* depth,
+                            uint8_t* n_valid, uint8_t* winner);
+
 /* Disparity -> depth, CameraStereoVision.cpp:47,98-100 (f64; 0 where disp 0). */
 int sva_disparity_to_depth_d(void* ctx, const uint8_t* disp, int n, double cam_distance,
                              double f, double pixel_size, double* depth);
@@ -788,6 +815,32 @@ int sva_array_depth_mixed(void* multi, const uint8_t* const* images, int n_image
                           const int32_t* group_start, int n_groups, const double* unit_baseline,
                           double f, double pixel_size, int uniqueness, double* depth,
                           uint16_t* maps, uint16_t* cost_min, uint16_t* cost_second);
+/* Sub-pixel depth from an array frame: one entry for the
+ * three routes above.  Every job runs with subpixel = 1, whatever
+ * pairs[j].params.subpixel says, its f32 map is gathered with its u16 map, and
+ * depth comes from sva_fuse_depth_sub_d / sva_fuse_depth_conf_sub_d, so it is
+ * not quantised to whole disparities.  The gather ships 4 more bytes per pixel
+ * and job than the entry of the same route above.
+ *   SVA_ARRAY_PAIRS         as sva_array_depth_conf: mode is SVA_FUSE_MEDIAN,
+ *                           _MIN_COST or _MAX_MARGIN, per-pair lr_check works.
+ *   SVA_ARRAY_GROUPS        as sva_array_depth_mb.
+ *   SVA_ARRAY_GROUPS_MIXED  as sva_array_depth_mixed.
+ * On the group routes mode must be SVA_FUSE_MEDIAN and n_valid and winner NULL
+ * (one map per group); unit_baseline must be non-NULL for GROUPS_MIXED and NULL
+ * for the other routes.  A break of these rules or an unknown route returns
+ * SVA_ERR_INVALID_ARG before group_start is read.  subpix (nullable): host
+ * [n_jobs][H][W] f32, the jobs' sub-pixel maps (n_jobs = n_pairs, or n_groups
+ * on the group routes), NaN where the pixel was rejected.  depth, n_valid,
+ * winner, maps, cost_min, cost_second: as for the entry of the same route. */
+#define SVA_ARRAY_PAIRS 0
+#define SVA_ARRAY_GROUPS 1        /* sva_array_depth_mb's route    */
+#define SVA_ARRAY_GROUPS_MIXED 2  /* sva_array_depth_mixed's route */
+int sva_array_depth_sub(void* multi, const uint8_t* const* images, int n_images, int width,
+                        int height, size_t pitch, const sva_array_pair* pairs, int n_pairs,
+                        const int32_t* group_start, int n_groups, int route,
+                        const double* unit_baseline, double f, double pixel_size, int uniqueness,
+                        int mode, double* depth, uint8_t* n_valid, uint8_t* winner, float* subpix,
+                        uint16_t* maps, uint16_t* cost_min, uint16_t* cost_second);
 
 #ifdef __cplusplus
 }

@@ -526,6 +526,20 @@ inline std::vector<std::vector<double>> arrayDepth(const ArrayFrame& fr,
     else if (maps) fr.scatter(all, n_pairs, maps);
     return fr.split(depth);
 }
+
+// The mixed route's unit baseline of every group: unit_k * pitch, or, with
+// unit_k = 0, the group's largest baseline.
+inline std::vector<double> unitBaselines(const ArrayFrame& fr, int unit_k, double pitch) {
+    std::vector<double> unit(fr.refs.size());
+    for (size_t g = 0; g < unit.size(); g++) {
+        double u = unit_k * pitch;
+        if (!unit_k)
+            for (int j = fr.group_start[g]; j < fr.group_start[g + 1]; j++)
+                u = std::max(u, fr.ap[j].baseline);
+        unit[g] = u;
+    }
+    return unit;
+}
 }  // namespace detail
 
 // One camera-array frame over a MultiEngine: replaces the pair loop of
@@ -686,18 +700,112 @@ inline std::vector<std::vector<double>> computeArrayDepthMixed(
     if (unit_k < 0) throw Error(SVA_ERR_INVALID_ARG, "computeArrayDepthMixed: unit_k must be >= 0");
     const detail::ArrayFrame fr = detail::arrayFrame(images, cameras, pairs, p, pitch,
                                                      "computeArrayDepthMixed");
-    std::vector<double> unit(fr.refs.size());
-    for (size_t g = 0; g < unit.size(); g++) {
-        double u = unit_k * pitch;
-        if (!unit_k)
-            for (int j = fr.group_start[g]; j < fr.group_start[g + 1]; j++)
-                u = std::max(u, fr.ap[j].baseline);
-        unit[g] = u;
-    }
+    const std::vector<double> unit = detail::unitBaselines(fr, unit_k, pitch);
     return detail::arrayDepth(fr, cameras, pairs.size(), true, maps,
                               [&](double f, double pixel_size, double* depth, uint16_t* all) {
         m.check(fr.call(sva_array_depth_mixed, m.handle(), (const double*)unit.data(), f,
                         pixel_size, uniqueness, depth, all, nullptr, nullptr));
+    });
+}
+
+// ---- sub-pixel depth -----------------------------------
+
+namespace detail {
+inline void packMaps(const char* who, const std::vector<std::vector<uint16_t>>& maps,
+                     const std::vector<std::vector<float>>& subpix, size_t np, size_t n_baselines,
+                     std::vector<uint16_t>* d, std::vector<float>* s) {
+    if (maps.empty() || maps.size() != n_baselines || subpix.size() != maps.size())
+        throw Error(SVA_ERR_INVALID_ARG,
+                    std::string(who) + ": need one baseline and one sub-pixel map per map");
+    d->resize(np * maps.size());
+    s->resize(np * maps.size());
+    for (size_t i = 0; i < maps.size(); i++) {
+        if (maps[i].size() != np || subpix[i].size() != np)
+            throw Error(SVA_ERR_INVALID_ARG, std::string(who) + ": map size");
+        std::copy(maps[i].begin(), maps[i].end(), d->begin() + i * np);
+        std::copy(subpix[i].begin(), subpix[i].end(), s->begin() + i * np);
+    }
+}
+}  // namespace detail
+
+// fuseDepth on the f32 sub-pixel maps the matchers write next to the u16 ones
+// (computeDisparitySGM's subpix): depth is no longer quantised to whole
+// disparities.  A map counts where its u16 disparity is valid and its
+// sub-pixel disparity is > 0 (NaN, a rejected pixel, is not).
+inline std::vector<double> fuseDepthSub(Engine& eng, const std::vector<std::vector<uint16_t>>& maps,
+                                        const std::vector<std::vector<float>>& subpix, int W, int H,
+                                        const std::vector<double>& baselines, double f,
+                                        double pixel_size, uint16_t invalid = 0xFFFF,
+                                        std::vector<uint8_t>* n_valid = nullptr) {
+    const size_t np = (size_t)W * H;
+    std::vector<uint16_t> d;
+    std::vector<float> s;
+    detail::packMaps("fuseDepthSub", maps, subpix, np, baselines.size(), &d, &s);
+    std::vector<double> depth(np);
+    if (n_valid) n_valid->resize(np);
+    eng.check(sva_fuse_depth_sub(eng.handle(), d.data(), s.data(), (int)maps.size(), W, H,
+                                 baselines.data(), f, pixel_size, invalid, depth.data(),
+                                 n_valid ? n_valid->data() : nullptr));
+    return depth;
+}
+
+// Cost-aware fusion with the winner's depth from its
+// sub-pixel map: mode SVA_FUSE_MIN_COST (cost_second may be empty) or
+// SVA_FUSE_MAX_MARGIN.  winner (nullable): the chosen map's index, 0xFF if none.
+inline std::vector<double> fuseDepthConfSub(
+    Engine& eng, const std::vector<std::vector<uint16_t>>& maps,
+    const std::vector<std::vector<float>>& subpix,
+    const std::vector<std::vector<uint16_t>>& cost_min,
+    const std::vector<std::vector<uint16_t>>& cost_second, int W, int H,
+    const std::vector<double>& baselines, double f, double pixel_size, int mode,
+    uint16_t invalid = 0xFFFF, std::vector<uint8_t>* n_valid = nullptr,
+    std::vector<uint8_t>* winner = nullptr) {
+    const size_t np = (size_t)W * H;
+    std::vector<uint16_t> d, cmin, csec;
+    std::vector<float> s;
+    detail::packMaps("fuseDepthConfSub", maps, subpix, np, baselines.size(), &d, &s);
+    if (cost_min.size() != maps.size() || (!cost_second.empty() && cost_second.size() != maps.size()))
+        throw Error(SVA_ERR_INVALID_ARG, "fuseDepthConfSub: need one cost plane per map");
+    for (size_t i = 0; i < maps.size(); i++) {
+        if (cost_min[i].size() != np || (!cost_second.empty() && cost_second[i].size() != np))
+            throw Error(SVA_ERR_INVALID_ARG, "fuseDepthConfSub: cost plane size");
+        cmin.insert(cmin.end(), cost_min[i].begin(), cost_min[i].end());
+        if (!cost_second.empty()) csec.insert(csec.end(), cost_second[i].begin(), cost_second[i].end());
+    }
+    std::vector<double> depth(np);
+    if (n_valid) n_valid->resize(np);
+    if (winner) winner->resize(np);
+    eng.check(sva_fuse_depth_conf_sub(eng.handle(), d.data(), s.data(), cmin.data(),
+                                      csec.empty() ? nullptr : csec.data(), (int)maps.size(), W, H,
+                                      baselines.data(), f, pixel_size, invalid, mode, depth.data(),
+                                      n_valid ? n_valid->data() : nullptr,
+                                      winner ? winner->data() : nullptr));
+    return depth;
+}
+
+// Sub-pixel depth from one camera-array frame (sva_array_depth_sub): the frame
+// of computeArrayDepthConf (route SVA_ARRAY_PAIRS; mode as there),
+// computeArrayDepthMulti (SVA_ARRAY_GROUPS) or computeArrayDepthMixed
+// (SVA_ARRAY_GROUPS_MIXED, with its unit_k), every job matched with
+// subpixel = 1 and depth fused from the f32 maps.  On the group routes mode
+// must stay SVA_FUSE_MEDIAN.  maps (nullable) as for the entry of that route:
+// one per pair in `pairs` order, or one per reference camera.
+inline std::vector<std::vector<double>> computeArrayDepthSub(
+    MultiEngine& m, const std::vector<ImageView>& images, const std::vector<Camera>& cameras,
+    const std::vector<std::array<int, 2>>& pairs, const sva_sgm_params& p,
+    int route = SVA_ARRAY_PAIRS, int uniqueness = 0, int mode = SVA_FUSE_MEDIAN, int unit_k = 0,
+    double pitch = 0.05, std::vector<std::vector<uint16_t>>* maps = nullptr) {
+    if (unit_k < 0) throw Error(SVA_ERR_INVALID_ARG, "computeArrayDepthSub: unit_k must be >= 0");
+    const detail::ArrayFrame fr = detail::arrayFrame(images, cameras, pairs, p, pitch,
+                                                     "computeArrayDepthSub");
+    std::vector<double> unit;
+    if (route == SVA_ARRAY_GROUPS_MIXED) unit = detail::unitBaselines(fr, unit_k, pitch);
+    return detail::arrayDepth(fr, cameras, pairs.size(), route != SVA_ARRAY_PAIRS, maps,
+                              [&](double f, double pixel_size, double* depth, uint16_t* all) {
+        m.check(fr.call(sva_array_depth_sub, m.handle(), route,
+                        unit.empty() ? (const double*)nullptr : (const double*)unit.data(), f,
+                        pixel_size, uniqueness, mode, depth, (uint8_t*)nullptr, (uint8_t*)nullptr,
+                        (float*)nullptr, all, (uint16_t*)nullptr, (uint16_t*)nullptr));
     });
 }
 

@@ -71,10 +71,15 @@ EXPORTED = [
     "sva_disparity_sgm_multi_d", "sva_array_depth_mb", "sva_cost_mixed_d",
     "sva_cost_fuse_mixed_d", "sva_disparity_sgm_mixed", "sva_disparity_sgm_mixed_d",
     "sva_array_depth_mixed", "sva_frame_layout_of", "sva_paths_frame_d", "sva_wta_frame_d",
+    "sva_fuse_depth_sub", "sva_fuse_depth_sub_d", "sva_fuse_depth_conf_sub",
+    "sva_fuse_depth_conf_sub_d", "sva_array_depth_sub",
 ]
 SVA_FUSE_MIN_COST = 0
 SVA_FUSE_MAX_MARGIN = 1
-SVA_FUSE_MEDIAN = 2      # sva_array_depth_conf only
+SVA_FUSE_MEDIAN = 2      # sva_array_depth_conf and sva_array_depth_sub only
+SVA_ARRAY_PAIRS = 0      # sva_array_depth_sub's routes
+SVA_ARRAY_GROUPS = 1
+SVA_ARRAY_GROUPS_MIXED = 2
 SVA_MULTI_GATHER_RCCL = 0
 SVA_MULTI_GATHER_PEER = 1
 SVA_MULTI_GATHER_ALL = 2
@@ -273,6 +278,16 @@ def _load() -> ct.CDLL:
                                             i32, sz, P(SgmParams), i32, vp, vp, vp, vp]),
         "sva_array_depth_mixed": (i32, [vp, P(vp), i32, i32, i32, sz, P(ArrayPair), i32, P(i32),
                                         i32, P(dbl), dbl, dbl, i32, vp, vp, vp, vp]),
+        "sva_fuse_depth_sub_d": (i32, [vp, vp, vp, i32, i32, i32, P(dbl), dbl, dbl, ct.c_uint16, vp,
+                                       vp]),
+        "sva_fuse_depth_sub": (i32, [vp, vp, vp, i32, i32, i32, P(dbl), dbl, dbl, ct.c_uint16, vp,
+                                     vp]),
+        "sva_fuse_depth_conf_sub_d": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, P(dbl), dbl, dbl,
+                                            ct.c_uint16, i32, vp, vp, vp]),
+        "sva_fuse_depth_conf_sub": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, P(dbl), dbl, dbl,
+                                          ct.c_uint16, i32, vp, vp, vp]),
+        "sva_array_depth_sub": (i32, [vp, P(vp), i32, i32, i32, sz, P(ArrayPair), i32, P(i32), i32,
+                                      i32, P(dbl), dbl, dbl, i32, i32, vp, vp, vp, vp, vp, vp, vp]),
         "sva_resize_linear_f64_d": (i32, [vp, vp, i32, i32, vp, i32, i32]),
         "sva_resize_linear_f64": (i32, [vp, vp, i32, i32, vp, i32, i32]),
         "sva_ref_error_d": (i32, [vp, vp, i32, i32, vp, i32, i32, ct.c_double, vp]),
@@ -842,6 +857,57 @@ class Context:
                                             invalid, int(mode), _ptr(depth), _ptr(n_valid),
                                             _ptr(winner)))
 
+    def fuse_depth_sub(self, disps: np.ndarray, subpix, baselines, f, pixel_size,
+                       invalid=0xFFFF, want_n_valid=True):
+        """(depth, n_valid or None): sva_fuse_depth_sub, the median of the depths
+        of the f32 sub-pixel maps (a map counts where its u16 disparity is valid
+        and subpix > 0).  subpix None: the NULL pointer the call refuses."""
+        d = np.ascontiguousarray(disps, dtype=np.uint16)
+        s = None if subpix is None else np.ascontiguousarray(subpix, dtype=np.float32)
+        N, H, W = d.shape
+        assert s is None or s.shape == d.shape
+        b = (ct.c_double * max(1, N))(*[float(v) for v in baselines])
+        out = np.zeros((H, W), np.float64)
+        nv = np.zeros((H, W), np.uint8) if want_n_valid else None
+        self._chk(lib.sva_fuse_depth_sub(self.h, _ptr(d), _ptr(s), N, W, H, b, f, pixel_size,
+                                         invalid, _ptr(out), _ptr(nv)))
+        return out, nv
+
+    def fuse_depth_sub_d(self, disps, subpix, n_maps, W, H, baselines, f, pixel_size, invalid,
+                         depth, n_valid=None):
+        b = (ct.c_double * max(1, n_maps))(*[float(v) for v in baselines])
+        self._chk(lib.sva_fuse_depth_sub_d(self.h, _ptr(disps), _ptr(subpix), n_maps, W, H, b, f,
+                                           pixel_size, invalid, _ptr(depth), _ptr(n_valid)))
+
+    def fuse_depth_conf_sub(self, disps: np.ndarray, subpix, cost_min: np.ndarray, cost_second,
+                            baselines, f, pixel_size, invalid=0xFFFF, mode=SVA_FUSE_MIN_COST,
+                            want_n_valid=True, want_winner=True):
+        """(depth, n_valid, winner): sva_fuse_depth_conf_sub, fuse_depth_conf with
+        the winner's depth taken from its f32 sub-pixel map."""
+        d = np.ascontiguousarray(disps, dtype=np.uint16)
+        s = None if subpix is None else np.ascontiguousarray(subpix, dtype=np.float32)
+        cm = np.ascontiguousarray(cost_min, dtype=np.uint16)
+        cs = None if cost_second is None else np.ascontiguousarray(cost_second, dtype=np.uint16)
+        N, H, W = d.shape
+        assert cm.shape == d.shape and (cs is None or cs.shape == d.shape)
+        assert s is None or s.shape == d.shape
+        b = (ct.c_double * max(1, N))(*[float(v) for v in baselines])
+        out = np.zeros((H, W), np.float64)
+        nv = np.zeros((H, W), np.uint8) if want_n_valid else None
+        win = np.zeros((H, W), np.uint8) if want_winner else None
+        self._chk(lib.sva_fuse_depth_conf_sub(self.h, _ptr(d), _ptr(s), _ptr(cm), _ptr(cs), N, W, H,
+                                              b, f, pixel_size, invalid, int(mode), _ptr(out),
+                                              _ptr(nv), _ptr(win)))
+        return out, nv, win
+
+    def fuse_depth_conf_sub_d(self, disps, subpix, cost_min, cost_second, n_maps, W, H, baselines,
+                              f, pixel_size, invalid, mode, depth, n_valid=None, winner=None):
+        b = (ct.c_double * max(1, n_maps))(*[float(v) for v in baselines])
+        self._chk(lib.sva_fuse_depth_conf_sub_d(self.h, _ptr(disps), _ptr(subpix), _ptr(cost_min),
+                                                _ptr(cost_second), n_maps, W, H, b, f, pixel_size,
+                                                invalid, int(mode), _ptr(depth), _ptr(n_valid),
+                                                _ptr(winner)))
+
     def disparity_to_depth(self, disp: np.ndarray, cam_distance, f, pixel_size):
         d = np.ascontiguousarray(disp, dtype=np.uint8)
         out = np.zeros(d.shape, np.float64)
@@ -997,6 +1063,32 @@ class Multi:
         ub = (ct.c_double * fr.G)(*[float(v) for v in unit_baseline])
         return self._array_depth_groups(lib.sva_array_depth_mixed, fr, (ub, f, pixel_size),
                                         uniqueness, want_maps, want_costs)
+
+    def array_depth_sub(self, images, pairs, group_start, f, pixel_size, route=SVA_ARRAY_PAIRS,
+                        unit_baseline=None, uniqueness=0, mode=SVA_FUSE_MEDIAN, want_sub=False,
+                        want_maps=False, want_costs=False):
+        """sva_array_depth_sub: the frame of array_depth_conf (SVA_ARRAY_PAIRS),
+        array_depth_mb (SVA_ARRAY_GROUPS) or array_depth_mixed
+        (SVA_ARRAY_GROUPS_MIXED, with unit_baseline) with the depth fused from the
+        jobs' f32 sub-pixel maps.  Returns (depth [G,H,W] f64, n_valid, winner,
+        subpix [J,H,W] f32, maps, cost_min, cost_second [J,H,W] u16), J = P jobs
+        on the pair route and G on the group routes; n_valid is None on the group
+        routes, winner there and with MEDIAN, the last four unless asked for."""
+        fr = _ArrayFrame(images, pairs, group_start)
+        pair = route == SVA_ARRAY_PAIRS
+        J = fr.P if pair else fr.G
+        ub = None if unit_baseline is None else \
+            (ct.c_double * max(1, len(unit_baseline)))(*[float(v) for v in unit_baseline])
+        depth = fr.planes(fr.G, np.float64)
+        nv = fr.planes(fr.G, np.uint8, pair)
+        win = fr.planes(fr.G, np.uint8, pair and mode != SVA_FUSE_MEDIAN)
+        sub = fr.planes(J, np.float32, want_sub)
+        maps = fr.planes(J, np.uint16, want_maps)
+        cmin, csec = fr.planes(J, np.uint16, want_costs), fr.planes(J, np.uint16, want_costs)
+        self._chk(lib.sva_array_depth_sub(self.h, *fr.head, int(route), ub, f, pixel_size,
+                                          int(uniqueness), int(mode), _ptr(depth), _ptr(nv),
+                                          _ptr(win), _ptr(sub), _ptr(maps), _ptr(cmin), _ptr(csec)))
+        return depth, nv, win, sub, maps, cmin, csec
 
     def array_depth(self, images, pairs, group_start, f, pixel_size, want_maps=False):
         """images: list of HxW u8 numpy views; pairs: list of (ref, other,

@@ -1,7 +1,8 @@
 // array_args.h -- the arguments of one camera-array frame (sva_array_depth,
-// _conf, _mb and _mixed) and their validation, shared by
-// multi.cpp and a host test program (tests/test_array_args_cpu.py compiles this
-// header with a C++ compiler under the sanitizers).  Plain C++: no HIP header.
+// _conf, _mb, _mixed and _sub) and their validation, shared by
+// multi.cpp and the host test programs (tests/test_array_args_cpu.py and
+// tests/test_array_sub_args_cpu.py compile this header with a C++ compiler
+// under the sanitizers).  Plain C++: no HIP header.
 #pragma once
 
 #include <algorithm>
@@ -20,7 +21,18 @@ namespace sva {
 // What a job of the frame is: a pair (every pair matched on its own, each
 // group's maps fused into depth), or a reference camera's whole group fused at
 // the cost level, of equal or of mixed baselines (§2.2d).
-enum class ArrayRoute { Pairs, Groups, GroupsMixed };
+// Unknown: a route number sva_array_depth_sub does not know; always refused.
+enum class ArrayRoute { Pairs, Groups, GroupsMixed, Unknown };
+
+// sva_array_depth_sub's SVA_ARRAY_* route number as a route.
+inline ArrayRoute array_route_of(int route) {
+    switch (route) {
+        case SVA_ARRAY_PAIRS: return ArrayRoute::Pairs;
+        case SVA_ARRAY_GROUPS: return ArrayRoute::Groups;
+        case SVA_ARRAY_GROUPS_MIXED: return ArrayRoute::GroupsMixed;
+        default: return ArrayRoute::Unknown;
+    }
+}
 
 struct ArrayArgs {
     const uint8_t* const* images = nullptr;   // n_images host views [H][pitch]
@@ -37,10 +49,14 @@ struct ArrayArgs {
     bool conf = false;
     int uniqueness = 0, mode = SVA_FUSE_MEDIAN;
     const double* unit_baseline = nullptr;    // per group; GroupsMixed only
+    // sub (sva_array_depth_sub): every job also writes its f32
+    // sub-pixel map, and depth is fused from those maps
+    bool sub = false;
     // host outputs, all but depth nullable: per group, then per job
     double* depth = nullptr;
     uint8_t *n_valid = nullptr, *winner = nullptr;
     uint16_t *maps = nullptr, *cost_min = nullptr, *cost_second = nullptr;
+    float* subpix = nullptr;                  // per job; sub only
 };
 
 inline int check_params(const sva_sgm_params& p) {
@@ -77,6 +93,7 @@ inline int check_array_args(const ArrayArgs& a, std::string& msg, std::vector<in
         return code;
     };
     const bool group = a.route != ArrayRoute::Pairs, mixed = a.route == ArrayRoute::GroupsMixed;
+    if (a.route == ArrayRoute::Unknown) return fail(SVA_ERR_INVALID_ARG, "unknown route");
     if (a.conf) {
         if (a.mode != SVA_FUSE_MIN_COST && a.mode != SVA_FUSE_MAX_MARGIN &&
             a.mode != SVA_FUSE_MEDIAN)
@@ -85,6 +102,15 @@ inline int check_array_args(const ArrayArgs& a, std::string& msg, std::vector<in
             return fail(SVA_ERR_INVALID_ARG, "uniqueness must be 0..100");
         if (a.winner && a.mode == SVA_FUSE_MEDIAN)
             return fail(SVA_ERR_INVALID_ARG, "the median has no winner map");
+    }
+    if (a.sub) {
+        // the entry takes every route's arguments: those of another route are refused
+        if (group && a.mode != SVA_FUSE_MEDIAN)
+            return fail(SVA_ERR_INVALID_ARG, "the group routes fuse one map: SVA_FUSE_MEDIAN only");
+        if (group && (a.n_valid || a.winner))
+            return fail(SVA_ERR_INVALID_ARG, "the group routes have no n_valid or winner map");
+        if (!mixed && a.unit_baseline)
+            return fail(SVA_ERR_INVALID_ARG, "unit_baseline is for SVA_ARRAY_GROUPS_MIXED only");
     }
     if (mixed && !a.unit_baseline) return fail(SVA_ERR_INVALID_ARG, "null unit_baseline");
     if (!a.images || a.n_images <= 0 || !a.pairs || a.n_pairs <= 0 || !a.group_start ||

@@ -12,7 +12,7 @@
 // through the public per-context entry points (sva_disparity_sgm_d,
 // sva_fuse_depth_d, and sva_disparity_sgm_conf_d / sva_fuse_depth_conf_d for
 // the confidence forms, whose cost planes are gathered like the maps); there
-// is no CPU path.  The four sva_array_depth* entry points fill one ArrayArgs
+// is no CPU path.  The five sva_array_depth* entry points fill one ArrayArgs
 // (array_args.h: the arguments and their checks, in one order) and run one
 // array_frame(): its jobs are pairs, or -- sva_array_depth_mb -- GROUPS (one
 // sva_disparity_sgm_multi_d per reference camera, DESIGN.md §2.2c;
@@ -118,6 +118,7 @@ struct Multi {
     std::vector<DevBuf> images;        // per device: uploaded views (sva_array_depth)
     DevBuf maps0, depth0, nvalid0;     // device 0 (sva_array_depth)
     DevBuf conf0, winner0;             // device 0: cost planes, winners (sva_array_depth_conf)
+    DevBuf sub0;                       // device 0: f32 sub-pixel maps (sva_array_depth_sub)
     PinnedBuf stage_in, stage_out;
     Rccl rccl;
     std::vector<ncclComm_t> comms;
@@ -294,9 +295,11 @@ int run_jobs(Multi* m, const Plan& P, const std::vector<std::vector<hipEvent_t>>
     std::vector<char> remote(n, 0);
     for (int j = 0; j < n; j++) remote[j] = P.dev[j] != 0 || m->gather_all;
     // a slot: the map, then the sub-pixel map, cost_min and cost_second where asked for
-    const size_t off_sub = np * 2, off_min = off_sub + (sub ? np * 4 : 0);
-    const size_t off_sec = off_min + (cmin ? np * 2 : 0);
-    const size_t per = off_sec + (csec ? np * 2 : 0);
+    // (each plane on a 16-byte boundary, so that an odd W * H keeps the f32 map aligned)
+    auto up16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
+    const size_t off_sub = up16(np * 2), off_min = off_sub + (sub ? up16(np * 4) : 0);
+    const size_t off_sec = off_min + (cmin ? up16(np * 2) : 0);
+    const size_t per = off_sec + (csec ? up16(np * 2) : 0);
     for (int d = 0; d < m->nd(); d++) {
         MHIP(m, hipSetDevice(m->devices[d]), "hipSetDevice");
         for (int s = 0; s < m->spd; s++) {
@@ -638,6 +641,7 @@ int sva_multi_destroy(void* mp) {
         m->nvalid0.release();
         m->conf0.release();
         m->winner0.release();
+        m->sub0.release();
     }
     m->stage_in.release();
     m->stage_out.release();
@@ -809,13 +813,15 @@ struct Download {
     }
 };
 
-// One camera-array frame: sva_array_depth, _conf, _mb and _mixed (array_args.h
+// One camera-array frame: sva_array_depth, _conf, _mb, _mixed and _sub (array_args.h
 // has their arguments and checks).  A job is a pair (ArrayRoute::Pairs: every
 // pair through sva_disparity_sgm_d or, with conf, sva_disparity_sgm_conf_d; a
 // group's maps are fused by `mode`) or a GROUP (group g's
 // pairs go through one sva_disparity_sgm_multi_d on device g mod n_devices,
 // and its one map becomes depth at the group's baseline; GroupsMixed, §2.2d:
-// sva_disparity_sgm_mixed_d, and the depth scale is the unit baseline).
+// sva_disparity_sgm_mixed_d, and the depth scale is the unit baseline).  With
+// a.sub (sva_array_depth_sub, §2.6c) every job also writes its f32 sub-pixel
+// map, gathered into sub0 like the u16 one, and depth is fused from those.
 int array_frame(void* mp, const ArrayArgs& a) {
     Multi* m = as_multi(mp);
     if (!m) return SVA_ERR_INVALID_ARG;
@@ -855,7 +861,9 @@ int array_frame(void* mp, const ArrayArgs& a) {
     if (want_min || want_sec)
         MHIP(m, m->conf0.ensure(plane * ((want_min ? 1 : 0) + (want_sec ? 1 : 0))), "cost planes");
     if (a.winner) MHIP(m, m->winner0.ensure(np * n_groups), "winner workspace");
+    if (a.sub) MHIP(m, m->sub0.ensure(plane * 2), "sub-pixel workspace");
     uint16_t* maps0 = (uint16_t*)m->maps0.ptr;
+    float* sub0 = a.sub ? (float*)m->sub0.ptr : nullptr;
     ConfPlanes cp;
     cp.uniqueness = a.uniqueness;
     cp.cost_min = want_min ? (uint16_t*)m->conf0.ptr : nullptr;
@@ -878,27 +886,29 @@ int array_frame(void* mp, const ArrayArgs& a) {
             waits[k].push_back(up_ev[d][pairs[j].other]);
         }
         prm[k] = pairs[j0].params;
-        prm[k].subpixel = 0;
+        prm[k].subpixel = a.sub ? 1 : 0;
     }
+    // os: the job's plane of sub0, null for every entry but sva_array_depth_sub
     int st = run_jobs(
-        m, P, waits, W, H, maps0, nullptr, std::vector<char>(n_jobs, 0), a.conf ? &cp : nullptr,
-        [&](int k, void* cx, uint16_t* od, float*, uint16_t* omin, uint16_t* osec) {
+        m, P, waits, W, H, maps0, sub0, std::vector<char>(n_jobs, a.sub ? 1 : 0),
+        a.conf ? &cp : nullptr,
+        [&](int k, void* cx, uint16_t* od, float* os, uint16_t* omin, uint16_t* osec) {
             const int n = (int)others[k].size();
             switch (a.route) {
                 case ArrayRoute::GroupsMixed:
                     return sva_disparity_sgm_mixed_d(cx, ref[k], others[k].data(), steps[k].data(),
                                                      &ratio[2 * (size_t)first[k]], n, W, H, W,
-                                                     &prm[k], a.uniqueness, od, nullptr, omin, osec);
+                                                     &prm[k], a.uniqueness, od, os, omin, osec);
                 case ArrayRoute::Groups:
                     return sva_disparity_sgm_multi_d(cx, ref[k], others[k].data(), steps[k].data(),
-                                                     n, W, H, W, &prm[k], a.uniqueness, od, nullptr,
+                                                     n, W, H, W, &prm[k], a.uniqueness, od, os,
                                                      omin, osec);
                 default:
                     return a.conf ? sva_disparity_sgm_conf_d(cx, ref[k], others[k][0], W, H, W,
-                                                             &prm[k], a.uniqueness, od, nullptr,
-                                                             omin, osec)
+                                                             &prm[k], a.uniqueness, od, os, omin,
+                                                             osec)
                                   : sva_disparity_sgm_d(cx, ref[k], others[k][0], W, H, W, &prm[k],
-                                                        od, nullptr);
+                                                        od, os);
             }
         },
         group ? "group" : "pair");
@@ -918,6 +928,7 @@ int array_frame(void* mp, const ArrayArgs& a) {
         if (win0) dl.add(g, win0 + o, a.winner + o, np);
     }
     dl.add(n_groups, maps0, a.maps, plane);
+    dl.add(n_groups, sub0, a.subpix, plane * 2);
     dl.add(n_groups, cp.cost_min, a.cost_min, plane);
     dl.add(n_groups, cp.cost_second, a.cost_second, plane);
     MHIP(m, m->stage_out.ensure(dl.total), "pinned staging");
@@ -929,7 +940,19 @@ int array_frame(void* mp, const ArrayArgs& a) {
         const int n_maps = group ? 1 : gs[g + 1] - j0;
         const double* base =
             a.route == ArrayRoute::GroupsMixed ? &a.unit_baseline[g] : &bases[j0];
-        if (a.conf && a.mode != SVA_FUSE_MEDIAN)
+        const bool by_cost = a.conf && a.mode != SVA_FUSE_MEDIAN;
+        if (a.sub && by_cost)
+            st = sva_fuse_depth_conf_sub_d(m->ctx[0], maps0 + o_maps, sub0 + o_maps,
+                                           cp.cost_min + o_maps,
+                                           cp.cost_second ? cp.cost_second + o_maps : nullptr,
+                                           n_maps, W, H, base, a.f, a.pixel_size,
+                                           pairs[j0].params.invalid, a.mode, depth0 + o,
+                                           nv0 ? nv0 + o : nullptr, win0 ? win0 + o : nullptr);
+        else if (a.sub)
+            st = sva_fuse_depth_sub_d(m->ctx[0], maps0 + o_maps, sub0 + o_maps, n_maps, W, H, base,
+                                      a.f, a.pixel_size, pairs[j0].params.invalid, depth0 + o,
+                                      nv0 ? nv0 + o : nullptr);
+        else if (by_cost)
             st = sva_fuse_depth_conf_d(m->ctx[0], maps0 + o_maps, cp.cost_min + o_maps,
                                        cp.cost_second ? cp.cost_second + o_maps : nullptr, n_maps,
                                        W, H, base, a.f, a.pixel_size, pairs[j0].params.invalid,
@@ -946,7 +969,7 @@ int array_frame(void* mp, const ArrayArgs& a) {
     return dl.finish(m);
 }
 
-// What the four entry points share; as it stands, sva_array_depth's: the pair
+// What the five entry points share; as it stands, sva_array_depth's: the pair
 // route, plain matching, median fusion.
 ArrayArgs frame_args(const uint8_t* const* images, int n_images, int W, int H, size_t pitch,
                      const sva_array_pair* pairs, int n_pairs, const int32_t* group_start,
@@ -1037,6 +1060,25 @@ int sva_array_depth_mixed(void* mp, const uint8_t* const* images, int n_images, 
     a.route = ArrayRoute::GroupsMixed;
     a.conf = true;
     a.unit_baseline = unit_baseline;
+    return array_frame(mp, a);
+}
+
+int sva_array_depth_sub(void* mp, const uint8_t* const* images, int n_images, int W, int H,
+                        size_t pitch, const sva_array_pair* pairs, int n_pairs,
+                        const int32_t* group_start, int n_groups, int route,
+                        const double* unit_baseline, double f, double pixel_size, int uniqueness,
+                        int mode, double* depth, uint8_t* n_valid, uint8_t* winner, float* subpix,
+                        uint16_t* maps, uint16_t* cost_min, uint16_t* cost_second) {
+    ArrayArgs a = frame_args(images, n_images, W, H, pitch, pairs, n_pairs, group_start, n_groups,
+                             f, pixel_size, uniqueness, depth, maps, cost_min, cost_second);
+    a.route = array_route_of(route);
+    a.conf = true;
+    a.sub = true;
+    a.mode = mode;
+    a.unit_baseline = unit_baseline;
+    a.n_valid = n_valid;
+    a.winner = winner;
+    a.subpix = subpix;
     return array_frame(mp, a);
 }
 

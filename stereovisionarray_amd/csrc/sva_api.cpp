@@ -1667,40 +1667,60 @@ int check_fuse_conf(Ctx* c, const uint16_t* disps, const uint16_t* cost_min,
 }
 
 // Both fusions on device planes: the median (mode < 0; cost planes and winner
-// unused) and the cost-aware ones.
-int run_fuse(Ctx* c, const uint16_t* disps, const uint16_t* cost_min, const uint16_t* cost_second,
-             int n_maps, size_t np, const double* baselines, double f, double pixel_size,
-             uint16_t invalid, int mode, double* depth, uint8_t* n_valid, uint8_t* winner) {
+// unused) and the cost-aware ones.  subpix non-null: the sub-pixel forms of
+// §2.6c, which read it next to disps.
+int run_fuse(Ctx* c, const uint16_t* disps, const float* subpix, const uint16_t* cost_min,
+             const uint16_t* cost_second, int n_maps, size_t np, const double* baselines, double f,
+             double pixel_size, uint16_t invalid, int mode, double* depth, uint8_t* n_valid,
+             uint8_t* winner) {
     double num[32];
     for (int i = 0; i < n_maps; i++) num[i] = baselines[i] * f;
-    SVA_HIP(c, mode < 0 ? launch_fuse_depth(*c, disps, n_maps, np, num, pixel_size, invalid, depth,
-                                            n_valid)
-                        : launch_fuse_depth_conf(*c, disps, cost_min, cost_second, n_maps, np, num,
-                                                 pixel_size, invalid, mode, depth, n_valid, winner),
-            "fuse launch");
+    hipError_t e;
+    if (subpix)
+        e = mode < 0 ? launch_fuse_depth_sub(*c, disps, subpix, n_maps, np, num, pixel_size, invalid,
+                                             depth, n_valid)
+                     : launch_fuse_depth_conf_sub(*c, disps, subpix, cost_min, cost_second, n_maps,
+                                                  np, num, pixel_size, invalid, mode, depth,
+                                                  n_valid, winner);
+    else
+        e = mode < 0 ? launch_fuse_depth(*c, disps, n_maps, np, num, pixel_size, invalid, depth,
+                                         n_valid)
+                     : launch_fuse_depth_conf(*c, disps, cost_min, cost_second, n_maps, np, num,
+                                              pixel_size, invalid, mode, depth, n_valid, winner);
+    SVA_HIP(c, e, "fuse launch");
     return SVA_OK;
 }
 
 // The host-buffer forms of both fusions, after their checks (median: mode < 0).
-int fuse_host(Ctx* c, const uint16_t* disps, const uint16_t* cost_min, const uint16_t* cost_second,
-              int n_maps, int W, int H, const double* baselines, double f, double pixel_size,
-              uint16_t invalid, int mode, double* depth, uint8_t* n_valid, uint8_t* winner) {
+// The f32 planes of the sub-pixel forms stage through in_mask, the fourth
+// input buffer.
+int fuse_host(Ctx* c, const uint16_t* disps, const float* subpix, const uint16_t* cost_min,
+              const uint16_t* cost_second, int n_maps, int W, int H, const double* baselines,
+              double f, double pixel_size, uint16_t invalid, int mode, double* depth,
+              uint8_t* n_valid, uint8_t* winner) {
     const size_t np = (size_t)W * H, in_bytes = np * 2 * (size_t)n_maps;
     Staging g{c};
     const uint16_t* dd = g.up<uint16_t>(c->in_a, disps, in_bytes);
+    const float* ds = subpix ? g.up<float>(c->in_mask, subpix, in_bytes * 2) : nullptr;
     const uint16_t* dmin = cost_min ? g.up<uint16_t>(c->in_b, cost_min, in_bytes) : nullptr;
     const uint16_t* dsec = cost_second ? g.up<uint16_t>(c->in_c, cost_second, in_bytes) : nullptr;
     double* dz = g.out<double>(c->out_a, np * 8);
     uint8_t* dn = g.out<uint8_t>(c->out_b, np);
     uint8_t* dw = mode < 0 ? nullptr : g.out<uint8_t>(c->out_c, np);
     if (g.st) return g.st;
-    if (int s = run_fuse(c, dd, dmin, dsec, n_maps, np, baselines, f, pixel_size, invalid, mode, dz,
-                         dn, dw))
+    if (int s = run_fuse(c, dd, ds, dmin, dsec, n_maps, np, baselines, f, pixel_size, invalid, mode,
+                         dz, dn, dw))
         return s;
     g.down(depth, dz, np * 8);
     g.down(n_valid, dn, np);
     g.down(winner, dw, np);
     return g.sync();
+}
+
+// The sub-pixel forms' own rule, after those of the u16 forms.
+int check_subpix(Ctx* c, const float* subpix) {
+    if (!subpix) return fail(c, SVA_ERR_INVALID_ARG, "null subpix");
+    return SVA_OK;
 }
 }  // namespace
 
@@ -1710,8 +1730,8 @@ int sva_fuse_depth_d(void* ctx, const uint16_t* disps, int n_maps, int W, int H,
     Ctx* c = as_ctx(ctx);
     SVA_CHECK_CTX(c);
     if (int s = check_fuse(c, disps, n_maps, W, H, baselines, depth)) return s;
-    return run_fuse(c, disps, nullptr, nullptr, n_maps, (size_t)W * H, baselines, f, pixel_size,
-                    invalid, -1, depth, n_valid, nullptr);
+    return run_fuse(c, disps, nullptr, nullptr, nullptr, n_maps, (size_t)W * H, baselines, f,
+                    pixel_size, invalid, -1, depth, n_valid, nullptr);
 }
 
 int sva_fuse_depth(void* ctx, const uint16_t* disps, int n_maps, int W, int H,
@@ -1720,8 +1740,8 @@ int sva_fuse_depth(void* ctx, const uint16_t* disps, int n_maps, int W, int H,
     Ctx* c = as_ctx(ctx);
     SVA_CHECK_CTX(c);
     if (int s = check_fuse(c, disps, n_maps, W, H, baselines, depth)) return s;
-    return fuse_host(c, disps, nullptr, nullptr, n_maps, W, H, baselines, f, pixel_size, invalid,
-                     -1, depth, n_valid, nullptr);
+    return fuse_host(c, disps, nullptr, nullptr, nullptr, n_maps, W, H, baselines, f, pixel_size,
+                     invalid, -1, depth, n_valid, nullptr);
 }
 
 int sva_fuse_depth_conf_d(void* ctx, const uint16_t* disps, const uint16_t* cost_min,
@@ -1733,7 +1753,7 @@ int sva_fuse_depth_conf_d(void* ctx, const uint16_t* disps, const uint16_t* cost
     if (int s = check_fuse_conf(c, disps, cost_min, cost_second, n_maps, W, H, baselines, mode,
                                 depth))
         return s;
-    return run_fuse(c, disps, cost_min, cost_second, n_maps, (size_t)W * H, baselines, f,
+    return run_fuse(c, disps, nullptr, cost_min, cost_second, n_maps, (size_t)W * H, baselines, f,
                     pixel_size, invalid, mode, depth, n_valid, winner);
 }
 
@@ -1746,8 +1766,61 @@ int sva_fuse_depth_conf(void* ctx, const uint16_t* disps, const uint16_t* cost_m
     if (int s = check_fuse_conf(c, disps, cost_min, cost_second, n_maps, W, H, baselines, mode,
                                 depth))
         return s;
-    return fuse_host(c, disps, cost_min, cost_second, n_maps, W, H, baselines, f, pixel_size,
-                     invalid, mode, depth, n_valid, winner);
+    return fuse_host(c, disps, nullptr, cost_min, cost_second, n_maps, W, H, baselines, f,
+                     pixel_size, invalid, mode, depth, n_valid, winner);
+}
+
+// Sub-pixel fusion: the four calls above on the f32 maps.
+int sva_fuse_depth_sub_d(void* ctx, const uint16_t* disps, const float* subpix, int n_maps, int W,
+                         int H, const double* baselines, double f, double pixel_size,
+                         uint16_t invalid, double* depth, uint8_t* n_valid) {
+    Ctx* c = as_ctx(ctx);
+    SVA_CHECK_CTX(c);
+    if (int s = check_fuse(c, disps, n_maps, W, H, baselines, depth)) return s;
+    if (int s = check_subpix(c, subpix)) return s;
+    return run_fuse(c, disps, subpix, nullptr, nullptr, n_maps, (size_t)W * H, baselines, f,
+                    pixel_size, invalid, -1, depth, n_valid, nullptr);
+}
+
+int sva_fuse_depth_sub(void* ctx, const uint16_t* disps, const float* subpix, int n_maps, int W,
+                       int H, const double* baselines, double f, double pixel_size,
+                       uint16_t invalid, double* depth, uint8_t* n_valid) {
+    Ctx* c = as_ctx(ctx);
+    SVA_CHECK_CTX(c);
+    if (int s = check_fuse(c, disps, n_maps, W, H, baselines, depth)) return s;
+    if (int s = check_subpix(c, subpix)) return s;
+    return fuse_host(c, disps, subpix, nullptr, nullptr, n_maps, W, H, baselines, f, pixel_size,
+                     invalid, -1, depth, n_valid, nullptr);
+}
+
+int sva_fuse_depth_conf_sub_d(void* ctx, const uint16_t* disps, const float* subpix,
+                              const uint16_t* cost_min, const uint16_t* cost_second, int n_maps,
+                              int W, int H, const double* baselines, double f, double pixel_size,
+                              uint16_t invalid, int mode, double* depth, uint8_t* n_valid,
+                              uint8_t* winner) {
+    Ctx* c = as_ctx(ctx);
+    SVA_CHECK_CTX(c);
+    if (int s = check_fuse_conf(c, disps, cost_min, cost_second, n_maps, W, H, baselines, mode,
+                                depth))
+        return s;
+    if (int s = check_subpix(c, subpix)) return s;
+    return run_fuse(c, disps, subpix, cost_min, cost_second, n_maps, (size_t)W * H, baselines, f,
+                    pixel_size, invalid, mode, depth, n_valid, winner);
+}
+
+int sva_fuse_depth_conf_sub(void* ctx, const uint16_t* disps, const float* subpix,
+                            const uint16_t* cost_min, const uint16_t* cost_second, int n_maps,
+                            int W, int H, const double* baselines, double f, double pixel_size,
+                            uint16_t invalid, int mode, double* depth, uint8_t* n_valid,
+                            uint8_t* winner) {
+    Ctx* c = as_ctx(ctx);
+    SVA_CHECK_CTX(c);
+    if (int s = check_fuse_conf(c, disps, cost_min, cost_second, n_maps, W, H, baselines, mode,
+                                depth))
+        return s;
+    if (int s = check_subpix(c, subpix)) return s;
+    return fuse_host(c, disps, subpix, cost_min, cost_second, n_maps, W, H, baselines, f,
+                     pixel_size, invalid, mode, depth, n_valid, winner);
 }
 
 // ------------------------------------------ refinement / 3-D --

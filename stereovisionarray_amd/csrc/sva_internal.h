@@ -238,6 +238,16 @@ hipError_t launch_fuse_depth_conf(Ctx& c, const uint16_t* disps, const uint16_t*
                                   const uint16_t* cost_second, int n_maps, size_t np,
                                   const double* num, double pixel_size, uint16_t invalid, int mode,
                                   double* depth, uint8_t* n_valid, uint8_t* winner);
+// Both fusions on the f32 sub-pixel maps: subpix [n_maps][np],
+// a map valid where its u16 disparity is and subpix > 0.
+hipError_t launch_fuse_depth_sub(Ctx& c, const uint16_t* disps, const float* subpix, int n_maps,
+                                 size_t np, const double* num, double pixel_size, uint16_t invalid,
+                                 double* depth, uint8_t* n_valid);
+hipError_t launch_fuse_depth_conf_sub(Ctx& c, const uint16_t* disps, const float* subpix,
+                                      const uint16_t* cost_min, const uint16_t* cost_second,
+                                      int n_maps, size_t np, const double* num, double pixel_size,
+                                      uint16_t invalid, int mode, double* depth, uint8_t* n_valid,
+                                      uint8_t* winner);
 // refpath.hip
 hipError_t launch_ref_endpoints(Ctx& c, int W, int H, const sva_camera& cref,
                                 const sva_camera& coth, int k, double t_near, double t_far,
