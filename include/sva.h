@@ -199,7 +199,11 @@ int sva_kernel_time(void* ctx, const char* name, double* total_ms, int64_t* coun
  *                            0 = refine_box_kernel (k 1..16), 1 =
  *                            refine_kernel (k 0; k 1..16 on planes of 2^31
  *                            bytes or more), 2 = the box-sum route
- *                            (k >= 17), -1 = none yet. */
+ *                            (k >= 17), -1 = none yet.
+ *   SVA_DEBUG_CROSS_ORDER    set / get: the block order of sva_cross_check*'s
+ *                            kernel, 0 = view-major, 1 = tile-major, -1 restores
+ *                            the built-in choice (get returns the order in
+ *                            force).  Speed only: the outputs do not change. */
 #define SVA_DEBUG_PLANE_SPLIT 1
 #define SVA_DEBUG_FAIL_COST_AT 2
 #define SVA_DEBUG_SIDE_IDLE 3
@@ -210,6 +214,7 @@ int sva_kernel_time(void* ctx, const char* name, double* total_ms, int64_t* coun
 #define SVA_DEBUG_DIAG_PAIR_MIN_PIXELS 8
 #define SVA_DEBUG_REFINE_ROUTE 9
 #define SVA_DEBUG_REFINE_LAST_ROUTE 10
+#define SVA_DEBUG_CROSS_ORDER 11
 int sva_set_debug(void* ctx, int key, int64_t value);
 int sva_get_debug(void* ctx, int key, int64_t* value);
 
@@ -260,7 +265,8 @@ int sva_disparity_sgm_conf_d(void* ctx, const uint8_t* left, const uint8_t* righ
  * n image pointers (device images for _d, host images otherwise).  The outputs,
  * uniqueness and the size limits are those of sva_disparity_sgm_conf*; the
  * confidence planes are optional.  Any D in 1..256.  lr_check has no multi-view
- * definition: SVA_ERR_UNSUPPORTED.  n outside 1..32, a null image or a zero
+ * definition: SVA_ERR_UNSUPPORTED (the consistency test between several
+ * reference cameras' maps is sva_cross_check*, below).  n outside 1..32, a null image or a zero
  * step: SVA_ERR_INVALID_ARG, before anything is launched.
  * Workspace: the context's cost workspace grows to (n + 1) * W * H * Dn bytes
  * (Dn = D rounded up to 64, 128, 192 or 256; 2.4 GB for n = 8 at 1080p D = 128)
@@ -298,7 +304,8 @@ int sva_cost_fuse_d(void* ctx, const uint8_t* volumes, size_t stride, int n, int
  * other pair costs one census launch and one cost_mixed launch.
  * Refused before anything is launched: null ratios, num or den outside 1..8, a
  * match distance t(dmin + D - 1) above 65535 (SVA_ERR_INVALID_ARG), and
- * everything sva_disparity_sgm_multi* refuses (lr_check: SVA_ERR_UNSUPPORTED).
+ * everything sva_disparity_sgm_multi* refuses (lr_check: SVA_ERR_UNSUPPORTED;
+ * sva_cross_check* is the multi-view consistency test).
  * Workspace as for sva_disparity_sgm_multi*, plus two census maps (16 bytes per
  * pixel). */
 int sva_disparity_sgm_mixed(void* ctx, const uint8_t* ref, const uint8_t* const* others,
@@ -667,6 +674,40 @@ int sva_fuse_depth_conf_sub(void* ctx, const uint16_t* disps, const float* subpi
                             double pixel_size, uint16_t invalid, int mode, double* depth,
                             uint8_t* n_valid, uint8_t* winner);
 
+/* Cross-view consistency check between the maps of several reference cameras
+ * (DESIGN.md §2.5b): the multi-view counterpart of lr_check, one pass over maps
+ * that already exist.  disps: [n_views][H][W] u16 (device / host), every map
+ * counting pixels of the SAME unit baseline.  view_step: HOST [n_views][2] i32,
+ * each view's position in unit baselines in the sense of sva_sgm_params (dir,
+ * dir_y): the match step from view a to view b is e = view_step[b] -
+ * view_step[a], so view a's pixel p at disparity s lies at q = p + s * e in
+ * view b, exactly.  For view a, pixel p, s = disps[a][p]:
+ *   s == invalid or s == 0   out = s, agree = conflict = 0;
+ *   else every b != a with q inside the image and t = disps[b][q] valid counts:
+ *     |t - s| <= max_diff    agree += 1
+ *     t < s - max_diff       conflict += 1 (b sees through the point)
+ *     t > s + max_diff       neither (b is occluded by something nearer)
+ *   out = s if agree >= min_agree and conflict <= max_conflict, else invalid.
+ * subpix (nullable): [n_views][H][W] f32; out_sub (nullable, needs subpix) gets
+ * subpix where the pixel is kept or was not valid and NaN where it is rejected
+ * (the marks of lr_check).  agree, conflict (nullable): [n_views][H][W] u8.
+ * Every view is checked against the INPUT maps.  Integer-only, so every output
+ * is exact; min_agree = 0 with max_conflict = 31 copies the input.
+ * SVA_ERR_INVALID_ARG, before anything is launched: n_views outside 1..32, a
+ * null disps, view_step or out, a step component outside -255..255, two views
+ * with equal view_step, max_diff < 0, min_agree or max_conflict outside 0..31,
+ * out_sub without subpix, out or out_sub overlapping disps or subpix.
+ * SVA_ERR_UNSUPPORTED: width * height >= 2^31.  _d is asynchronous on the
+ * context stream; its kernel is timed as "cross_check". */
+int sva_cross_check_d(void* ctx, const uint16_t* disps, const float* subpix, int n_views,
+                      int width, int height, const int32_t* view_step, uint16_t invalid,
+                      int max_diff, int min_agree, int max_conflict, uint16_t* out,
+                      float* out_sub, uint8_t* agree, uint8_t* conflict);
+int sva_cross_check(void* ctx, const uint16_t* disps, const float* subpix, int n_views, int width,
+                    int height, const int32_t* view_step, uint16_t invalid, int max_diff,
+                    int min_agree, int max_conflict, uint16_t* out, float* out_sub,
+                    uint8_t* agree, uint8_t* conflict);
+
 /* Disparity -> depth, CameraStereoVision.cpp:47,98-100 (f64; 0 where disp 0). */
 int sva_disparity_to_depth_d(void* ctx, const uint8_t* disp, int n, double cam_distance,
                              double f, double pixel_size, double* depth);
@@ -794,7 +835,8 @@ int sva_array_depth_conf(void* multi, const uint8_t* const* images, int n_images
  * sva_array_depth_conf.  Within a group the pairs must share ref, D, dmin, P1,
  * P2 and invalid, and their baselines may differ by at most 1e-9 relative (a
  * different major-axis baseline is a different depth scale):
- * SVA_ERR_INVALID_ARG otherwise.  lr_check: SVA_ERR_UNSUPPORTED.  Each context
+ * SVA_ERR_INVALID_ARG otherwise.  lr_check: SVA_ERR_UNSUPPORTED (a frame with
+ * several reference cameras has sva_array_depth_checked instead).  Each context
  * that runs a group grows its cost workspace as sva_disparity_sgm_multi_d
  * says.  Synchronous. */
 int sva_array_depth_mb(void* multi, const uint8_t* const* images, int n_images, int width,
@@ -841,6 +883,37 @@ int sva_array_depth_sub(void* multi, const uint8_t* const* images, int n_images,
                         const double* unit_baseline, double f, double pixel_size, int uniqueness,
                         int mode, double* depth, uint8_t* n_valid, uint8_t* winner, float* subpix,
                         uint16_t* maps, uint16_t* cost_min, uint16_t* cost_second);
+/* An array frame of several reference cameras with the cross-view check
+ * (DESIGN.md §2.5b, §7): sva_array_depth_sub's arguments on a GROUP route (so
+ * mode is SVA_FUSE_MEDIAN and n_valid and winner are NULL), then the check's;
+ * between the gather and the depth step devices[0] runs sva_cross_check_d over
+ * the groups' maps, view g being camera pairs[group_start[g]].ref.  maps,
+ * subpix and depth are those of the CHECKED maps (depth from sva_fuse_depth_d,
+ * or with sub = 1 from sva_fuse_depth_sub_d); cost_min / cost_second are the
+ * matcher's.  view_step: host [n_images][2] i32, every camera's position in
+ * unit baselines (see sva_cross_check).  sub: 0 = integer depth as
+ * sva_array_depth_mb / _mixed (subpix must be NULL), 1 = as sva_array_depth_sub.
+ * agree, conflict (nullable): host [n_groups][H][W] u8.  min_agree = 0 with
+ * max_conflict = 31 gives the unchecked entry's outputs bit for bit.
+ * SVA_ARRAY_PAIRS: SVA_ERR_UNSUPPORTED (its maps share one reference camera:
+ * nothing to cross).  sub outside 0 / 1: SVA_ERR_INVALID_ARG, answered first.
+ * Then the rules of the route's own entry, and after them, in this order:
+ * null view_step; n_groups > 32 (SVA_ERR_UNSUPPORTED); two groups with one ref;
+ * groups whose params.invalid differ; groups whose depth scale (the pairs'
+ * baseline, or unit_baseline[g] on GROUPS_MIXED) differs by more than 1e-9
+ * relative; a pair whose step contradicts view_step -- with M = max(|dir|,
+ * |dir_y|), its ratio num/den (1/1 on GROUPS) and e = view_step[other] -
+ * view_step[ref], e * M * den must equal (dir, dir_y) * num; then the ranges of
+ * sva_cross_check on the groups' view_step, max_diff, min_agree, max_conflict.
+ * SVA_ERR_INVALID_ARG unless noted, before anything is launched. */
+int sva_array_depth_checked(void* multi, const uint8_t* const* images, int n_images, int width,
+                            int height, size_t pitch, const sva_array_pair* pairs, int n_pairs,
+                            const int32_t* group_start, int n_groups, int route,
+                            const double* unit_baseline, double f, double pixel_size,
+                            int uniqueness, int mode, double* depth, uint8_t* n_valid,
+                            uint8_t* winner, float* subpix, uint16_t* maps, uint16_t* cost_min,
+                            uint16_t* cost_second, const int32_t* view_step, int sub, int max_diff,
+                            int min_agree, int max_conflict, uint8_t* agree, uint8_t* conflict);
 
 #ifdef __cplusplus
 }

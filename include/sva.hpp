@@ -809,6 +809,101 @@ inline std::vector<std::vector<double>> computeArrayDepthSub(
     });
 }
 
+// ---- cross-view consistency check ------------------------
+
+// What crossCheck keeps of each view: the checked map, and the optional planes.
+struct CrossChecked {
+    std::vector<std::vector<uint16_t>> maps;
+    std::vector<std::vector<float>> subpix;       // empty unless sub-pixel maps went in
+    std::vector<std::vector<uint8_t>> agree, conflict;
+};
+
+// The consistency test between the maps of several reference cameras
+// (sva_cross_check): maps[v] is W*H u16 and counts pixels of one unit baseline
+// shared by all views, view_step[v] is view v's position in unit baselines in
+// the sense of PairStep (dir, dir_y) -- minus its grid offset.  A valid pixel
+// stays where at least min_agree other views hold a disparity within max_diff
+// at the pixel that sees the same point, and at most max_conflict hold a smaller
+// one (they see through it); otherwise it becomes `invalid`, and NaN in subpix.
+// subpix: empty, or one f32 map per view.
+inline CrossChecked crossCheck(Engine& eng, const std::vector<std::vector<uint16_t>>& maps,
+                               const std::vector<std::vector<float>>& subpix, int W, int H,
+                               const std::vector<std::array<int32_t, 2>>& view_step,
+                               int max_diff = 1, int min_agree = 1, int max_conflict = 0,
+                               uint16_t invalid = 0xFFFF) {
+    const size_t np = (size_t)W * H, n = maps.size();
+    if (maps.empty() || view_step.size() != n || (!subpix.empty() && subpix.size() != n))
+        throw Error(SVA_ERR_INVALID_ARG,
+                    "crossCheck: need one view_step (and sub-pixel map) per map");
+    std::vector<uint16_t> d(np * n), out(np * n);
+    std::vector<float> s(subpix.empty() ? 0 : np * n), out_s(s.size());
+    std::vector<uint8_t> ag(np * n), cf(np * n);
+    std::vector<int32_t> vs;
+    for (size_t i = 0; i < n; i++) {
+        if (maps[i].size() != np || (!subpix.empty() && subpix[i].size() != np))
+            throw Error(SVA_ERR_INVALID_ARG, "crossCheck: map size");
+        std::copy(maps[i].begin(), maps[i].end(), d.begin() + i * np);
+        if (!subpix.empty()) std::copy(subpix[i].begin(), subpix[i].end(), s.begin() + i * np);
+        vs.push_back(view_step[i][0]);
+        vs.push_back(view_step[i][1]);
+    }
+    eng.check(sva_cross_check(eng.handle(), d.data(), s.empty() ? nullptr : s.data(), (int)n, W, H,
+                              vs.data(), invalid, max_diff, min_agree, max_conflict, out.data(),
+                              s.empty() ? nullptr : out_s.data(), ag.data(), cf.data()));
+    CrossChecked r;
+    for (size_t i = 0; i < n; i++) {
+        r.maps.emplace_back(out.begin() + i * np, out.begin() + (i + 1) * np);
+        if (!s.empty()) r.subpix.emplace_back(out_s.begin() + i * np, out_s.begin() + (i + 1) * np);
+        r.agree.emplace_back(ag.begin() + i * np, ag.begin() + (i + 1) * np);
+        r.conflict.emplace_back(cf.begin() + i * np, cf.begin() + (i + 1) * np);
+    }
+    return r;
+}
+
+// computeArrayDepthMulti / Mixed (sub = false) or the group routes of
+// computeArrayDepthSub (sub = true) with the cross-view check between the
+// reference cameras' maps before depth (sva_array_depth_checked).  route:
+// SVA_ARRAY_GROUPS or SVA_ARRAY_GROUPS_MIXED.  Every camera's view_step is
+// minus its grid offset from cameras[0], in units of `pitch`; on
+// SVA_ARRAY_GROUPS the pairs must therefore be one grid unit long on their
+// major axis, and on GROUPS_MIXED the unit baseline is `pitch` (a longer unit
+// would put the cameras at fractions of it, which view_step cannot say).
+// maps, agree, conflict (nullable): one plane per reference camera, in the
+// order of the result.
+inline std::vector<std::vector<double>> computeArrayDepthChecked(
+    MultiEngine& m, const std::vector<ImageView>& images, const std::vector<Camera>& cameras,
+    const std::vector<std::array<int, 2>>& pairs, const sva_sgm_params& p,
+    int route = SVA_ARRAY_GROUPS, bool sub = false, int max_diff = 1, int min_agree = 1,
+    int max_conflict = 0, int uniqueness = 0, double pitch = 0.05,
+    std::vector<std::vector<uint16_t>>* maps = nullptr,
+    std::vector<std::vector<uint8_t>>* agree = nullptr,
+    std::vector<std::vector<uint8_t>>* conflict = nullptr) {
+    const detail::ArrayFrame fr = detail::arrayFrame(images, cameras, pairs, p, pitch,
+                                                     "computeArrayDepthChecked");
+    std::vector<double> unit;
+    if (route == SVA_ARRAY_GROUPS_MIXED) unit = detail::unitBaselines(fr, 1, pitch);
+    std::vector<int32_t> vs;
+    for (const Camera& c : cameras) {
+        vs.push_back(-(int32_t)std::lround((c.pos3D.x - cameras[0].pos3D.x) / pitch));
+        vs.push_back(-(int32_t)std::lround((c.pos3D.y - cameras[0].pos3D.y) / pitch));
+    }
+    const size_t np = (size_t)fr.W * fr.H, ng = fr.refs.size();
+    std::vector<uint8_t> ag(agree ? np * ng : 0), cf(conflict ? np * ng : 0);
+    auto depth = detail::arrayDepth(fr, cameras, pairs.size(), route != SVA_ARRAY_PAIRS, maps,
+                                    [&](double f, double pixel_size, double* depth, uint16_t* all) {
+        m.check(fr.call(sva_array_depth_checked, m.handle(), route,
+                        unit.empty() ? (const double*)nullptr : (const double*)unit.data(), f,
+                        pixel_size, uniqueness, (int)SVA_FUSE_MEDIAN, depth, (uint8_t*)nullptr,
+                        (uint8_t*)nullptr, (float*)nullptr, all, (uint16_t*)nullptr,
+                        (uint16_t*)nullptr, (const int32_t*)vs.data(), sub ? 1 : 0, max_diff,
+                        min_agree, max_conflict, agree ? ag.data() : (uint8_t*)nullptr,
+                        conflict ? cf.data() : (uint8_t*)nullptr));
+    });
+    if (agree) *agree = fr.split(ag);
+    if (conflict) *conflict = fr.split(cf);
+    return depth;
+}
+
 
 // ---- refinement and 3-D output ----
 // The reference's names and argument meaning; cv::Mat becomes ImageView (u8)

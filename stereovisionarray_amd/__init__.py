@@ -44,6 +44,7 @@ SVA_DEBUG_DIAG_ROUTE = 7
 SVA_DEBUG_DIAG_PAIR_MIN_PIXELS = 8
 SVA_DEBUG_REFINE_ROUTE = 9
 SVA_DEBUG_REFINE_LAST_ROUTE = 10
+SVA_DEBUG_CROSS_ORDER = 11
 # The ABI this binding is written against (include/sva.h SVA_ABI_VERSION).
 ABI_VERSION = 6
 
@@ -72,7 +73,8 @@ EXPORTED = [
     "sva_cost_fuse_mixed_d", "sva_disparity_sgm_mixed", "sva_disparity_sgm_mixed_d",
     "sva_array_depth_mixed", "sva_frame_layout_of", "sva_paths_frame_d", "sva_wta_frame_d",
     "sva_fuse_depth_sub", "sva_fuse_depth_sub_d", "sva_fuse_depth_conf_sub",
-    "sva_fuse_depth_conf_sub_d", "sva_array_depth_sub",
+    "sva_fuse_depth_conf_sub_d", "sva_array_depth_sub", "sva_cross_check", "sva_cross_check_d",
+    "sva_array_depth_checked",
 ]
 SVA_FUSE_MIN_COST = 0
 SVA_FUSE_MAX_MARGIN = 1
@@ -288,6 +290,13 @@ def _load() -> ct.CDLL:
                                           ct.c_uint16, i32, vp, vp, vp]),
         "sva_array_depth_sub": (i32, [vp, P(vp), i32, i32, i32, sz, P(ArrayPair), i32, P(i32), i32,
                                       i32, P(dbl), dbl, dbl, i32, i32, vp, vp, vp, vp, vp, vp, vp]),
+        "sva_cross_check_d": (i32, [vp, vp, vp, i32, i32, i32, P(ct.c_int32), ct.c_uint16, i32, i32,
+                                    i32, vp, vp, vp, vp]),
+        "sva_cross_check": (i32, [vp, vp, vp, i32, i32, i32, P(ct.c_int32), ct.c_uint16, i32, i32,
+                                  i32, vp, vp, vp, vp]),
+        "sva_array_depth_checked": (i32, [vp, P(vp), i32, i32, i32, sz, P(ArrayPair), i32, P(i32),
+                                          i32, i32, P(dbl), dbl, dbl, i32, i32, vp, vp, vp, vp, vp,
+                                          vp, vp, P(ct.c_int32), i32, i32, i32, i32, vp, vp]),
         "sva_resize_linear_f64_d": (i32, [vp, vp, i32, i32, vp, i32, i32]),
         "sva_resize_linear_f64": (i32, [vp, vp, i32, i32, vp, i32, i32]),
         "sva_ref_error_d": (i32, [vp, vp, i32, i32, vp, i32, i32, ct.c_double, vp]),
@@ -366,6 +375,15 @@ def _i32_pairs(pairs):
     if pairs is None:
         return None
     return (ct.c_int32 * max(2, 2 * len(pairs)))(*[int(v) for s in pairs for v in s])
+
+
+def _steps(view_step, n):
+    """n (x, y) view positions as a C [n][2] i32 array (a short list is padded
+    with zeros, so that the library's own checks see it); None stays null."""
+    if view_step is None:
+        return None
+    flat = [int(v) for s in view_step for v in s]
+    return (ct.c_int32 * max(2, 2 * n, len(flat)))(*flat)
 
 
 def _ptr_table(arrays):
@@ -908,6 +926,33 @@ class Context:
                                                 invalid, int(mode), _ptr(depth), _ptr(n_valid),
                                                 _ptr(winner)))
 
+    def cross_check(self, disps: np.ndarray, view_step, subpix=None, invalid=0xFFFF, max_diff=1,
+                    min_agree=1, max_conflict=0, want_agree=True, want_conflict=True):
+        """(out, out_sub or None, agree, conflict): sva_cross_check, the cross-view
+        consistency check of n maps [n][H][W] u16 of one unit
+        baseline; view_step: n (x, y) positions in unit baselines.  A pixel stays
+        where at least min_agree other views agree within max_diff and at most
+        max_conflict see through it; out_sub (with subpix) is NaN where rejected."""
+        d = np.ascontiguousarray(disps, dtype=np.uint16)
+        s = None if subpix is None else np.ascontiguousarray(subpix, dtype=np.float32)
+        N, H, W = d.shape
+        assert s is None or s.shape == d.shape
+        out = np.zeros_like(d)
+        osub = None if s is None else np.zeros_like(s)
+        ag = np.zeros(d.shape, np.uint8) if want_agree else None
+        cf = np.zeros(d.shape, np.uint8) if want_conflict else None
+        self._chk(lib.sva_cross_check(self.h, _ptr(d), _ptr(s), N, W, H, _steps(view_step, N),
+                                      invalid, int(max_diff), int(min_agree), int(max_conflict),
+                                      _ptr(out), _ptr(osub), _ptr(ag), _ptr(cf)))
+        return out, osub, ag, cf
+
+    def cross_check_d(self, disps, subpix, n_views, W, H, view_step, invalid, max_diff, min_agree,
+                      max_conflict, out, out_sub=None, agree=None, conflict=None):
+        self._chk(lib.sva_cross_check_d(self.h, _ptr(disps), _ptr(subpix), n_views, W, H,
+                                        _steps(view_step, n_views), invalid, int(max_diff),
+                                        int(min_agree), int(max_conflict), _ptr(out),
+                                        _ptr(out_sub), _ptr(agree), _ptr(conflict)))
+
     def disparity_to_depth(self, disp: np.ndarray, cam_distance, f, pixel_size):
         d = np.ascontiguousarray(disp, dtype=np.uint8)
         out = np.zeros(d.shape, np.float64)
@@ -1089,6 +1134,32 @@ class Multi:
                                           int(uniqueness), int(mode), _ptr(depth), _ptr(nv),
                                           _ptr(win), _ptr(sub), _ptr(maps), _ptr(cmin), _ptr(csec)))
         return depth, nv, win, sub, maps, cmin, csec
+
+    def array_depth_checked(self, images, pairs, group_start, f, pixel_size, view_step,
+                            route=SVA_ARRAY_GROUPS, unit_baseline=None, uniqueness=0, sub=0,
+                            max_diff=1, min_agree=1, max_conflict=0, want_sub=False,
+                            want_maps=False, want_costs=False, want_counts=False):
+        """sva_array_depth_checked: array_depth_mb / array_depth_mixed (sub = 0) or
+        the group routes of array_depth_sub (sub = 1) with the cross-view check
+         between the groups' maps before depth.  view_step: one
+        (x, y) position in unit baselines per image.  Returns (depth [G,H,W] f64,
+        subpix [G,H,W] f32, maps, cost_min, cost_second [G,H,W] u16, agree,
+        conflict [G,H,W] u8), each but depth None unless asked for; maps, subpix
+        and depth are the checked ones."""
+        fr = _ArrayFrame(images, pairs, group_start)
+        ub = None if unit_baseline is None else \
+            (ct.c_double * max(1, len(unit_baseline)))(*[float(v) for v in unit_baseline])
+        vs = None if view_step is None else _steps(view_step, len(view_step))
+        depth = fr.planes(fr.G, np.float64)
+        subp = fr.planes(fr.G, np.float32, want_sub)
+        maps = fr.planes(fr.G, np.uint16, want_maps)
+        cmin, csec = fr.planes(fr.G, np.uint16, want_costs), fr.planes(fr.G, np.uint16, want_costs)
+        ag, cf = fr.planes(fr.G, np.uint8, want_counts), fr.planes(fr.G, np.uint8, want_counts)
+        self._chk(lib.sva_array_depth_checked(
+            self.h, *fr.head, int(route), ub, f, pixel_size, int(uniqueness), SVA_FUSE_MEDIAN,
+            _ptr(depth), None, None, _ptr(subp), _ptr(maps), _ptr(cmin), _ptr(csec), vs, int(sub),
+            int(max_diff), int(min_agree), int(max_conflict), _ptr(ag), _ptr(cf)))
+        return depth, subp, maps, cmin, csec, ag, cf
 
     def array_depth(self, images, pairs, group_start, f, pixel_size, want_maps=False):
         """images: list of HxW u8 numpy views; pairs: list of (ref, other,

@@ -1,8 +1,9 @@
 // array_args.h -- the arguments of one camera-array frame (sva_array_depth,
-// _conf, _mb, _mixed and _sub) and their validation, shared by
-// multi.cpp and the host test programs (tests/test_array_args_cpu.py and
-// tests/test_array_sub_args_cpu.py compile this header with a C++ compiler
-// under the sanitizers).  Plain C++: no HIP header.
+// _conf, _mb, _mixed, _sub and _checked) and their validation,
+// shared by multi.cpp and the host test programs (tests/test_array_args_cpu.py,
+// tests/test_array_sub_args_cpu.py and tests/test_cross_check_cpu.py compile
+// this header with a C++ compiler under the sanitizers).  Plain C++: no HIP
+// header.
 #pragma once
 
 #include <algorithm>
@@ -13,6 +14,7 @@
 #include <vector>
 
 #include "cost_mixed_math.h"
+#include "cross_check_math.h"
 #include "sva.h"
 #include "sva_native_d.h"
 
@@ -57,6 +59,12 @@ struct ArrayArgs {
     uint8_t *n_valid = nullptr, *winner = nullptr;
     uint16_t *maps = nullptr, *cost_min = nullptr, *cost_second = nullptr;
     float* subpix = nullptr;                  // per job; sub only
+    // cross (sva_array_depth_checked): the groups' maps go
+    // through sva_cross_check_d before depth; group routes only
+    bool cross = false;
+    const int32_t* view_step = nullptr;       // [n_images][2], unit baselines
+    int max_diff = 0, min_agree = 0, max_conflict = 0;
+    uint8_t *agree = nullptr, *conflict = nullptr;   // host, per group, nullable
 };
 
 inline int check_params(const sva_sgm_params& p) {
@@ -87,6 +95,14 @@ inline bool baseline_ratio(double baseline, double unit, int32_t* num, int32_t* 
 // every pair; every group's shared values; the mixed route's ratios.  Returns
 // the status and the message of the first rule broken.  ratio (GroupsMixed):
 // receives every pair's reduced (num, den).
+// With a.cross, after all of the above and in this order: the pair route
+// (SVA_ERR_UNSUPPORTED); a subpix plane without sub; null view_step; more than
+// 32 groups (SVA_ERR_UNSUPPORTED); two groups with one ref; groups whose
+// `invalid` differ; groups whose depth scale differs; a pair whose step
+// contradicts view_step; the ranges of cross_check_math.h on the groups'
+// view_step (components, then duplicates) and on max_diff, min_agree,
+// max_conflict.  (The entry itself refuses a `sub` outside 0 / 1 before it
+// builds these arguments: ArrayArgs::sub is a bool.)
 inline int check_array_args(const ArrayArgs& a, std::string& msg, std::vector<int32_t>& ratio) {
     auto fail = [&](int code, const std::string& m) {
         msg = m;
@@ -103,7 +119,7 @@ inline int check_array_args(const ArrayArgs& a, std::string& msg, std::vector<in
         if (a.winner && a.mode == SVA_FUSE_MEDIAN)
             return fail(SVA_ERR_INVALID_ARG, "the median has no winner map");
     }
-    if (a.sub) {
+    if (a.sub || a.cross) {
         // the entry takes every route's arguments: those of another route are refused
         if (group && a.mode != SVA_FUSE_MEDIAN)
             return fail(SVA_ERR_INVALID_ARG, "the group routes fuse one map: SVA_FUSE_MEDIAN only");
@@ -156,10 +172,9 @@ inline int check_array_args(const ArrayArgs& a, std::string& msg, std::vector<in
                 return fail(SVA_ERR_INVALID_ARG, of_group + " have different major-axis baselines");
         }
     }
-    if (!mixed) return SVA_OK;
     // every pair's baseline as a ratio of its group's unit
-    ratio.assign(2 * (size_t)a.n_pairs, 0);
-    for (int g = 0; g < a.n_groups; g++)
+    if (mixed) ratio.assign(2 * (size_t)a.n_pairs, 0);
+    for (int g = 0; mixed && g < a.n_groups; g++)
         for (int j = gs[g]; j < gs[g + 1]; j++) {
             int32_t* rj = &ratio[2 * (size_t)j];
             if (!baseline_ratio(a.pairs[j].baseline, a.unit_baseline[g], rj, rj + 1))
@@ -173,6 +188,55 @@ inline int check_array_args(const ArrayArgs& a, std::string& msg, std::vector<in
                 return fail(SVA_ERR_INVALID_ARG,
                             "the match distance of pair " + std::to_string(j) + " exceeds 16 bits");
         }
+    if (!a.cross) return SVA_OK;
+    // ---- the cross-view check ----
+    if (!group)
+        return fail(SVA_ERR_UNSUPPORTED,
+                    "the cross-view check needs a group route: the pair route's maps share one "
+                    "reference camera");
+    if (!a.sub && a.subpix)
+        return fail(SVA_ERR_INVALID_ARG, "subpix needs sub = 1");
+    if (!a.view_step) return fail(SVA_ERR_INVALID_ARG, "null view_step");
+    if (a.n_groups > cc::kMaxViews)
+        return fail(SVA_ERR_UNSUPPORTED, "the cross-view check takes 1..32 groups");
+    auto scale_of = [&](int g) { return mixed ? a.unit_baseline[g] : a.pairs[gs[g]].baseline; };
+    for (int g = 1; g < a.n_groups; g++) {
+        for (int h = 0; h < g; h++)
+            if (a.pairs[gs[g]].ref == a.pairs[gs[h]].ref)
+                return fail(SVA_ERR_INVALID_ARG, "groups " + std::to_string(h) + " and " +
+                                                     std::to_string(g) + " share ref");
+    }
+    for (int g = 1; g < a.n_groups; g++)
+        if (a.pairs[gs[g]].params.invalid != a.pairs[gs[0]].params.invalid)
+            return fail(SVA_ERR_INVALID_ARG,
+                        "params.invalid of group " + std::to_string(g) + " differs from group 0's");
+    for (int g = 1; g < a.n_groups; g++) {
+        const double s0 = scale_of(0), sg = scale_of(g);
+        if (!(std::fabs(sg - s0) <= 1e-9 * std::max(std::fabs(sg), std::fabs(s0))))
+            return fail(SVA_ERR_INVALID_ARG, "the depth scale of group " + std::to_string(g) +
+                                                 " differs from group 0's");
+    }
+    for (int j = 0; j < a.n_pairs; j++) {
+        const sva_array_pair& q = a.pairs[j];
+        const long long dx = q.params.dir, dy = q.params.dir_y;
+        const long long M = std::max(std::llabs(dx), std::llabs(dy));
+        const long long num = mixed ? ratio[2 * (size_t)j] : 1;
+        const long long den = mixed ? ratio[2 * (size_t)j + 1] : 1;
+        const long long ex = (long long)a.view_step[2 * q.other] - a.view_step[2 * q.ref];
+        const long long ey = (long long)a.view_step[2 * q.other + 1] - a.view_step[2 * q.ref + 1];
+        if (ex * M * den != dx * num || ey * M * den != dy * num)
+            return fail(SVA_ERR_INVALID_ARG,
+                        "the step of pair " + std::to_string(j) + " contradicts view_step");
+    }
+    std::vector<int32_t> vs(2 * (size_t)a.n_groups);
+    for (int g = 0; g < a.n_groups; g++) {
+        vs[2 * (size_t)g] = a.view_step[2 * a.pairs[gs[g]].ref];
+        vs[2 * (size_t)g + 1] = a.view_step[2 * a.pairs[gs[g]].ref + 1];
+    }
+    const char* m = cc::step_range_error(vs.data(), a.n_groups);
+    if (!m) m = cc::step_distinct_error(vs.data(), a.n_groups);
+    if (!m) m = cc::thresholds_error(a.max_diff, a.min_agree, a.max_conflict);
+    if (m) return fail(SVA_ERR_INVALID_ARG, m);
     return SVA_OK;
 }
 

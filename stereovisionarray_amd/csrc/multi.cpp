@@ -12,7 +12,7 @@
 // through the public per-context entry points (sva_disparity_sgm_d,
 // sva_fuse_depth_d, and sva_disparity_sgm_conf_d / sva_fuse_depth_conf_d for
 // the confidence forms, whose cost planes are gathered like the maps); there
-// is no CPU path.  The five sva_array_depth* entry points fill one ArrayArgs
+// is no CPU path.  The six sva_array_depth* entry points fill one ArrayArgs
 // (array_args.h: the arguments and their checks, in one order) and run one
 // array_frame(): its jobs are pairs, or -- sva_array_depth_mb -- GROUPS (one
 // sva_disparity_sgm_multi_d per reference camera, DESIGN.md §2.2c;
@@ -119,6 +119,7 @@ struct Multi {
     DevBuf maps0, depth0, nvalid0;     // device 0 (sva_array_depth)
     DevBuf conf0, winner0;             // device 0: cost planes, winners (sva_array_depth_conf)
     DevBuf sub0;                       // device 0: f32 sub-pixel maps (sva_array_depth_sub)
+    DevBuf cross0;                     // device 0: the checked planes (sva_array_depth_checked)
     PinnedBuf stage_in, stage_out;
     Rccl rccl;
     std::vector<ncclComm_t> comms;
@@ -642,6 +643,7 @@ int sva_multi_destroy(void* mp) {
         m->conf0.release();
         m->winner0.release();
         m->sub0.release();
+        m->cross0.release();
     }
     m->stage_in.release();
     m->stage_out.release();
@@ -813,7 +815,7 @@ struct Download {
     }
 };
 
-// One camera-array frame: sva_array_depth, _conf, _mb, _mixed and _sub (array_args.h
+// One camera-array frame: sva_array_depth, _conf, _mb, _mixed, _sub and _checked (array_args.h
 // has their arguments and checks).  A job is a pair (ArrayRoute::Pairs: every
 // pair through sva_disparity_sgm_d or, with conf, sva_disparity_sgm_conf_d; a
 // group's maps are fused by `mode`) or a GROUP (group g's
@@ -822,6 +824,9 @@ struct Download {
 // sva_disparity_sgm_mixed_d, and the depth scale is the unit baseline).  With
 // a.sub (sva_array_depth_sub, §2.6c) every job also writes its f32 sub-pixel
 // map, gathered into sub0 like the u16 one, and depth is fused from those.
+// With a.cross (sva_array_depth_checked, §2.5b) the groups' maps pass through
+// sva_cross_check_d on device 0 before step 4, which then reads the checked
+// planes.
 int array_frame(void* mp, const ArrayArgs& a) {
     Multi* m = as_multi(mp);
     if (!m) return SVA_ERR_INVALID_ARG;
@@ -913,6 +918,30 @@ int array_frame(void* mp, const ArrayArgs& a) {
         },
         group ? "group" : "pair");
     if (st) return st;
+    // 3b. the cross-view check: one pass on device 0 over the gathered maps into
+    // planes of cross0 -- u16 maps, f32 maps (sub), agree, conflict -- which take
+    // the place of maps0 / sub0 from here on
+    uint8_t *agree0 = nullptr, *conflict0 = nullptr;
+    if (a.cross) {
+        MHIP(m, hipSetDevice(m->devices[0]), "hipSetDevice");
+        MHIP(m, m->cross0.ensure(plane * (a.sub ? 3 : 1) + 2 * np * n_groups), "check workspace");
+        uint8_t* w = (uint8_t*)m->cross0.ptr;
+        float* csub = a.sub ? (float*)w : nullptr;             // the f32 planes first: aligned
+        uint16_t* cmaps = (uint16_t*)(w + (a.sub ? plane * 2 : 0));
+        agree0 = w + plane * (a.sub ? 3 : 1);
+        conflict0 = agree0 + np * n_groups;
+        std::vector<int32_t> vs(2 * (size_t)n_groups);
+        for (int g = 0; g < n_groups; g++) {
+            vs[2 * (size_t)g] = a.view_step[2 * pairs[gs[g]].ref];
+            vs[2 * (size_t)g + 1] = a.view_step[2 * pairs[gs[g]].ref + 1];
+        }
+        st = sva_cross_check_d(m->ctx[0], maps0, sub0, n_groups, W, H, vs.data(),
+                               pairs[0].params.invalid, a.max_diff, a.min_agree, a.max_conflict,
+                               cmaps, csub, agree0, conflict0);
+        if (st) return m->ctx_fail(st, m->ctx[0], "cross-view check");
+        maps0 = cmaps;
+        sub0 = csub;
+    }
     // 4. depth per group on device 0 -- the fusion of its pairs' maps, or the
     // depth of its one map (the median of one is the map's own depth) -- each
     // group's download as soon as it is done, the per-job planes at the end
@@ -931,6 +960,8 @@ int array_frame(void* mp, const ArrayArgs& a) {
     dl.add(n_groups, sub0, a.subpix, plane * 2);
     dl.add(n_groups, cp.cost_min, a.cost_min, plane);
     dl.add(n_groups, cp.cost_second, a.cost_second, plane);
+    dl.add(n_groups, agree0, a.agree, np * n_groups);
+    dl.add(n_groups, conflict0, a.conflict, np * n_groups);
     MHIP(m, m->stage_out.ensure(dl.total), "pinned staging");
     std::vector<double> bases(n_pairs);
     for (int j = 0; j < n_pairs; j++) bases[j] = pairs[j].baseline;
@@ -969,7 +1000,7 @@ int array_frame(void* mp, const ArrayArgs& a) {
     return dl.finish(m);
 }
 
-// What the five entry points share; as it stands, sva_array_depth's: the pair
+// What the six entry points share; as it stands, sva_array_depth's: the pair
 // route, plain matching, median fusion.
 ArrayArgs frame_args(const uint8_t* const* images, int n_images, int W, int H, size_t pitch,
                      const sva_array_pair* pairs, int n_pairs, const int32_t* group_start,
@@ -1079,6 +1110,38 @@ int sva_array_depth_sub(void* mp, const uint8_t* const* images, int n_images, in
     a.n_valid = n_valid;
     a.winner = winner;
     a.subpix = subpix;
+    return array_frame(mp, a);
+}
+
+int sva_array_depth_checked(void* mp, const uint8_t* const* images, int n_images, int W, int H,
+                            size_t pitch, const sva_array_pair* pairs, int n_pairs,
+                            const int32_t* group_start, int n_groups, int route,
+                            const double* unit_baseline, double f, double pixel_size,
+                            int uniqueness, int mode, double* depth, uint8_t* n_valid,
+                            uint8_t* winner, float* subpix, uint16_t* maps, uint16_t* cost_min,
+                            uint16_t* cost_second, const int32_t* view_step, int sub, int max_diff,
+                            int min_agree, int max_conflict, uint8_t* agree, uint8_t* conflict) {
+    if (sub != 0 && sub != 1) {
+        Multi* m = as_multi(mp);
+        return m ? m->fail(SVA_ERR_INVALID_ARG, "sub must be 0 or 1") : SVA_ERR_INVALID_ARG;
+    }
+    ArrayArgs a = frame_args(images, n_images, W, H, pitch, pairs, n_pairs, group_start, n_groups,
+                             f, pixel_size, uniqueness, depth, maps, cost_min, cost_second);
+    a.route = array_route_of(route);
+    a.conf = true;
+    a.sub = sub != 0;
+    a.mode = mode;
+    a.unit_baseline = unit_baseline;
+    a.n_valid = n_valid;
+    a.winner = winner;
+    a.subpix = subpix;
+    a.cross = true;
+    a.view_step = view_step;
+    a.max_diff = max_diff;
+    a.min_agree = min_agree;
+    a.max_conflict = max_conflict;
+    a.agree = agree;
+    a.conflict = conflict;
     return array_frame(mp, a);
 }
 

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "cost_mixed_math.h"
+#include "cross_check_math.h"
 #include "sva_internal.h"
 #include "sva_tuning.h"
 
@@ -895,6 +896,11 @@ int sva_set_debug(void* ctx, int key, int64_t value) {
             if (value < 0 || value > 1) return fail(c, SVA_ERR_INVALID_ARG, "refine route must be 0 or 1");
             c->dbg_refine_route = (int)value;
             return SVA_OK;
+        case SVA_DEBUG_CROSS_ORDER:
+            if (value < -1 || value > 1)
+                return fail(c, SVA_ERR_INVALID_ARG, "cross order must be -1, 0 or 1");
+            c->dbg_cross_order = (int)value;
+            return SVA_OK;
         default:
             return fail(c, SVA_ERR_INVALID_ARG, "unknown or read-only debug key");
     }
@@ -916,6 +922,9 @@ int sva_get_debug(void* ctx, int key, int64_t* value) {
             return SVA_OK;
         case SVA_DEBUG_REFINE_ROUTE: *value = c->dbg_refine_route; return SVA_OK;
         case SVA_DEBUG_REFINE_LAST_ROUTE: *value = c->last_refine_route; return SVA_OK;
+        case SVA_DEBUG_CROSS_ORDER:
+            *value = c->dbg_cross_order >= 0 ? c->dbg_cross_order : tune::kCrossTileMajor;
+            return SVA_OK;
         case SVA_DEBUG_SIDE_IDLE: {
             bool idle = true;
             for (hipStream_t s : c->side) {
@@ -1821,6 +1830,89 @@ int sva_fuse_depth_conf_sub(void* ctx, const uint16_t* disps, const float* subpi
     if (int s = check_subpix(c, subpix)) return s;
     return fuse_host(c, disps, subpix, cost_min, cost_second, n_maps, W, H, baselines, f,
                      pixel_size, invalid, mode, depth, n_valid, winner);
+}
+
+// ------------------------- cross-view consistency check --
+namespace {
+bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return a && b && x < y + nb && y < x + na;
+}
+
+// The rules of sva_cross_check and sva_cross_check_d, in sva.h's order; the
+// pointers are the caller's (host or device), which is where overlap matters.
+int check_cross(Ctx* c, const uint16_t* disps, const float* subpix, int n, int W, int H,
+                const int32_t* view_step, int max_diff, int min_agree, int max_conflict,
+                const uint16_t* out, const float* out_sub) {
+    if (!disps || !view_step || !out) return fail(c, SVA_ERR_INVALID_ARG, "null pointer");
+    if (n < 1 || n > cc::kMaxViews) return fail(c, SVA_ERR_INVALID_ARG, "n_views must be 1..32");
+    if (W <= 0 || H <= 0) return fail(c, SVA_ERR_INVALID_ARG, "image size must be positive");
+    if ((unsigned long long)W * (unsigned long long)H >= (1ull << 31))
+        return fail(c, SVA_ERR_UNSUPPORTED, "the cross-view check needs W * H < 2^31");
+    const char* m = cc::step_range_error(view_step, n);
+    if (!m) m = cc::step_distinct_error(view_step, n);
+    if (!m) m = cc::thresholds_error(max_diff, min_agree, max_conflict);
+    if (m) return fail(c, SVA_ERR_INVALID_ARG, m);
+    if (out_sub && !subpix) return fail(c, SVA_ERR_INVALID_ARG, "out_sub needs subpix");
+    const size_t b16 = (size_t)W * H * 2 * (size_t)n, b32 = b16 * 2;
+    if (ranges_overlap(out, b16, disps, b16) || ranges_overlap(out, b16, subpix, b32) ||
+        ranges_overlap(out_sub, b32, disps, b16) || ranges_overlap(out_sub, b32, subpix, b32))
+        return fail(c, SVA_ERR_INVALID_ARG, "an output overlaps an input");
+    return SVA_OK;
+}
+
+int run_cross(Ctx* c, const uint16_t* disps, const float* subpix, int n, int W, int H,
+              const int32_t* view_step, uint16_t invalid, int max_diff, int min_agree,
+              int max_conflict, uint16_t* out, float* out_sub, uint8_t* agree, uint8_t* conflict) {
+    const int order = c->dbg_cross_order >= 0 ? c->dbg_cross_order : tune::kCrossTileMajor;
+    SVA_HIP(c, launch_cross_check(*c, disps, subpix, n, W, H, view_step, invalid, max_diff,
+                                  min_agree, max_conflict, order, out, out_sub, agree, conflict),
+            "cross-check launch");
+    return SVA_OK;
+}
+}  // namespace
+
+int sva_cross_check_d(void* ctx, const uint16_t* disps, const float* subpix, int n, int W, int H,
+                      const int32_t* view_step, uint16_t invalid, int max_diff, int min_agree,
+                      int max_conflict, uint16_t* out, float* out_sub, uint8_t* agree,
+                      uint8_t* conflict) {
+    Ctx* c = as_ctx(ctx);
+    SVA_CHECK_CTX(c);
+    if (int s = check_cross(c, disps, subpix, n, W, H, view_step, max_diff, min_agree, max_conflict,
+                            out, out_sub))
+        return s;
+    return run_cross(c, disps, subpix, n, W, H, view_step, invalid, max_diff, min_agree,
+                     max_conflict, out, out_sub, agree, conflict);
+}
+
+// The count planes stage through out_c, agree first.
+int sva_cross_check(void* ctx, const uint16_t* disps, const float* subpix, int n, int W, int H,
+                    const int32_t* view_step, uint16_t invalid, int max_diff, int min_agree,
+                    int max_conflict, uint16_t* out, float* out_sub, uint8_t* agree,
+                    uint8_t* conflict) {
+    Ctx* c = as_ctx(ctx);
+    SVA_CHECK_CTX(c);
+    if (int s = check_cross(c, disps, subpix, n, W, H, view_step, max_diff, min_agree, max_conflict,
+                            out, out_sub))
+        return s;
+    const size_t nnp = (size_t)W * H * (size_t)n;
+    Staging g{c};
+    const uint16_t* dd = g.up<uint16_t>(c->in_a, disps, nnp * 2);
+    const float* ds = subpix ? g.up<float>(c->in_mask, subpix, nnp * 4) : nullptr;
+    uint16_t* dout = g.out<uint16_t>(c->out_a, nnp * 2);
+    float* dsub = out_sub ? g.out<float>(c->out_b, nnp * 4) : nullptr;
+    uint8_t* cnt = agree || conflict ? g.out<uint8_t>(c->out_c, nnp * 2) : nullptr;
+    uint8_t* dag = agree ? cnt : nullptr;
+    uint8_t* dcf = conflict ? cnt + nnp : nullptr;
+    if (g.st) return g.st;
+    if (int s = run_cross(c, dd, ds, n, W, H, view_step, invalid, max_diff, min_agree, max_conflict,
+                          dout, dsub, dag, dcf))
+        return s;
+    g.down(out, dout, nnp * 2);
+    g.down(out_sub, dsub, nnp * 4);
+    g.down(agree, dag, nnp);
+    g.down(conflict, dcf, nnp);
+    return g.sync();
 }
 
 // ------------------------------------------ refinement / 3-D --

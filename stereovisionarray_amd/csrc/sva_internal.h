@@ -67,6 +67,9 @@ struct Ctx {
     // refine_kernel<ND>, 2 = box-sum route, -1 = no refine launch yet)
     int dbg_refine_route = 0;
     int last_refine_route = -1;
+    // SVA_DEBUG_CROSS_ORDER: cross_check's block order (-1 = tune::kCrossTileMajor,
+    // 0 = view-major, 1 = tile-major)
+    int dbg_cross_order = -1;
     // Mode R's split plane loop: one first-minimum key per pixel (refpath.hip).
     // ref_finalize_kernel puts every key it reads back to all-ones, so after
     // the first call only a grown buffer needs the memset: ref_keys_clean =
@@ -248,6 +251,14 @@ hipError_t launch_fuse_depth_conf_sub(Ctx& c, const uint16_t* disps, const float
                                       int n_maps, size_t np, const double* num, double pixel_size,
                                       uint16_t invalid, int mode, double* depth, uint8_t* n_valid,
                                       uint8_t* winner);
+// cross_check.hip -- the cross-view consistency check: n <= 32
+// maps [n][H][W] of one unit baseline, view_step [n][2] (host); subpix / out_sub
+// (f32), agree, conflict (u8) nullable, out_sub needs subpix; W * H < 2^31.
+// tile_major: the block order (tune::kCrossTileMajor), speed only.
+hipError_t launch_cross_check(Ctx& c, const uint16_t* disps, const float* subpix, int n, int W,
+                              int H, const int32_t* view_step, uint16_t invalid, int max_diff,
+                              int min_agree, int max_conflict, int tile_major, uint16_t* out,
+                              float* out_sub, uint8_t* agree, uint8_t* conflict);
 // refpath.hip
 hipError_t launch_ref_endpoints(Ctx& c, int W, int H, const sva_camera& cref,
                                 const sva_camera& coth, int k, double t_near, double t_far,

@@ -247,5 +247,20 @@ constexpr int kPlaneSplitMin = 3;
 constexpr int kPlaneSplitMax = 6;
 constexpr int kPlaneSplitRounds = 4;
 
+// ---- cross_check.hip -------------------------------------
+// Block order: 0 view-major, 1 tile-major (the view index innermost in groups
+// of 8 tiles, so the workgroups that share an XCD walk one tile of every view).
+// A/B at 1080p on real maps, the orders alternating call by call, 15 calls each,
+// every plane written, stream events around the call (tools/bench_cross_check.py
+// --kernel, profiles/cross_check/kernel_1080p.json), ms median (min-max), view /
+// tile:
+// n = 25  1.380 (1.374-1.385) / 1.339 (1.333-1.344); u16 planes only 1.282
+// (1.275-1.285) / 1.221 (1.212-1.226): tile-major wins outside both spreads.
+// n = 9   0.243 (0.221-0.258) / 0.224 (0.216-0.232): the spreads overlap, no
+// significant difference.  320x240: 13-55 us, equal in one session, tile-major
+// slower in the median in another; not decisive.
+// Chosen on n = 25; one order for every n rather than a switch on n.
+constexpr int kCrossTileMajor = 1;
+
 }  // namespace tune
 }  // namespace sva
