@@ -708,6 +708,41 @@ int sva_cross_check(void* ctx, const uint16_t* disps, const float* subpix, int n
                     int min_agree, int max_conflict, uint16_t* out, float* out_sub,
                     uint8_t* agree, uint8_t* conflict);
 
+/* Speckle filter: removes the small connected components of
+ * n_maps >= 1 disparity maps disps [n_maps][H][W] u16 (device / host), the
+ * post-filter of OpenCV's filterSpeckles and libSGM's speckleWindowSize /
+ * speckleRange, on the device.  A pixel is valid iff d != invalid and d != 0.
+ * Two pixels of one map are linked iff they are 4-neighbours, both valid, and
+ * |d1 - d2| <= max_diff (against the neighbour, not against a seed; max_diff
+ * above 65535 counts as 65535).  comp_size(p) = the pixel count of p's connected
+ * component of that graph, 0 where p is not valid; maps never connect.
+ *   out = d         where p is not valid or comp_size > max_size
+ *   out = invalid   where p is valid and comp_size <= max_size
+ * subpix (nullable): [n_maps][H][W] f32; out_sub (nullable, needs subpix) gets
+ * subpix where out = d and NaN where the pixel was removed.  comp_size
+ * (nullable): [n_maps][H][W] u32.  max_size in 0..2^31-1; max_size = 0 copies
+ * the input bit for bit.  Integer-only and independent of any ordering: every
+ * output byte has one right value.  In place is allowed: out == disps and / or
+ * out_sub == subpix, exactly.
+ * Workspace: 8 * n_maps * width * height bytes of device memory per context
+ * (two u32 planes per map), grown on demand, kept for later calls and freed by
+ * sva_destroy; none for max_size = 0 without comp_size.
+ * Returned before anything is launched, in this order: SVA_ERR_INVALID_ARG for
+ * a null disps or out, n_maps < 1, a width or height < 1; SVA_ERR_UNSUPPORTED
+ * for width * height >= 2^31; SVA_ERR_INVALID_ARG for max_size < 0, max_diff <
+ * 0, out_sub without subpix, or any overlap of an output (out, out_sub,
+ * comp_size) with an input or another output other than the two in-place forms
+ * above; SVA_ERR_OUT_OF_MEMORY if the workspace cannot be had.  _d is
+ * asynchronous on the context stream; its four launches are timed as
+ * "speckle_label", "speckle_merge", "speckle_count" and "speckle_apply" (the
+ * copy: "speckle_apply" alone). */
+int sva_filter_speckles_d(void* ctx, const uint16_t* disps, const float* subpix, int n_maps,
+                          int width, int height, uint16_t invalid, int max_size, int max_diff,
+                          uint16_t* out, float* out_sub, uint32_t* comp_size);
+int sva_filter_speckles(void* ctx, const uint16_t* disps, const float* subpix, int n_maps,
+                        int width, int height, uint16_t invalid, int max_size, int max_diff,
+                        uint16_t* out, float* out_sub, uint32_t* comp_size);
+
 /* Disparity -> depth, CameraStereoVision.cpp:47,98-100 (f64; 0 where disp 0). */
 int sva_disparity_to_depth_d(void* ctx, const uint8_t* disp, int n, double cam_distance,
                              double f, double pixel_size, double* depth);
@@ -914,6 +949,40 @@ int sva_array_depth_checked(void* multi, const uint8_t* const* images, int n_ima
                             uint8_t* winner, float* subpix, uint16_t* maps, uint16_t* cost_min,
                             uint16_t* cost_second, const int32_t* view_step, int sub, int max_diff,
                             int min_agree, int max_conflict, uint8_t* agree, uint8_t* conflict);
+/* An array frame with the speckle filter:
+ * sva_array_depth_checked's arguments, then check, the filter's max_size and
+ * max_diff (see sva_filter_speckles) and comp_size (nullable): host
+ * [n_jobs][H][W] u32, one plane per map (per pair on SVA_ARRAY_PAIRS, per group
+ * on the group routes).  devices[0] runs sva_filter_speckles_d in place over
+ * every job's map after the optional cross-view check and before the depth step.
+ * check = 1: sva_array_depth_checked plus the filter (group routes only).
+ * check = 0: no cross-view check; view_step, max_diff, min_agree, max_conflict
+ * are ignored, agree and conflict must be NULL, and every route is accepted: on
+ * SVA_ARRAY_PAIRS every pair's map is filtered before its group's fusion, with
+ * every mode and with per-pair lr_check.  maps, subpix, depth, n_valid and
+ * winner are those of the FILTERED maps; cost_min / cost_second are the
+ * matcher's.  Bit for bit: speckle_max_size = 0 gives sva_array_depth_checked's
+ * outputs (check = 1), sva_array_depth_sub's (check = 0, sub = 1) or those of
+ * the route's own entry -- sva_array_depth_conf, _mb, _mixed -- (check = 0, sub
+ * = 0); any other value gives the stand-alone composition: the unfiltered
+ * frame's maps through sva_cross_check (check = 1), sva_filter_speckles and the
+ * matching sva_fuse_depth*.
+ * sub outside 0 / 1: SVA_ERR_INVALID_ARG, answered first.  Then the rules of
+ * sva_array_depth_checked (check = 1) or of the route's own entry and of
+ * sva_array_depth_sub's shared argument list (check = 0), and after them, in
+ * this order, SVA_ERR_INVALID_ARG for: check outside 0 / 1; with check = 0, a
+ * non-NULL agree or conflict, then a subpix plane with sub = 0;
+ * speckle_max_size < 0; speckle_max_diff < 0.  Before anything is launched. */
+int sva_array_depth_filtered(void* multi, const uint8_t* const* images, int n_images, int width,
+                             int height, size_t pitch, const sva_array_pair* pairs, int n_pairs,
+                             const int32_t* group_start, int n_groups, int route,
+                             const double* unit_baseline, double f, double pixel_size,
+                             int uniqueness, int mode, double* depth, uint8_t* n_valid,
+                             uint8_t* winner, float* subpix, uint16_t* maps, uint16_t* cost_min,
+                             uint16_t* cost_second, const int32_t* view_step, int sub,
+                             int max_diff, int min_agree, int max_conflict, uint8_t* agree,
+                             uint8_t* conflict, int check, int speckle_max_size,
+                             int speckle_max_diff, uint32_t* comp_size);
 
 #ifdef __cplusplus
 }

@@ -904,6 +904,93 @@ inline std::vector<std::vector<double>> computeArrayDepthChecked(
     return depth;
 }
 
+// ---- speckle filter ---------------------------------------
+
+// What filterSpeckles keeps of each map: the filtered map, the optional f32
+// map, and the size of every pixel's component (0 where the pixel is not valid).
+struct SpeckleFiltered {
+    std::vector<std::vector<uint16_t>> maps;
+    std::vector<std::vector<float>> subpix;       // empty unless sub-pixel maps went in
+    std::vector<std::vector<uint32_t>> comp_size;
+};
+
+// Removes the small connected components of each map (sva_filter_speckles): a
+// valid pixel (not `invalid`, not 0) whose 4-connected component -- neighbours
+// linked where both are valid and differ by at most max_diff -- has at most
+// max_size pixels becomes `invalid`, and NaN in subpix.  maps[i] is W*H u16;
+// subpix: empty, or one f32 map per map.  max_size = 0 returns the input.
+inline SpeckleFiltered filterSpeckles(Engine& eng, const std::vector<std::vector<uint16_t>>& maps,
+                                      const std::vector<std::vector<float>>& subpix, int W, int H,
+                                      int max_size, int max_diff, uint16_t invalid = 0xFFFF) {
+    const size_t np = (size_t)W * H, n = maps.size();
+    if (maps.empty() || (!subpix.empty() && subpix.size() != n))
+        throw Error(SVA_ERR_INVALID_ARG, "filterSpeckles: need one sub-pixel map per map");
+    std::vector<uint16_t> d(np * n);
+    std::vector<float> s(subpix.empty() ? 0 : np * n);
+    std::vector<uint32_t> size(np * n);
+    for (size_t i = 0; i < n; i++) {
+        if (maps[i].size() != np || (!subpix.empty() && subpix[i].size() != np))
+            throw Error(SVA_ERR_INVALID_ARG, "filterSpeckles: map size");
+        std::copy(maps[i].begin(), maps[i].end(), d.begin() + i * np);
+        if (!subpix.empty()) std::copy(subpix[i].begin(), subpix[i].end(), s.begin() + i * np);
+    }
+    // in place on the packed copies
+    eng.check(sva_filter_speckles(eng.handle(), d.data(), s.empty() ? nullptr : s.data(), (int)n, W,
+                                  H, invalid, max_size, max_diff, d.data(),
+                                  s.empty() ? nullptr : s.data(), size.data()));
+    SpeckleFiltered r;
+    for (size_t i = 0; i < n; i++) {
+        r.maps.emplace_back(d.begin() + i * np, d.begin() + (i + 1) * np);
+        if (!s.empty()) r.subpix.emplace_back(s.begin() + i * np, s.begin() + (i + 1) * np);
+        r.comp_size.emplace_back(size.begin() + i * np, size.begin() + (i + 1) * np);
+    }
+    return r;
+}
+
+// An array frame with the speckle filter over every job's map before depth
+// (sva_array_depth_filtered).  check = false: the frame of computeArrayDepthConf
+// (route SVA_ARRAY_PAIRS; mode as there, per-pair lr_check allowed),
+// computeArrayDepthMulti (SVA_ARRAY_GROUPS) or computeArrayDepthMixed
+// (SVA_ARRAY_GROUPS_MIXED, unit baseline `pitch`), or with sub = true of
+// computeArrayDepthSub.  check = true: computeArrayDepthChecked (group routes,
+// its view_step convention and thresholds), the filter after the check.
+// maps, comp_size (nullable): one plane per pair in `pairs` order, or one per
+// reference camera.
+inline std::vector<std::vector<double>> computeArrayDepthFiltered(
+    MultiEngine& m, const std::vector<ImageView>& images, const std::vector<Camera>& cameras,
+    const std::vector<std::array<int, 2>>& pairs, const sva_sgm_params& p, int speckle_max_size,
+    int speckle_max_diff, int route = SVA_ARRAY_GROUPS, bool check = false, bool sub = false,
+    int max_diff = 1, int min_agree = 1, int max_conflict = 0, int uniqueness = 0,
+    int mode = SVA_FUSE_MEDIAN, double pitch = 0.05,
+    std::vector<std::vector<uint16_t>>* maps = nullptr,
+    std::vector<std::vector<uint32_t>>* comp_size = nullptr) {
+    const detail::ArrayFrame fr = detail::arrayFrame(images, cameras, pairs, p, pitch,
+                                                     "computeArrayDepthFiltered");
+    std::vector<double> unit;
+    if (route == SVA_ARRAY_GROUPS_MIXED) unit = detail::unitBaselines(fr, 1, pitch);
+    std::vector<int32_t> vs;
+    for (const Camera& c : cameras) {
+        vs.push_back(-(int32_t)std::lround((c.pos3D.x - cameras[0].pos3D.x) / pitch));
+        vs.push_back(-(int32_t)std::lround((c.pos3D.y - cameras[0].pos3D.y) / pitch));
+    }
+    const bool per_group = route != SVA_ARRAY_PAIRS;
+    const size_t np = (size_t)fr.W * fr.H;
+    std::vector<uint32_t> size(comp_size ? np * (per_group ? fr.refs.size() : fr.ap.size()) : 0);
+    auto depth = detail::arrayDepth(fr, cameras, pairs.size(), per_group, maps,
+                                    [&](double f, double pixel_size, double* depth, uint16_t* all) {
+        m.check(fr.call(sva_array_depth_filtered, m.handle(), route,
+                        unit.empty() ? (const double*)nullptr : (const double*)unit.data(), f,
+                        pixel_size, uniqueness, mode, depth, (uint8_t*)nullptr, (uint8_t*)nullptr,
+                        (float*)nullptr, all, (uint16_t*)nullptr, (uint16_t*)nullptr,
+                        (const int32_t*)vs.data(), sub ? 1 : 0, max_diff, min_agree, max_conflict,
+                        (uint8_t*)nullptr, (uint8_t*)nullptr, check ? 1 : 0, speckle_max_size,
+                        speckle_max_diff, comp_size ? size.data() : (uint32_t*)nullptr));
+    });
+    if (comp_size && per_group) *comp_size = fr.split(size);
+    else if (comp_size) fr.scatter(size, pairs.size(), comp_size);
+    return depth;
+}
+
 
 // ---- refinement and 3-D output ----
 // The reference's names and argument meaning; cv::Mat becomes ImageView (u8)

@@ -74,7 +74,8 @@ EXPORTED = [
     "sva_array_depth_mixed", "sva_frame_layout_of", "sva_paths_frame_d", "sva_wta_frame_d",
     "sva_fuse_depth_sub", "sva_fuse_depth_sub_d", "sva_fuse_depth_conf_sub",
     "sva_fuse_depth_conf_sub_d", "sva_array_depth_sub", "sva_cross_check", "sva_cross_check_d",
-    "sva_array_depth_checked",
+    "sva_array_depth_checked", "sva_filter_speckles", "sva_filter_speckles_d",
+    "sva_array_depth_filtered",
 ]
 SVA_FUSE_MIN_COST = 0
 SVA_FUSE_MAX_MARGIN = 1
@@ -297,6 +298,13 @@ def _load() -> ct.CDLL:
         "sva_array_depth_checked": (i32, [vp, P(vp), i32, i32, i32, sz, P(ArrayPair), i32, P(i32),
                                           i32, i32, P(dbl), dbl, dbl, i32, i32, vp, vp, vp, vp, vp,
                                           vp, vp, P(ct.c_int32), i32, i32, i32, i32, vp, vp]),
+        "sva_filter_speckles_d": (i32, [vp, vp, vp, i32, i32, i32, ct.c_uint16, i32, i32, vp, vp,
+                                        vp]),
+        "sva_filter_speckles": (i32, [vp, vp, vp, i32, i32, i32, ct.c_uint16, i32, i32, vp, vp, vp]),
+        "sva_array_depth_filtered": (i32, [vp, P(vp), i32, i32, i32, sz, P(ArrayPair), i32, P(i32),
+                                           i32, i32, P(dbl), dbl, dbl, i32, i32, vp, vp, vp, vp, vp,
+                                           vp, vp, P(ct.c_int32), i32, i32, i32, i32, vp, vp, i32,
+                                           i32, i32, vp]),
         "sva_resize_linear_f64_d": (i32, [vp, vp, i32, i32, vp, i32, i32]),
         "sva_resize_linear_f64": (i32, [vp, vp, i32, i32, vp, i32, i32]),
         "sva_ref_error_d": (i32, [vp, vp, i32, i32, vp, i32, i32, ct.c_double, vp]),
@@ -953,6 +961,30 @@ class Context:
                                         int(min_agree), int(max_conflict), _ptr(out),
                                         _ptr(out_sub), _ptr(agree), _ptr(conflict)))
 
+    def filter_speckles(self, disps: np.ndarray, max_size, max_diff, subpix=None, invalid=0xFFFF,
+                        want_size=True):
+        """(out, out_sub or None, comp_size or None): sva_filter_speckles, the
+        speckle filter of n maps [n][H][W] u16.  A valid pixel
+        whose 4-connected component (neighbours within max_diff) has at most
+        max_size pixels becomes `invalid`; out_sub (with subpix) is NaN there."""
+        d = np.ascontiguousarray(disps, dtype=np.uint16)
+        s = None if subpix is None else np.ascontiguousarray(subpix, dtype=np.float32)
+        N, H, W = d.shape
+        assert s is None or s.shape == d.shape
+        out = np.zeros_like(d)
+        osub = None if s is None else np.zeros_like(s)
+        size = np.zeros(d.shape, np.uint32) if want_size else None
+        self._chk(lib.sva_filter_speckles(self.h, _ptr(d), _ptr(s), N, W, H, invalid, int(max_size),
+                                          int(max_diff), _ptr(out), _ptr(osub), _ptr(size)))
+        return out, osub, size
+
+    def filter_speckles_d(self, disps, subpix, n_maps, W, H, invalid, max_size, max_diff, out,
+                          out_sub=None, comp_size=None):
+        """sva_filter_speckles_d on device pointers; out may be disps and out_sub subpix."""
+        self._chk(lib.sva_filter_speckles_d(self.h, _ptr(disps), _ptr(subpix), n_maps, W, H, invalid,
+                                            int(max_size), int(max_diff), _ptr(out), _ptr(out_sub),
+                                            _ptr(comp_size)))
+
     def disparity_to_depth(self, disp: np.ndarray, cam_distance, f, pixel_size):
         d = np.ascontiguousarray(disp, dtype=np.uint8)
         out = np.zeros(d.shape, np.float64)
@@ -1160,6 +1192,41 @@ class Multi:
             _ptr(depth), None, None, _ptr(subp), _ptr(maps), _ptr(cmin), _ptr(csec), vs, int(sub),
             int(max_diff), int(min_agree), int(max_conflict), _ptr(ag), _ptr(cf)))
         return depth, subp, maps, cmin, csec, ag, cf
+
+    def array_depth_filtered(self, images, pairs, group_start, f, pixel_size, speckle_max_size,
+                             speckle_max_diff, check=0, view_step=None, route=SVA_ARRAY_GROUPS,
+                             unit_baseline=None, uniqueness=0, mode=SVA_FUSE_MEDIAN, sub=0,
+                             max_diff=1, min_agree=1, max_conflict=0, want_sub=False,
+                             want_maps=False, want_costs=False, want_counts=False, want_size=False,
+                             want_n_valid=False, want_winner=False):
+        """sva_array_depth_filtered: the array frame with the speckle filter
+         over every job's map before depth -- after the
+        cross-view check with check = 1 (group routes), alone with check = 0 (every
+        route; on SVA_ARRAY_PAIRS `mode` fuses each group's filtered maps).
+        Returns a dict: depth [G,H,W] f64, and where asked for n_valid, winner
+        [G,H,W] u8, subpix f32, maps, cost_min, cost_second u16, comp_size u32
+        [jobs,H,W], agree, conflict [G,H,W] u8; None where not."""
+        fr = _ArrayFrame(images, pairs, group_start)
+        nj = len(pairs) if int(route) == SVA_ARRAY_PAIRS else fr.G
+        ub = None if unit_baseline is None else \
+            (ct.c_double * max(1, len(unit_baseline)))(*[float(v) for v in unit_baseline])
+        vs = None if view_step is None else _steps(view_step, len(view_step))
+        r = dict(depth=fr.planes(fr.G, np.float64),
+                 n_valid=fr.planes(fr.G, np.uint8, want_n_valid),
+                 winner=fr.planes(fr.G, np.uint8, want_winner),
+                 subpix=fr.planes(nj, np.float32, want_sub), maps=fr.planes(nj, np.uint16, want_maps),
+                 cost_min=fr.planes(nj, np.uint16, want_costs),
+                 cost_second=fr.planes(nj, np.uint16, want_costs),
+                 agree=fr.planes(fr.G, np.uint8, want_counts),
+                 conflict=fr.planes(fr.G, np.uint8, want_counts),
+                 comp_size=fr.planes(nj, np.uint32, want_size))
+        self._chk(lib.sva_array_depth_filtered(
+            self.h, *fr.head, int(route), ub, f, pixel_size, int(uniqueness), int(mode),
+            _ptr(r["depth"]), _ptr(r["n_valid"]), _ptr(r["winner"]), _ptr(r["subpix"]),
+            _ptr(r["maps"]), _ptr(r["cost_min"]), _ptr(r["cost_second"]), vs, int(sub),
+            int(max_diff), int(min_agree), int(max_conflict), _ptr(r["agree"]), _ptr(r["conflict"]),
+            int(check), int(speckle_max_size), int(speckle_max_diff), _ptr(r["comp_size"])))
+        return r
 
     def array_depth(self, images, pairs, group_start, f, pixel_size, want_maps=False):
         """images: list of HxW u8 numpy views; pairs: list of (ref, other,

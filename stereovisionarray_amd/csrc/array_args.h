@@ -1,9 +1,9 @@
 // array_args.h -- the arguments of one camera-array frame (sva_array_depth,
-// _conf, _mb, _mixed, _sub and _checked) and their validation,
-// shared by multi.cpp and the host test programs (tests/test_array_args_cpu.py,
-// tests/test_array_sub_args_cpu.py and tests/test_cross_check_cpu.py compile
-// this header with a C++ compiler under the sanitizers).  Plain C++: no HIP
-// header.
+// _conf, _mb, _mixed, _sub, _checked and _filtered) and their
+// validation, shared by multi.cpp and the host test programs
+// (tests/test_array_args_cpu.py, tests/test_array_sub_args_cpu.py,
+// tests/test_cross_check_cpu.py and tests/test_speckle_cpu.py compile this
+// header with a C++ compiler under the sanitizers).  Plain C++: no HIP header.
 #pragma once
 
 #include <algorithm>
@@ -15,6 +15,7 @@
 
 #include "cost_mixed_math.h"
 #include "cross_check_math.h"
+#include "speckle_math.h"
 #include "sva.h"
 #include "sva_native_d.h"
 
@@ -65,6 +66,13 @@ struct ArrayArgs {
     const int32_t* view_step = nullptr;       // [n_images][2], unit baselines
     int max_diff = 0, min_agree = 0, max_conflict = 0;
     uint8_t *agree = nullptr, *conflict = nullptr;   // host, per group, nullable
+    // speckle (sva_array_depth_filtered): the jobs' maps go
+    // through sva_filter_speckles_d in place, after the check (check = 1: cross
+    // is set too) and before depth; every route
+    bool speckle = false;
+    int check = 0;                            // the entry's `check`, as given
+    int speckle_max_size = 0, speckle_max_diff = 0;
+    uint32_t* comp_size = nullptr;            // host, per job, nullable
 };
 
 inline int check_params(const sva_sgm_params& p) {
@@ -103,7 +111,7 @@ inline bool baseline_ratio(double baseline, double unit, int32_t* num, int32_t* 
 // view_step (components, then duplicates) and on max_diff, min_agree,
 // max_conflict.  (The entry itself refuses a `sub` outside 0 / 1 before it
 // builds these arguments: ArrayArgs::sub is a bool.)
-inline int check_array_args(const ArrayArgs& a, std::string& msg, std::vector<int32_t>& ratio) {
+inline int check_frame_args(const ArrayArgs& a, std::string& msg, std::vector<int32_t>& ratio) {
     auto fail = [&](int code, const std::string& m) {
         msg = m;
         return code;
@@ -119,7 +127,7 @@ inline int check_array_args(const ArrayArgs& a, std::string& msg, std::vector<in
         if (a.winner && a.mode == SVA_FUSE_MEDIAN)
             return fail(SVA_ERR_INVALID_ARG, "the median has no winner map");
     }
-    if (a.sub || a.cross) {
+    if (a.sub || a.cross || a.speckle) {
         // the entry takes every route's arguments: those of another route are refused
         if (group && a.mode != SVA_FUSE_MEDIAN)
             return fail(SVA_ERR_INVALID_ARG, "the group routes fuse one map: SVA_FUSE_MEDIAN only");
@@ -237,6 +245,27 @@ inline int check_array_args(const ArrayArgs& a, std::string& msg, std::vector<in
     if (!m) m = cc::step_distinct_error(vs.data(), a.n_groups);
     if (!m) m = cc::thresholds_error(a.max_diff, a.min_agree, a.max_conflict);
     if (m) return fail(SVA_ERR_INVALID_ARG, m);
+    return SVA_OK;
+}
+
+// check_frame_args, and with a.speckle (sva_array_depth_filtered) after all of
+// its rules -- those of a.cross among them, which the entry sets iff check == 1
+// -- in this order: a check outside 0 / 1; with check = 0, an agree or conflict
+// plane, then a subpix plane without sub; speckle_max_size < 0;
+// speckle_max_diff < 0.
+inline int check_array_args(const ArrayArgs& a, std::string& msg, std::vector<int32_t>& ratio) {
+    if (int st = check_frame_args(a, msg, ratio)) return st;
+    if (!a.speckle) return SVA_OK;
+    auto fail = [&](const char* m) {
+        msg = m;
+        return (int)SVA_ERR_INVALID_ARG;
+    };
+    if (a.check != 0 && a.check != 1) return fail("check must be 0 or 1");
+    if (a.check == 0 && (a.agree || a.conflict))
+        return fail("agree and conflict need check = 1");
+    if (a.check == 0 && !a.sub && a.subpix) return fail("subpix needs sub = 1");
+    if (const char* m = sp::thresholds_error(a.speckle_max_size, a.speckle_max_diff))
+        return fail(m);
     return SVA_OK;
 }
 

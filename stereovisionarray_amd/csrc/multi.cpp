@@ -12,7 +12,7 @@
 // through the public per-context entry points (sva_disparity_sgm_d,
 // sva_fuse_depth_d, and sva_disparity_sgm_conf_d / sva_fuse_depth_conf_d for
 // the confidence forms, whose cost planes are gathered like the maps); there
-// is no CPU path.  The six sva_array_depth* entry points fill one ArrayArgs
+// is no CPU path.  The seven sva_array_depth* entry points fill one ArrayArgs
 // (array_args.h: the arguments and their checks, in one order) and run one
 // array_frame(): its jobs are pairs, or -- sva_array_depth_mb -- GROUPS (one
 // sva_disparity_sgm_multi_d per reference camera, DESIGN.md §2.2c;
@@ -120,6 +120,7 @@ struct Multi {
     DevBuf conf0, winner0;             // device 0: cost planes, winners (sva_array_depth_conf)
     DevBuf sub0;                       // device 0: f32 sub-pixel maps (sva_array_depth_sub)
     DevBuf cross0;                     // device 0: the checked planes (sva_array_depth_checked)
+    DevBuf speckle0;                   // device 0: comp_size planes (sva_array_depth_filtered)
     PinnedBuf stage_in, stage_out;
     Rccl rccl;
     std::vector<ncclComm_t> comms;
@@ -644,6 +645,7 @@ int sva_multi_destroy(void* mp) {
         m->winner0.release();
         m->sub0.release();
         m->cross0.release();
+        m->speckle0.release();
     }
     m->stage_in.release();
     m->stage_out.release();
@@ -815,7 +817,7 @@ struct Download {
     }
 };
 
-// One camera-array frame: sva_array_depth, _conf, _mb, _mixed, _sub and _checked (array_args.h
+// One camera-array frame: sva_array_depth, _conf, _mb, _mixed, _sub, _checked and _filtered (array_args.h
 // has their arguments and checks).  A job is a pair (ArrayRoute::Pairs: every
 // pair through sva_disparity_sgm_d or, with conf, sva_disparity_sgm_conf_d; a
 // group's maps are fused by `mode`) or a GROUP (group g's
@@ -826,7 +828,8 @@ struct Download {
 // map, gathered into sub0 like the u16 one, and depth is fused from those.
 // With a.cross (sva_array_depth_checked, §2.5b) the groups' maps pass through
 // sva_cross_check_d on device 0 before step 4, which then reads the checked
-// planes.
+// planes.  With a.speckle (sva_array_depth_filtered, §2.5c) every job's map --
+// checked or not -- then passes through sva_filter_speckles_d in place.
 int array_frame(void* mp, const ArrayArgs& a) {
     Multi* m = as_multi(mp);
     if (!m) return SVA_ERR_INVALID_ARG;
@@ -942,6 +945,26 @@ int array_frame(void* mp, const ArrayArgs& a) {
         maps0 = cmaps;
         sub0 = csub;
     }
+    // 3c. the speckle filter, in place on the maps step 4 reads: one call per run
+    // of jobs that share `invalid` (a pair route's groups may differ in it)
+    uint32_t* size0 = nullptr;
+    if (a.speckle) {
+        MHIP(m, hipSetDevice(m->devices[0]), "hipSetDevice");
+        if (a.comp_size) {
+            MHIP(m, m->speckle0.ensure(plane * 2), "speckle workspace");
+            size0 = (uint32_t*)m->speckle0.ptr;
+        }
+        for (int k = 0, k1; k < n_jobs; k = k1) {
+            const uint16_t inv = pairs[first[k]].params.invalid;
+            for (k1 = k + 1; k1 < n_jobs && pairs[first[k1]].params.invalid == inv;) k1++;
+            const size_t o = (size_t)k * np;
+            float* sk = sub0 ? sub0 + o : nullptr;
+            st = sva_filter_speckles_d(m->ctx[0], maps0 + o, sk, k1 - k, W, H, inv,
+                                       a.speckle_max_size, a.speckle_max_diff, maps0 + o, sk,
+                                       size0 ? size0 + o : nullptr);
+            if (st) return m->ctx_fail(st, m->ctx[0], "speckle filter");
+        }
+    }
     // 4. depth per group on device 0 -- the fusion of its pairs' maps, or the
     // depth of its one map (the median of one is the map's own depth) -- each
     // group's download as soon as it is done, the per-job planes at the end
@@ -962,6 +985,7 @@ int array_frame(void* mp, const ArrayArgs& a) {
     dl.add(n_groups, cp.cost_second, a.cost_second, plane);
     dl.add(n_groups, agree0, a.agree, np * n_groups);
     dl.add(n_groups, conflict0, a.conflict, np * n_groups);
+    dl.add(n_groups, size0, a.comp_size, plane * 2);
     MHIP(m, m->stage_out.ensure(dl.total), "pinned staging");
     std::vector<double> bases(n_pairs);
     for (int j = 0; j < n_pairs; j++) bases[j] = pairs[j].baseline;
@@ -1000,7 +1024,7 @@ int array_frame(void* mp, const ArrayArgs& a) {
     return dl.finish(m);
 }
 
-// What the six entry points share; as it stands, sva_array_depth's: the pair
+// What the seven entry points share; as it stands, sva_array_depth's: the pair
 // route, plain matching, median fusion.
 ArrayArgs frame_args(const uint8_t* const* images, int n_images, int W, int H, size_t pitch,
                      const sva_array_pair* pairs, int n_pairs, const int32_t* group_start,
@@ -1142,6 +1166,47 @@ int sva_array_depth_checked(void* mp, const uint8_t* const* images, int n_images
     a.max_conflict = max_conflict;
     a.agree = agree;
     a.conflict = conflict;
+    return array_frame(mp, a);
+}
+
+int sva_array_depth_filtered(void* mp, const uint8_t* const* images, int n_images, int W, int H,
+                             size_t pitch, const sva_array_pair* pairs, int n_pairs,
+                             const int32_t* group_start, int n_groups, int route,
+                             const double* unit_baseline, double f, double pixel_size,
+                             int uniqueness, int mode, double* depth, uint8_t* n_valid,
+                             uint8_t* winner, float* subpix, uint16_t* maps, uint16_t* cost_min,
+                             uint16_t* cost_second, const int32_t* view_step, int sub,
+                             int max_diff, int min_agree, int max_conflict, uint8_t* agree,
+                             uint8_t* conflict, int check, int speckle_max_size,
+                             int speckle_max_diff, uint32_t* comp_size) {
+    if (sub != 0 && sub != 1) {
+        Multi* m = as_multi(mp);
+        return m ? m->fail(SVA_ERR_INVALID_ARG, "sub must be 0 or 1") : SVA_ERR_INVALID_ARG;
+    }
+    ArrayArgs a = frame_args(images, n_images, W, H, pitch, pairs, n_pairs, group_start, n_groups,
+                             f, pixel_size, uniqueness, depth, maps, cost_min, cost_second);
+    a.route = array_route_of(route);
+    a.conf = true;
+    a.sub = sub != 0;
+    a.mode = mode;
+    a.unit_baseline = unit_baseline;
+    a.n_valid = n_valid;
+    a.winner = winner;
+    a.subpix = subpix;
+    a.cross = check == 1;
+    if (a.cross) {   // check = 0 ignores the check's arguments
+        a.view_step = view_step;
+        a.max_diff = max_diff;
+        a.min_agree = min_agree;
+        a.max_conflict = max_conflict;
+    }
+    a.agree = agree;
+    a.conflict = conflict;
+    a.speckle = true;
+    a.check = check;
+    a.speckle_max_size = speckle_max_size;
+    a.speckle_max_diff = speckle_max_diff;
+    a.comp_size = comp_size;
     return array_frame(mp, a);
 }
 

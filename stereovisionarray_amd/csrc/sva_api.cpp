@@ -17,6 +17,7 @@
 
 #include "cost_mixed_math.h"
 #include "cross_check_math.h"
+#include "speckle_math.h"
 #include "sva_internal.h"
 #include "sva_tuning.h"
 
@@ -691,7 +692,7 @@ int sva_destroy(void* ctx) {
     c->census_side.release();
     for (DevBuf* b : {&c->census_l, &c->census_r, &c->cost, &c->paths, &c->ckpt, &c->scratch_u16,
                       &c->disp_r, &c->in_a, &c->in_b, &c->in_mask, &c->out_a, &c->out_b,
-                      &c->out_c, &c->in_c, &c->shifted, &c->keys, &c->counts, &c->total, &c->ref_keys, &c->refine_ws})
+                      &c->out_c, &c->in_c, &c->shifted, &c->keys, &c->counts, &c->total, &c->ref_keys, &c->refine_ws, &c->speckle_ws})
         b->release();
     c->timer.release_all();
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
@@ -1912,6 +1913,101 @@ int sva_cross_check(void* ctx, const uint16_t* disps, const float* subpix, int n
     g.down(out_sub, dsub, nnp * 4);
     g.down(agree, dag, nnp);
     g.down(conflict, dcf, nnp);
+    return g.sync();
+}
+
+// ------------------------------------------- speckle filter --
+namespace {
+// a and b may be the same plane (in place), and nothing else
+bool bad_overlap(const void* a, const void* b, size_t nb_each) {
+    return a != b && ranges_overlap(a, nb_each, b, nb_each);
+}
+
+// The rules of sva_filter_speckles and sva_filter_speckles_d, in sva.h's order;
+// the pointers are the caller's (host or device), which is where overlap matters.
+int check_speckle(Ctx* c, const uint16_t* disps, const float* subpix, int n, int W, int H,
+                  int max_size, int max_diff, const uint16_t* out, const float* out_sub,
+                  const uint32_t* comp_size) {
+    if (!disps || !out) return fail(c, SVA_ERR_INVALID_ARG, "null pointer");
+    if (n < 1) return fail(c, SVA_ERR_INVALID_ARG, "n_maps must be >= 1");
+    if (W <= 0 || H <= 0) return fail(c, SVA_ERR_INVALID_ARG, "image size must be positive");
+    if ((unsigned long long)W * (unsigned long long)H >= (1ull << 31))
+        return fail(c, SVA_ERR_UNSUPPORTED, "the speckle filter needs W * H < 2^31");
+    if (const char* m = sp::thresholds_error(max_size, max_diff))
+        return fail(c, SVA_ERR_INVALID_ARG, m);
+    if (out_sub && !subpix) return fail(c, SVA_ERR_INVALID_ARG, "out_sub needs subpix");
+    // the byte counts saturate: a frame too large for the address space overlaps everything
+    const unsigned long long px = (unsigned long long)W * H;
+    const size_t lim = ~(size_t)0;
+    const size_t b16 = px > lim / 2 / (size_t)n ? lim : (size_t)px * 2 * (size_t)n;
+    const size_t b32 = b16 > lim / 2 ? lim : b16 * 2;
+    if ((out != disps && ranges_overlap(out, b16, disps, b16)) ||
+        ranges_overlap(out, b16, subpix, b32) || ranges_overlap(out, b16, out_sub, b32) ||
+        ranges_overlap(out, b16, comp_size, b32) || ranges_overlap(out_sub, b32, disps, b16) ||
+        bad_overlap(out_sub, subpix, b32) || ranges_overlap(out_sub, b32, comp_size, b32) ||
+        ranges_overlap(comp_size, b32, disps, b16) || ranges_overlap(comp_size, b32, subpix, b32))
+        return fail(c, SVA_ERR_INVALID_ARG,
+                    "an output overlaps an input or another output (in place: out == disps, "
+                    "out_sub == subpix)");
+    return SVA_OK;
+}
+
+// The workspace, then the launches.  max_size = 0 without comp_size is a copy
+// and takes no workspace.
+int run_speckle(Ctx* c, const uint16_t* disps, const float* subpix, int n, int W, int H,
+                uint16_t invalid, int max_size, int max_diff, uint16_t* out, float* out_sub,
+                uint32_t* comp_size) {
+    uint32_t *label = nullptr, *count = nullptr;
+    if (max_size != 0 || comp_size) {
+        const unsigned long long planes = (unsigned long long)W * H * (unsigned long long)n;
+        if (planes > (~(size_t)0) / 8)
+            return fail(c, SVA_ERR_OUT_OF_MEMORY, "speckle workspace: larger than the address space");
+        const hipError_t e = c->speckle_ws.ensure((size_t)planes * 8);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();   // the failed allocation is reported here, not by a later call
+            return fail(c, SVA_ERR_OUT_OF_MEMORY,
+                        std::string("speckle workspace: ") + hipGetErrorString(e));
+        }
+        label = (uint32_t*)c->speckle_ws.ptr;
+        count = label + planes;
+    }
+    SVA_HIP(c, launch_speckle(*c, disps, subpix, n, W, H, invalid, max_size, max_diff, label, count,
+                              out, out_sub, comp_size),
+            "speckle launch");
+    return SVA_OK;
+}
+}  // namespace
+
+int sva_filter_speckles_d(void* ctx, const uint16_t* disps, const float* subpix, int n, int W,
+                          int H, uint16_t invalid, int max_size, int max_diff, uint16_t* out,
+                          float* out_sub, uint32_t* comp_size) {
+    Ctx* c = as_ctx(ctx);
+    SVA_CHECK_CTX(c);
+    if (int s = check_speckle(c, disps, subpix, n, W, H, max_size, max_diff, out, out_sub, comp_size))
+        return s;
+    return run_speckle(c, disps, subpix, n, W, H, invalid, max_size, max_diff, out, out_sub,
+                       comp_size);
+}
+
+// On the device the staged maps are filtered in place.
+int sva_filter_speckles(void* ctx, const uint16_t* disps, const float* subpix, int n, int W, int H,
+                        uint16_t invalid, int max_size, int max_diff, uint16_t* out, float* out_sub,
+                        uint32_t* comp_size) {
+    Ctx* c = as_ctx(ctx);
+    SVA_CHECK_CTX(c);
+    if (int s = check_speckle(c, disps, subpix, n, W, H, max_size, max_diff, out, out_sub, comp_size))
+        return s;
+    const size_t nnp = (size_t)W * H * (size_t)n;
+    Staging g{c};
+    uint16_t* dd = g.up<uint16_t>(c->in_a, disps, nnp * 2);
+    float* ds = out_sub ? g.up<float>(c->in_mask, subpix, nnp * 4) : nullptr;
+    uint32_t* dsize = comp_size ? g.out<uint32_t>(c->out_c, nnp * 4) : nullptr;
+    if (g.st) return g.st;
+    if (int s = run_speckle(c, dd, ds, n, W, H, invalid, max_size, max_diff, dd, ds, dsize))
+        return s;
+    g.down(out, dd, nnp * 2);
+    g.down(out_sub, ds, nnp * 4);
+    g.down(comp_size, dsize, nnp * 4);
     return g.sync();
 }
 

@@ -70,6 +70,8 @@ struct Ctx {
     // SVA_DEBUG_CROSS_ORDER: cross_check's block order (-1 = tune::kCrossTileMajor,
     // 0 = view-major, 1 = tile-major)
     int dbg_cross_order = -1;
+    // the speckle filter's label and count planes (speckle.hip; sva.h gives the size)
+    DevBuf speckle_ws;
     // Mode R's split plane loop: one first-minimum key per pixel (refpath.hip).
     // ref_finalize_kernel puts every key it reads back to all-ones, so after
     // the first call only a grown buffer needs the memset: ref_keys_clean =
@@ -259,6 +261,13 @@ hipError_t launch_cross_check(Ctx& c, const uint16_t* disps, const float* subpix
                               int H, const int32_t* view_step, uint16_t invalid, int max_diff,
                               int min_agree, int max_conflict, int tile_major, uint16_t* out,
                               float* out_sub, uint8_t* agree, uint8_t* conflict);
+// speckle.hip -- the speckle filter: n maps [n][H][W], W * H <
+// 2^31; label, count: u32 workspace planes [n][H][W] (both null: max_size = 0
+// and no comp_size, a copy); subpix / out_sub (f32) and comp_size (u32)
+// nullable, out_sub needs subpix; out may be disps and out_sub subpix.
+hipError_t launch_speckle(Ctx& c, const uint16_t* disps, const float* subpix, int n, int W, int H,
+                          uint16_t invalid, int max_size, int max_diff, uint32_t* label,
+                          uint32_t* count, uint16_t* out, float* out_sub, uint32_t* comp_size);
 // refpath.hip
 hipError_t launch_ref_endpoints(Ctx& c, int W, int H, const sva_camera& cref,
                                 const sva_camera& coth, int k, double t_near, double t_far,

@@ -262,5 +262,24 @@ constexpr int kPlaneSplitRounds = 4;
 // Chosen on n = 25; one order for every n rather than a switch on n.
 constexpr int kCrossTileMajor = 1;
 
+// ---- speckle.hip -----------------------------------------
+// The label pass's tile: one workgroup of 256 threads resolves kSpeckleTileW x
+// kSpeckleTileH pixels in LDS (10 bytes of LDS per pixel).  A wide, flat tile
+// keeps the u16 row reads and the u32 row writes 128 bytes and more long.
+// One A/B, 64x16 against 32x32 (a library built by tools/build_variants.sh), each
+// in a process of its own in one session: tools/bench_speckle.py --kernel, 1080p
+// real maps, 15 calls, max_size 20, max_diff 1, u16 planes only, stream events
+// around the four launches (profiles/speckle/kernel_1080p*.json), ms median
+// (min-max), 64x16 / 32x32:
+// n = 25  2.177 (2.166-2.194) / 2.173 (2.106-2.205): no difference.  The square
+// tile's label pass is faster, 1.222 (1.214-1.229) / 1.105 (1.093-1.114), and
+// its merge pass -- 1.5x the border links -- slower by as much, 0.571
+// (0.555-0.582) / 0.688 (0.618-0.718).
+// n = 8   0.734 (0.722-0.752) / 0.700 (0.691-0.734): the spreads overlap.
+// n = 1   0.157 (0.154-0.162) / 0.149 (0.146-0.153): 32x32 ahead by 8 us, its
+// slowest call 0.2 us under the other's fastest.
+// No winner where the time is (n = 25), so the shape the layout argues for stays.
+constexpr int kSpeckleTileW = 64, kSpeckleTileH = 16;
+
 }  // namespace tune
 }  // namespace sva
