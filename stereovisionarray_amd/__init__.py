@@ -840,99 +840,75 @@ class Context:
         self._chk(lib.sva_masked_mean_d(self.h, _ptr(image), _ptr(mask), w, h, ct.byref(out)))
         return out.value
 
-    def fuse_depth(self, disps: np.ndarray, baselines, f, pixel_size, invalid=0xFFFF):
+    def _fuse_d(self, fn, planes, n_maps, W, H, baselines, f, pixel_size, invalid, mode, outs):
+        """One sva_fuse_depth* call: planes and outs (arrays, pointers or None) in
+        that entry's order; mode None for a median entry, which takes none."""
+        b = (ct.c_double * max(1, n_maps))(*[float(v) for v in baselines])
+        self._chk(fn(self.h, *map(_ptr, planes), n_maps, W, H, b, f, pixel_size, invalid,
+                     *([] if mode is None else [int(mode)]), *map(_ptr, outs)))
+
+    def _fuse(self, fn, disps, planes, baselines, f, pixel_size, invalid, mode, want):
+        """The host-array form: planes, (array or None, dtype) pairs shaped as
+        disps, follow it in the call; want: whether n_valid (and winner) are
+        asked for.  Returns (depth, n_valid[, winner]), None where not wanted."""
         d = np.ascontiguousarray(disps, dtype=np.uint16)
         N, H, W = d.shape
-        b = (ct.c_double * N)(*[float(v) for v in baselines])
-        out = np.zeros((H, W), np.float64)
-        nv = np.zeros((H, W), np.uint8)
-        self._chk(lib.sva_fuse_depth(self.h, _ptr(d), N, W, H, b, f, pixel_size, invalid,
-                                     _ptr(out), _ptr(nv)))
-        return out, nv
+        ins = [d] + [None if x is None else np.ascontiguousarray(x, dtype=t) for x, t in planes]
+        assert all(x is None or x.shape == d.shape for x in ins)
+        outs = [np.zeros((H, W), np.float64)]
+        outs += [np.zeros((H, W), np.uint8) if w else None for w in want]
+        self._fuse_d(fn, ins, N, W, H, baselines, f, pixel_size, invalid, mode, outs)
+        return tuple(outs)
+
+    def fuse_depth(self, disps: np.ndarray, baselines, f, pixel_size, invalid=0xFFFF):
+        return self._fuse(lib.sva_fuse_depth, disps, [], baselines, f, pixel_size, invalid, None,
+                          [True])
 
     def fuse_depth_d(self, disps, n_maps, W, H, baselines, f, pixel_size, invalid, depth,
                      n_valid=None):
-        b = (ct.c_double * n_maps)(*[float(v) for v in baselines])
-        self._chk(lib.sva_fuse_depth_d(self.h, _ptr(disps), n_maps, W, H, b, f, pixel_size,
-                                       invalid, _ptr(depth), _ptr(n_valid)))
+        self._fuse_d(lib.sva_fuse_depth_d, [disps], n_maps, W, H, baselines, f, pixel_size,
+                     invalid, None, [depth, n_valid])
 
     def fuse_depth_conf(self, disps: np.ndarray, cost_min: np.ndarray, cost_second, baselines,
                         f, pixel_size, invalid=0xFFFF, mode=SVA_FUSE_MIN_COST):
         """(depth, n_valid, winner): sva_fuse_depth_conf, the depth of the valid
         map with the smallest cost_min (SVA_FUSE_MIN_COST; cost_second may be
         None) or the largest cost_second - cost_min (SVA_FUSE_MAX_MARGIN)."""
-        d = np.ascontiguousarray(disps, dtype=np.uint16)
-        cm = np.ascontiguousarray(cost_min, dtype=np.uint16)
-        cs = None if cost_second is None else np.ascontiguousarray(cost_second, dtype=np.uint16)
-        N, H, W = d.shape
-        assert cm.shape == d.shape and (cs is None or cs.shape == d.shape)
-        b = (ct.c_double * max(1, N))(*[float(v) for v in baselines])
-        out = np.zeros((H, W), np.float64)
-        nv = np.zeros((H, W), np.uint8)
-        win = np.zeros((H, W), np.uint8)
-        self._chk(lib.sva_fuse_depth_conf(self.h, _ptr(d), _ptr(cm), _ptr(cs), N, W, H, b, f,
-                                          pixel_size, invalid, int(mode), _ptr(out), _ptr(nv),
-                                          _ptr(win)))
-        return out, nv, win
+        return self._fuse(lib.sva_fuse_depth_conf, disps,
+                          [(cost_min, np.uint16), (cost_second, np.uint16)], baselines, f,
+                          pixel_size, invalid, mode, [True, True])
 
     def fuse_depth_conf_d(self, disps, cost_min, cost_second, n_maps, W, H, baselines, f,
                           pixel_size, invalid, mode, depth, n_valid=None, winner=None):
-        b = (ct.c_double * max(1, n_maps))(*[float(v) for v in baselines])
-        self._chk(lib.sva_fuse_depth_conf_d(self.h, _ptr(disps), _ptr(cost_min),
-                                            _ptr(cost_second), n_maps, W, H, b, f, pixel_size,
-                                            invalid, int(mode), _ptr(depth), _ptr(n_valid),
-                                            _ptr(winner)))
+        self._fuse_d(lib.sva_fuse_depth_conf_d, [disps, cost_min, cost_second], n_maps, W, H,
+                     baselines, f, pixel_size, invalid, mode, [depth, n_valid, winner])
 
     def fuse_depth_sub(self, disps: np.ndarray, subpix, baselines, f, pixel_size,
                        invalid=0xFFFF, want_n_valid=True):
         """(depth, n_valid or None): sva_fuse_depth_sub, the median of the depths
         of the f32 sub-pixel maps (a map counts where its u16 disparity is valid
         and subpix > 0).  subpix None: the NULL pointer the call refuses."""
-        d = np.ascontiguousarray(disps, dtype=np.uint16)
-        s = None if subpix is None else np.ascontiguousarray(subpix, dtype=np.float32)
-        N, H, W = d.shape
-        assert s is None or s.shape == d.shape
-        b = (ct.c_double * max(1, N))(*[float(v) for v in baselines])
-        out = np.zeros((H, W), np.float64)
-        nv = np.zeros((H, W), np.uint8) if want_n_valid else None
-        self._chk(lib.sva_fuse_depth_sub(self.h, _ptr(d), _ptr(s), N, W, H, b, f, pixel_size,
-                                         invalid, _ptr(out), _ptr(nv)))
-        return out, nv
+        return self._fuse(lib.sva_fuse_depth_sub, disps, [(subpix, np.float32)], baselines, f,
+                          pixel_size, invalid, None, [want_n_valid])
 
     def fuse_depth_sub_d(self, disps, subpix, n_maps, W, H, baselines, f, pixel_size, invalid,
                          depth, n_valid=None):
-        b = (ct.c_double * max(1, n_maps))(*[float(v) for v in baselines])
-        self._chk(lib.sva_fuse_depth_sub_d(self.h, _ptr(disps), _ptr(subpix), n_maps, W, H, b, f,
-                                           pixel_size, invalid, _ptr(depth), _ptr(n_valid)))
+        self._fuse_d(lib.sva_fuse_depth_sub_d, [disps, subpix], n_maps, W, H, baselines, f,
+                     pixel_size, invalid, None, [depth, n_valid])
 
     def fuse_depth_conf_sub(self, disps: np.ndarray, subpix, cost_min: np.ndarray, cost_second,
                             baselines, f, pixel_size, invalid=0xFFFF, mode=SVA_FUSE_MIN_COST,
                             want_n_valid=True, want_winner=True):
         """(depth, n_valid, winner): sva_fuse_depth_conf_sub, fuse_depth_conf with
         the winner's depth taken from its f32 sub-pixel map."""
-        d = np.ascontiguousarray(disps, dtype=np.uint16)
-        s = None if subpix is None else np.ascontiguousarray(subpix, dtype=np.float32)
-        cm = np.ascontiguousarray(cost_min, dtype=np.uint16)
-        cs = None if cost_second is None else np.ascontiguousarray(cost_second, dtype=np.uint16)
-        N, H, W = d.shape
-        assert cm.shape == d.shape and (cs is None or cs.shape == d.shape)
-        assert s is None or s.shape == d.shape
-        b = (ct.c_double * max(1, N))(*[float(v) for v in baselines])
-        out = np.zeros((H, W), np.float64)
-        nv = np.zeros((H, W), np.uint8) if want_n_valid else None
-        win = np.zeros((H, W), np.uint8) if want_winner else None
-        self._chk(lib.sva_fuse_depth_conf_sub(self.h, _ptr(d), _ptr(s), _ptr(cm), _ptr(cs), N, W, H,
-                                              b, f, pixel_size, invalid, int(mode), _ptr(out),
-                                              _ptr(nv), _ptr(win)))
-        return out, nv, win
+        return self._fuse(lib.sva_fuse_depth_conf_sub, disps,
+                          [(subpix, np.float32), (cost_min, np.uint16), (cost_second, np.uint16)],
+                          baselines, f, pixel_size, invalid, mode, [want_n_valid, want_winner])
 
     def fuse_depth_conf_sub_d(self, disps, subpix, cost_min, cost_second, n_maps, W, H, baselines,
                               f, pixel_size, invalid, mode, depth, n_valid=None, winner=None):
-        b = (ct.c_double * max(1, n_maps))(*[float(v) for v in baselines])
-        self._chk(lib.sva_fuse_depth_conf_sub_d(self.h, _ptr(disps), _ptr(subpix), _ptr(cost_min),
-                                                _ptr(cost_second), n_maps, W, H, b, f, pixel_size,
-                                                invalid, int(mode), _ptr(depth), _ptr(n_valid),
-                                                _ptr(winner)))
+        self._fuse_d(lib.sva_fuse_depth_conf_sub_d, [disps, subpix, cost_min, cost_second], n_maps,
+                     W, H, baselines, f, pixel_size, invalid, mode, [depth, n_valid, winner])
 
     def cross_check(self, disps: np.ndarray, view_step, subpix=None, invalid=0xFFFF, max_diff=1,
                     min_agree=1, max_conflict=0, want_agree=True, want_conflict=True):

@@ -1654,153 +1654,132 @@ int sva_disparity_to_depth(void* ctx, const uint8_t* disp, int n, double cam_dis
 }
 
 namespace {
-int check_fuse(Ctx* c, const uint16_t* disps, int n_maps, int W, int H, const double* b,
-               const double* depth) {
-    if (!disps || !b || !depth) return fail(c, SVA_ERR_INVALID_ARG, "null pointer");
-    if (n_maps < 1 || n_maps > 32) return fail(c, SVA_ERR_UNSUPPORTED, "n_maps must be 1..32");
-    if (W <= 0 || H <= 0) return fail(c, SVA_ERR_INVALID_ARG, "image size must be positive");
-    return SVA_OK;
-}
+// One fusion call: the planes are all on the host
+// or all on the device.  subpix: the sub-pixel forms; cost_min, cost_second and
+// winner: the cost-aware ones.
+struct FuseArgs {
+    const uint16_t* disps;
+    const float* subpix;
+    const uint16_t *cost_min, *cost_second;
+    int n_maps, W, H;
+    const double* baselines;
+    double f, pixel_size;
+    uint16_t invalid;
+    int mode;   // SVA_FUSE_MEDIAN from the median entries
+    double* depth;
+    uint8_t *n_valid, *winner;
+};
 
-// Cost-aware fusion.
-int check_fuse_conf(Ctx* c, const uint16_t* disps, const uint16_t* cost_min,
-                    const uint16_t* cost_second, int n_maps, int W, int H, const double* b,
-                    int mode, const double* depth) {
-    if (!disps || !cost_min || !b || !depth) return fail(c, SVA_ERR_INVALID_ARG, "null pointer");
-    if (mode != SVA_FUSE_MIN_COST && mode != SVA_FUSE_MAX_MARGIN)
+// The rules of the eight entries, in sva.h's order.  by_cost: a cost-aware entry,
+// which takes its mode from the caller and refuses SVA_FUSE_MEDIAN; sub: a
+// sub-pixel entry, whose own rule comes after those of its u16 form.
+int check_fuse(Ctx* c, const FuseArgs& a, bool by_cost, bool sub) {
+    if (!a.disps || (by_cost && !a.cost_min) || !a.baselines || !a.depth)
+        return fail(c, SVA_ERR_INVALID_ARG, "null pointer");
+    if (by_cost && a.mode != SVA_FUSE_MIN_COST && a.mode != SVA_FUSE_MAX_MARGIN)
         return fail(c, SVA_ERR_INVALID_ARG, "mode must be SVA_FUSE_MIN_COST or SVA_FUSE_MAX_MARGIN");
-    if (mode == SVA_FUSE_MAX_MARGIN && !cost_second)
+    if (by_cost && a.mode == SVA_FUSE_MAX_MARGIN && !a.cost_second)
         return fail(c, SVA_ERR_INVALID_ARG, "SVA_FUSE_MAX_MARGIN needs the cost_second planes");
-    if (n_maps < 1 || n_maps > 32) return fail(c, SVA_ERR_INVALID_ARG, "n_maps must be 1..32");
-    if (W <= 0 || H <= 0) return fail(c, SVA_ERR_INVALID_ARG, "image size must be positive");
+    if (a.n_maps < 1 || a.n_maps > 32)
+        return fail(c, by_cost ? SVA_ERR_INVALID_ARG : SVA_ERR_UNSUPPORTED, "n_maps must be 1..32");
+    if (a.W <= 0 || a.H <= 0) return fail(c, SVA_ERR_INVALID_ARG, "image size must be positive");
+    if (sub && !a.subpix) return fail(c, SVA_ERR_INVALID_ARG, "null subpix");
     return SVA_OK;
 }
 
-// Both fusions on device planes: the median (mode < 0; cost planes and winner
-// unused) and the cost-aware ones.  subpix non-null: the sub-pixel forms of
-// §2.6c, which read it next to disps.
-int run_fuse(Ctx* c, const uint16_t* disps, const float* subpix, const uint16_t* cost_min,
-             const uint16_t* cost_second, int n_maps, size_t np, const double* baselines, double f,
-             double pixel_size, uint16_t invalid, int mode, double* depth, uint8_t* n_valid,
-             uint8_t* winner) {
+// A checked call on device planes.
+int run_fuse(Ctx* c, const FuseArgs& a) {
     double num[32];
-    for (int i = 0; i < n_maps; i++) num[i] = baselines[i] * f;
-    hipError_t e;
-    if (subpix)
-        e = mode < 0 ? launch_fuse_depth_sub(*c, disps, subpix, n_maps, np, num, pixel_size, invalid,
-                                             depth, n_valid)
-                     : launch_fuse_depth_conf_sub(*c, disps, subpix, cost_min, cost_second, n_maps,
-                                                  np, num, pixel_size, invalid, mode, depth,
-                                                  n_valid, winner);
-    else
-        e = mode < 0 ? launch_fuse_depth(*c, disps, n_maps, np, num, pixel_size, invalid, depth,
-                                         n_valid)
-                     : launch_fuse_depth_conf(*c, disps, cost_min, cost_second, n_maps, np, num,
-                                              pixel_size, invalid, mode, depth, n_valid, winner);
-    SVA_HIP(c, e, "fuse launch");
+    for (int i = 0; i < a.n_maps; i++) num[i] = a.baselines[i] * a.f;
+    SVA_HIP(c,
+            launch_fuse(*c, a.disps, a.subpix, a.cost_min, a.cost_second, a.n_maps,
+                        (size_t)a.W * a.H, num, a.pixel_size, a.invalid, a.mode, a.depth, a.n_valid,
+                        a.winner),
+            "fuse launch");
     return SVA_OK;
 }
 
-// The host-buffer forms of both fusions, after their checks (median: mode < 0).
-// The f32 planes of the sub-pixel forms stage through in_mask, the fourth
-// input buffer.
-int fuse_host(Ctx* c, const uint16_t* disps, const float* subpix, const uint16_t* cost_min,
-              const uint16_t* cost_second, int n_maps, int W, int H, const double* baselines,
-              double f, double pixel_size, uint16_t invalid, int mode, double* depth,
-              uint8_t* n_valid, uint8_t* winner) {
-    const size_t np = (size_t)W * H, in_bytes = np * 2 * (size_t)n_maps;
+// A checked call on host planes.  The f32 planes of the sub-pixel forms stage
+// through in_mask, the fourth input buffer.
+int fuse_host(Ctx* c, const FuseArgs& a) {
+    const size_t np = (size_t)a.W * a.H, in_bytes = np * 2 * (size_t)a.n_maps;
     Staging g{c};
-    const uint16_t* dd = g.up<uint16_t>(c->in_a, disps, in_bytes);
-    const float* ds = subpix ? g.up<float>(c->in_mask, subpix, in_bytes * 2) : nullptr;
-    const uint16_t* dmin = cost_min ? g.up<uint16_t>(c->in_b, cost_min, in_bytes) : nullptr;
-    const uint16_t* dsec = cost_second ? g.up<uint16_t>(c->in_c, cost_second, in_bytes) : nullptr;
-    double* dz = g.out<double>(c->out_a, np * 8);
-    uint8_t* dn = g.out<uint8_t>(c->out_b, np);
-    uint8_t* dw = mode < 0 ? nullptr : g.out<uint8_t>(c->out_c, np);
+    FuseArgs d = a;
+    d.disps = g.up<uint16_t>(c->in_a, a.disps, in_bytes);
+    if (a.subpix) d.subpix = g.up<float>(c->in_mask, a.subpix, in_bytes * 2);
+    if (a.cost_min) d.cost_min = g.up<uint16_t>(c->in_b, a.cost_min, in_bytes);
+    if (a.cost_second) d.cost_second = g.up<uint16_t>(c->in_c, a.cost_second, in_bytes);
+    d.depth = g.out<double>(c->out_a, np * 8);
+    d.n_valid = g.out<uint8_t>(c->out_b, np);
+    d.winner = a.mode == SVA_FUSE_MEDIAN ? nullptr : g.out<uint8_t>(c->out_c, np);
     if (g.st) return g.st;
-    if (int s = run_fuse(c, dd, ds, dmin, dsec, n_maps, np, baselines, f, pixel_size, invalid, mode,
-                         dz, dn, dw))
-        return s;
-    g.down(depth, dz, np * 8);
-    g.down(n_valid, dn, np);
-    g.down(winner, dw, np);
+    if (int s = run_fuse(c, d)) return s;
+    g.down(a.depth, d.depth, np * 8);
+    g.down(a.n_valid, d.n_valid, np);
+    g.down(a.winner, d.winner, np);
     return g.sync();
 }
 
-// The sub-pixel forms' own rule, after those of the u16 forms.
-int check_subpix(Ctx* c, const float* subpix) {
-    if (!subpix) return fail(c, SVA_ERR_INVALID_ARG, "null subpix");
-    return SVA_OK;
+// What tells the eight entries apart: a cost-aware one, a sub-pixel one, host planes.
+enum : unsigned { kFuseByCost = 1, kFuseSub = 2, kFuseHost = 4 };
+
+int fuse_entry(void* ctx, const FuseArgs& a, unsigned kind) {
+    Ctx* c = as_ctx(ctx);
+    SVA_CHECK_CTX(c);
+    if (int s = check_fuse(c, a, kind & kFuseByCost, kind & kFuseSub)) return s;
+    return (kind & kFuseHost) ? fuse_host(c, a) : run_fuse(c, a);
 }
 }  // namespace
 
 int sva_fuse_depth_d(void* ctx, const uint16_t* disps, int n_maps, int W, int H,
                      const double* baselines, double f, double pixel_size, uint16_t invalid,
                      double* depth, uint8_t* n_valid) {
-    Ctx* c = as_ctx(ctx);
-    SVA_CHECK_CTX(c);
-    if (int s = check_fuse(c, disps, n_maps, W, H, baselines, depth)) return s;
-    return run_fuse(c, disps, nullptr, nullptr, nullptr, n_maps, (size_t)W * H, baselines, f,
-                    pixel_size, invalid, -1, depth, n_valid, nullptr);
+    return fuse_entry(ctx, {disps, nullptr, nullptr, nullptr, n_maps, W, H, baselines, f, pixel_size,
+                            invalid, SVA_FUSE_MEDIAN, depth, n_valid, nullptr},
+                      0);
 }
 
 int sva_fuse_depth(void* ctx, const uint16_t* disps, int n_maps, int W, int H,
                    const double* baselines, double f, double pixel_size, uint16_t invalid,
                    double* depth, uint8_t* n_valid) {
-    Ctx* c = as_ctx(ctx);
-    SVA_CHECK_CTX(c);
-    if (int s = check_fuse(c, disps, n_maps, W, H, baselines, depth)) return s;
-    return fuse_host(c, disps, nullptr, nullptr, nullptr, n_maps, W, H, baselines, f, pixel_size,
-                     invalid, -1, depth, n_valid, nullptr);
+    return fuse_entry(ctx, {disps, nullptr, nullptr, nullptr, n_maps, W, H, baselines, f, pixel_size,
+                            invalid, SVA_FUSE_MEDIAN, depth, n_valid, nullptr},
+                      kFuseHost);
 }
 
 int sva_fuse_depth_conf_d(void* ctx, const uint16_t* disps, const uint16_t* cost_min,
                           const uint16_t* cost_second, int n_maps, int W, int H,
                           const double* baselines, double f, double pixel_size, uint16_t invalid,
                           int mode, double* depth, uint8_t* n_valid, uint8_t* winner) {
-    Ctx* c = as_ctx(ctx);
-    SVA_CHECK_CTX(c);
-    if (int s = check_fuse_conf(c, disps, cost_min, cost_second, n_maps, W, H, baselines, mode,
-                                depth))
-        return s;
-    return run_fuse(c, disps, nullptr, cost_min, cost_second, n_maps, (size_t)W * H, baselines, f,
-                    pixel_size, invalid, mode, depth, n_valid, winner);
+    return fuse_entry(ctx, {disps, nullptr, cost_min, cost_second, n_maps, W, H, baselines, f,
+                            pixel_size, invalid, mode, depth, n_valid, winner},
+                      kFuseByCost);
 }
 
 int sva_fuse_depth_conf(void* ctx, const uint16_t* disps, const uint16_t* cost_min,
                         const uint16_t* cost_second, int n_maps, int W, int H,
                         const double* baselines, double f, double pixel_size, uint16_t invalid,
                         int mode, double* depth, uint8_t* n_valid, uint8_t* winner) {
-    Ctx* c = as_ctx(ctx);
-    SVA_CHECK_CTX(c);
-    if (int s = check_fuse_conf(c, disps, cost_min, cost_second, n_maps, W, H, baselines, mode,
-                                depth))
-        return s;
-    return fuse_host(c, disps, nullptr, cost_min, cost_second, n_maps, W, H, baselines, f,
-                     pixel_size, invalid, mode, depth, n_valid, winner);
+    return fuse_entry(ctx, {disps, nullptr, cost_min, cost_second, n_maps, W, H, baselines, f,
+                            pixel_size, invalid, mode, depth, n_valid, winner},
+                      kFuseByCost | kFuseHost);
 }
 
 // Sub-pixel fusion: the four calls above on the f32 maps.
 int sva_fuse_depth_sub_d(void* ctx, const uint16_t* disps, const float* subpix, int n_maps, int W,
                          int H, const double* baselines, double f, double pixel_size,
                          uint16_t invalid, double* depth, uint8_t* n_valid) {
-    Ctx* c = as_ctx(ctx);
-    SVA_CHECK_CTX(c);
-    if (int s = check_fuse(c, disps, n_maps, W, H, baselines, depth)) return s;
-    if (int s = check_subpix(c, subpix)) return s;
-    return run_fuse(c, disps, subpix, nullptr, nullptr, n_maps, (size_t)W * H, baselines, f,
-                    pixel_size, invalid, -1, depth, n_valid, nullptr);
+    return fuse_entry(ctx, {disps, subpix, nullptr, nullptr, n_maps, W, H, baselines, f, pixel_size,
+                            invalid, SVA_FUSE_MEDIAN, depth, n_valid, nullptr},
+                      kFuseSub);
 }
 
 int sva_fuse_depth_sub(void* ctx, const uint16_t* disps, const float* subpix, int n_maps, int W,
                        int H, const double* baselines, double f, double pixel_size,
                        uint16_t invalid, double* depth, uint8_t* n_valid) {
-    Ctx* c = as_ctx(ctx);
-    SVA_CHECK_CTX(c);
-    if (int s = check_fuse(c, disps, n_maps, W, H, baselines, depth)) return s;
-    if (int s = check_subpix(c, subpix)) return s;
-    return fuse_host(c, disps, subpix, nullptr, nullptr, n_maps, W, H, baselines, f, pixel_size,
-                     invalid, -1, depth, n_valid, nullptr);
+    return fuse_entry(ctx, {disps, subpix, nullptr, nullptr, n_maps, W, H, baselines, f, pixel_size,
+                            invalid, SVA_FUSE_MEDIAN, depth, n_valid, nullptr},
+                      kFuseSub | kFuseHost);
 }
 
 int sva_fuse_depth_conf_sub_d(void* ctx, const uint16_t* disps, const float* subpix,
@@ -1808,14 +1787,9 @@ int sva_fuse_depth_conf_sub_d(void* ctx, const uint16_t* disps, const float* sub
                               int W, int H, const double* baselines, double f, double pixel_size,
                               uint16_t invalid, int mode, double* depth, uint8_t* n_valid,
                               uint8_t* winner) {
-    Ctx* c = as_ctx(ctx);
-    SVA_CHECK_CTX(c);
-    if (int s = check_fuse_conf(c, disps, cost_min, cost_second, n_maps, W, H, baselines, mode,
-                                depth))
-        return s;
-    if (int s = check_subpix(c, subpix)) return s;
-    return run_fuse(c, disps, subpix, cost_min, cost_second, n_maps, (size_t)W * H, baselines, f,
-                    pixel_size, invalid, mode, depth, n_valid, winner);
+    return fuse_entry(ctx, {disps, subpix, cost_min, cost_second, n_maps, W, H, baselines, f,
+                            pixel_size, invalid, mode, depth, n_valid, winner},
+                      kFuseByCost | kFuseSub);
 }
 
 int sva_fuse_depth_conf_sub(void* ctx, const uint16_t* disps, const float* subpix,
@@ -1823,14 +1797,9 @@ int sva_fuse_depth_conf_sub(void* ctx, const uint16_t* disps, const float* subpi
                             int W, int H, const double* baselines, double f, double pixel_size,
                             uint16_t invalid, int mode, double* depth, uint8_t* n_valid,
                             uint8_t* winner) {
-    Ctx* c = as_ctx(ctx);
-    SVA_CHECK_CTX(c);
-    if (int s = check_fuse_conf(c, disps, cost_min, cost_second, n_maps, W, H, baselines, mode,
-                                depth))
-        return s;
-    if (int s = check_subpix(c, subpix)) return s;
-    return fuse_host(c, disps, subpix, cost_min, cost_second, n_maps, W, H, baselines, f,
-                     pixel_size, invalid, mode, depth, n_valid, winner);
+    return fuse_entry(ctx, {disps, subpix, cost_min, cost_second, n_maps, W, H, baselines, f,
+                            pixel_size, invalid, mode, depth, n_valid, winner},
+                      kFuseByCost | kFuseSub | kFuseHost);
 }
 
 // ------------------------- cross-view consistency check --

@@ -230,29 +230,18 @@ hipError_t launch_cost_fuse(Ctx& c, const uint8_t* volumes, size_t stride, int n
 hipError_t launch_cost_mixed(Ctx& c, const uint64_t* cen_ref, const uint64_t* cen_oth, int W, int H,
                              int D, int dmin, int sx, int sy, int num, int den, uint8_t* C,
                              int dreal = 0);
-// Median depth fusion over n_maps <= 32 u16 maps.
-// num[i] = baseline_i * f (host-computed, same f64 product as the oracle).
-hipError_t launch_fuse_depth(Ctx& c, const uint16_t* disps, int n_maps, size_t np,
-                             const double* num, double pixel_size, uint16_t invalid,
-                             double* depth, uint8_t* n_valid);
-// Cost-aware fusion: per pixel the depth of the valid map
-// with the smallest cost_min (mode SVA_FUSE_MIN_COST; cost_second nullable)
-// or the largest cost_second - cost_min (SVA_FUSE_MAX_MARGIN); winner
-// (nullable) gets its index, 0xFF if none.
-hipError_t launch_fuse_depth_conf(Ctx& c, const uint16_t* disps, const uint16_t* cost_min,
-                                  const uint16_t* cost_second, int n_maps, size_t np,
-                                  const double* num, double pixel_size, uint16_t invalid, int mode,
-                                  double* depth, uint8_t* n_valid, uint8_t* winner);
-// Both fusions on the f32 sub-pixel maps: subpix [n_maps][np],
-// a map valid where its u16 disparity is and subpix > 0.
-hipError_t launch_fuse_depth_sub(Ctx& c, const uint16_t* disps, const float* subpix, int n_maps,
-                                 size_t np, const double* num, double pixel_size, uint16_t invalid,
-                                 double* depth, uint8_t* n_valid);
-hipError_t launch_fuse_depth_conf_sub(Ctx& c, const uint16_t* disps, const float* subpix,
-                                      const uint16_t* cost_min, const uint16_t* cost_second,
-                                      int n_maps, size_t np, const double* num, double pixel_size,
-                                      uint16_t invalid, int mode, double* depth, uint8_t* n_valid,
-                                      uint8_t* winner);
+// fuse.hip -- depth fusion over n_maps <= 32 u16 maps [n_maps][np] (DESIGN.md
+// §2.6, §2.6b, §2.6c).  num[i] = baseline_i * f (host-computed, the oracle's f64
+// product).  mode SVA_FUSE_MEDIAN: the median of the valid maps' depths (cost
+// planes and winner unused).  SVA_FUSE_MIN_COST / SVA_FUSE_MAX_MARGIN: the depth
+// of the valid map with the smallest cost_min / the largest cost_second -
+// cost_min (cost_second nullable for MIN_COST); winner (nullable) gets its
+// index, 0xFF if none.  subpix (nullable, f32 [n_maps][np]): the depths come
+// from it, and a map is valid where its u16 disparity is and subpix > 0.
+hipError_t launch_fuse(Ctx& c, const uint16_t* disps, const float* subpix, const uint16_t* cost_min,
+                       const uint16_t* cost_second, int n_maps, size_t np, const double* num,
+                       double pixel_size, uint16_t invalid, int mode, double* depth,
+                       uint8_t* n_valid, uint8_t* winner);
 // cross_check.hip -- the cross-view consistency check: n <= 32
 // maps [n][H][W] of one unit baseline, view_step [n][2] (host); subpix / out_sub
 // (f32), agree, conflict (u8) nullable, out_sub needs subpix; W * H < 2^31.

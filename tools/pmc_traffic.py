@@ -20,7 +20,8 @@ import sys
 
 SHORT = {
     "sgm_paths_kernel": "sgm_paths",
-    "hamming_cost2_kernel": "cost2", "fuse_depth_kernel": "fuse_depth",
+    # "::" keeps cost_fuse_kernel< out; the frames measured here fuse by the u16 median
+    "hamming_cost2_kernel": "cost2", "::fuse_kernel": "fuse_depth",
     "hamming_cost_rows_kernel": "cost", "census9x7_rows_kernel": "census",
     "census_cost_mma_kernel": "cost", "wta_hv_kernel": "wta_hv",
 }
