@@ -203,7 +203,10 @@ int sva_kernel_time(void* ctx, const char* name, double* total_ms, int64_t* coun
  *   SVA_DEBUG_CROSS_ORDER    set / get: the block order of sva_cross_check*'s
  *                            kernel, 0 = view-major, 1 = tile-major, -1 restores
  *                            the built-in choice (get returns the order in
- *                            force).  Speed only: the outputs do not change. */
+ *                            force).  Speed only: the outputs do not change.
+ *   SVA_DEBUG_FILL_SEGMENT   set / get: the segment length of sva_fill_holes*'s
+ *                            scan, 1..65536; 0 restores the built-in length
+ *                            (get returns the length in force).  Speed only. */
 #define SVA_DEBUG_PLANE_SPLIT 1
 #define SVA_DEBUG_FAIL_COST_AT 2
 #define SVA_DEBUG_SIDE_IDLE 3
@@ -215,6 +218,7 @@ int sva_kernel_time(void* ctx, const char* name, double* total_ms, int64_t* coun
 #define SVA_DEBUG_REFINE_ROUTE 9
 #define SVA_DEBUG_REFINE_LAST_ROUTE 10
 #define SVA_DEBUG_CROSS_ORDER 11
+#define SVA_DEBUG_FILL_SEGMENT 12
 int sva_set_debug(void* ctx, int key, int64_t value);
 int sva_get_debug(void* ctx, int key, int64_t* value);
 
@@ -743,6 +747,53 @@ int sva_filter_speckles(void* ctx, const uint16_t* disps, const float* subpix, i
                         int width, int height, uint16_t invalid, int max_size, int max_diff,
                         uint16_t* out, float* out_sub, uint32_t* comp_size);
 
+/* Hole filling: fills the holes of n_maps >= 1 disparity maps
+ * disps [n_maps][H][W] u16 (device / host) from the nearest valid pixels, the
+ * last step of an SGM post-filter chain (Hirschmueller's disparity
+ * interpolation).  A pixel is valid iff d != invalid and d != 0; every other
+ * pixel is a hole.  For a hole p, direction k = 0..7 -- E (+1,0), W (-1,0),
+ * S (0,+1), N (0,-1), SE (+1,+1), NW (-1,-1), SW (-1,+1), NE (+1,-1) -- walks
+ * p + j * r_k for j = 1..max_dist inside the frame; the first valid pixel of
+ * the INPUT map is its candidate (d, j, k), j counting steps on the diagonals
+ * too.  Filled pixels never serve as sources.  n = the number of directions
+ * with a candidate; the candidates sorted by (d, j, k):
+ *   n >= min_found: out = d of element 0 (SVA_FILL_MIN), min(1, n - 1)
+ *                   (SVA_FILL_SECOND, the occlusion rule: the second lowest),
+ *                   (n - 1) / 2 (SVA_FILL_MEDIAN, the lower median)
+ *   n <  min_found: out = disps, unchanged (0 stays 0, invalid stays invalid)
+ * and out = disps at every valid pixel.  subpix (nullable): [n_maps][H][W] f32;
+ * out_sub (nullable, needs subpix) gets the 32 bits of subpix at the chosen
+ * candidate's source pixel where p was filled and those of subpix[p] everywhere
+ * else, NaN included.  n_found (nullable): [n_maps][H][W] u8, n at the holes,
+ * filled or not, and 0 at valid pixels.  max_dist in 0..255 (SVA_FILL_MAX_DIST:
+ * an occlusion band is about as wide as the disparity range, and j fits eight
+ * bits of the sort key); max_dist = 0 copies the input bit for bit.  min_found
+ * in 1..8.  Maps never interact.  Integer-only and independent of any ordering:
+ * every output byte has one right value.  In place is allowed: out == disps and
+ * / or out_sub == subpix, exactly.
+ * Workspace: 32 * n_maps * width * height bytes of device memory per context
+ * (eight u32 key planes per map: 32 bytes per pixel), grown on demand, kept for
+ * later calls and freed by sva_destroy; none for max_dist = 0.
+ * Returned before anything is launched, in this order: SVA_ERR_INVALID_ARG for
+ * a null disps or out, n_maps < 1, a width or height < 1; SVA_ERR_UNSUPPORTED
+ * for width * height >= 2^31; SVA_ERR_INVALID_ARG for max_dist outside 0..255,
+ * min_found outside 1..8, mode outside 0..2, out_sub without subpix, or any
+ * overlap of an output (out, out_sub, n_found) with an input or another output
+ * other than the two in-place forms above; SVA_ERR_OUT_OF_MEMORY if the
+ * workspace cannot be had.  _d is asynchronous on the context stream; its two
+ * launches are timed as "fill_scan" and "fill_apply" (the copy: "fill_apply"
+ * alone). */
+#define SVA_FILL_MIN 0
+#define SVA_FILL_SECOND 1
+#define SVA_FILL_MEDIAN 2
+#define SVA_FILL_MAX_DIST 255
+int sva_fill_holes_d(void* ctx, const uint16_t* disps, const float* subpix, int n_maps,
+                     int width, int height, uint16_t invalid, int max_dist, int min_found,
+                     int mode, uint16_t* out, float* out_sub, uint8_t* n_found);
+int sva_fill_holes(void* ctx, const uint16_t* disps, const float* subpix, int n_maps, int width,
+                   int height, uint16_t invalid, int max_dist, int min_found, int mode,
+                   uint16_t* out, float* out_sub, uint8_t* n_found);
+
 /* Disparity -> depth, CameraStereoVision.cpp:47,98-100 (f64; 0 where disp 0). */
 int sva_disparity_to_depth_d(void* ctx, const uint8_t* disp, int n, double cam_distance,
                              double f, double pixel_size, double* depth);
@@ -983,6 +1034,34 @@ int sva_array_depth_filtered(void* multi, const uint8_t* const* images, int n_im
                              int max_diff, int min_agree, int max_conflict, uint8_t* agree,
                              uint8_t* conflict, int check, int speckle_max_size,
                              int speckle_max_diff, uint32_t* comp_size);
+/* An array frame with hole filling:
+ * sva_array_depth_filtered's arguments, then the fill's max_dist, min_found and
+ * mode (see sva_fill_holes) and n_found (nullable): host [n_jobs][H][W] u8, one
+ * plane per map (per pair on SVA_ARRAY_PAIRS, per group on the group routes).
+ * devices[0] runs sva_fill_holes_d in place over every job's map -- and its f32
+ * plane with sub = 1 -- after the speckle filter and before the depth step, on
+ * every route; on SVA_ARRAY_PAIRS per pair, before the group's fusion.  maps,
+ * subpix, depth, n_valid and winner are those of the FILLED maps; cost_min /
+ * cost_second stay the matcher's: at a filled pixel they describe the match
+ * that was rejected, not the value filled in, so SVA_FUSE_MEDIAN is the sensible
+ * fusion mode after a fill.  Bit for bit: fill_max_dist = 0 gives
+ * sva_array_depth_filtered's outputs; any other value gives the stand-alone
+ * composition: the filtered frame's maps through sva_fill_holes and the
+ * matching sva_fuse_depth*.
+ * After all of sva_array_depth_filtered's rules, in this order,
+ * SVA_ERR_INVALID_ARG for: fill_max_dist outside 0..255; fill_min_found outside
+ * 1..8; fill_mode outside 0..2.  Before anything is launched. */
+int sva_array_depth_filled(void* multi, const uint8_t* const* images, int n_images, int width,
+                           int height, size_t pitch, const sva_array_pair* pairs, int n_pairs,
+                           const int32_t* group_start, int n_groups, int route,
+                           const double* unit_baseline, double f, double pixel_size,
+                           int uniqueness, int mode, double* depth, uint8_t* n_valid,
+                           uint8_t* winner, float* subpix, uint16_t* maps, uint16_t* cost_min,
+                           uint16_t* cost_second, const int32_t* view_step, int sub, int max_diff,
+                           int min_agree, int max_conflict, uint8_t* agree, uint8_t* conflict,
+                           int check, int speckle_max_size, int speckle_max_diff,
+                           uint32_t* comp_size, int fill_max_dist, int fill_min_found,
+                           int fill_mode, uint8_t* n_found);
 
 #ifdef __cplusplus
 }

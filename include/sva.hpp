@@ -991,6 +991,95 @@ inline std::vector<std::vector<double>> computeArrayDepthFiltered(
     return depth;
 }
 
+// ---- hole filling -----------------------------------------
+
+// What fillHoles makes of each map: the filled map, the optional f32 map, and
+// the number of directions that found a valid pixel (0 where the pixel is valid).
+struct HolesFilled {
+    std::vector<std::vector<uint16_t>> maps;
+    std::vector<std::vector<float>> subpix;       // empty unless sub-pixel maps went in
+    std::vector<std::vector<uint8_t>> n_found;
+};
+
+// Fills the holes of each map (sva_fill_holes): a pixel that is 0 or `invalid`
+// looks up to max_dist steps along the eight directions for the nearest valid
+// pixel of the input map; with at least min_found candidates it takes the one
+// `mode` picks of them sorted by (value, distance, direction) -- SVA_FILL_MIN,
+// SVA_FILL_SECOND (the occlusion rule) or SVA_FILL_MEDIAN -- and in subpix that
+// source's f32 value.  maps[i] is W*H u16; subpix: empty, or one f32 map per
+// map.  max_dist in 0..255; 0 returns the input.
+inline HolesFilled fillHoles(Engine& eng, const std::vector<std::vector<uint16_t>>& maps,
+                             const std::vector<std::vector<float>>& subpix, int W, int H,
+                             int max_dist, int min_found = 1, int mode = SVA_FILL_SECOND,
+                             uint16_t invalid = 0xFFFF) {
+    const size_t np = (size_t)W * H, n = maps.size();
+    if (maps.empty() || (!subpix.empty() && subpix.size() != n))
+        throw Error(SVA_ERR_INVALID_ARG, "fillHoles: need one sub-pixel map per map");
+    std::vector<uint16_t> d(np * n);
+    std::vector<float> s(subpix.empty() ? 0 : np * n);
+    std::vector<uint8_t> found(np * n);
+    for (size_t i = 0; i < n; i++) {
+        if (maps[i].size() != np || (!subpix.empty() && subpix[i].size() != np))
+            throw Error(SVA_ERR_INVALID_ARG, "fillHoles: map size");
+        std::copy(maps[i].begin(), maps[i].end(), d.begin() + i * np);
+        if (!subpix.empty()) std::copy(subpix[i].begin(), subpix[i].end(), s.begin() + i * np);
+    }
+    // in place on the packed copies
+    eng.check(sva_fill_holes(eng.handle(), d.data(), s.empty() ? nullptr : s.data(), (int)n, W, H,
+                             invalid, max_dist, min_found, mode, d.data(),
+                             s.empty() ? nullptr : s.data(), found.data()));
+    HolesFilled r;
+    for (size_t i = 0; i < n; i++) {
+        r.maps.emplace_back(d.begin() + i * np, d.begin() + (i + 1) * np);
+        if (!s.empty()) r.subpix.emplace_back(s.begin() + i * np, s.begin() + (i + 1) * np);
+        r.n_found.emplace_back(found.begin() + i * np, found.begin() + (i + 1) * np);
+    }
+    return r;
+}
+
+// computeArrayDepthFiltered's frame with hole filling over every job's map
+// after the speckle filter and before depth (sva_array_depth_filled).  The
+// frame's cost planes stay the matcher's -- at a filled pixel they describe the
+// rejected match -- so the median is the fusion mode that makes sense after a
+// fill.  maps, n_found (nullable): one plane per pair in `pairs` order, or one
+// per reference camera.
+inline std::vector<std::vector<double>> computeArrayDepthFilled(
+    MultiEngine& m, const std::vector<ImageView>& images, const std::vector<Camera>& cameras,
+    const std::vector<std::array<int, 2>>& pairs, const sva_sgm_params& p, int fill_max_dist,
+    int fill_min_found = 1, int fill_mode = SVA_FILL_SECOND, int speckle_max_size = 0,
+    int speckle_max_diff = 0, int route = SVA_ARRAY_GROUPS, bool check = false, bool sub = false,
+    int max_diff = 1, int min_agree = 1, int max_conflict = 0, int uniqueness = 0,
+    int mode = SVA_FUSE_MEDIAN, double pitch = 0.05,
+    std::vector<std::vector<uint16_t>>* maps = nullptr,
+    std::vector<std::vector<uint8_t>>* n_found = nullptr) {
+    const detail::ArrayFrame fr = detail::arrayFrame(images, cameras, pairs, p, pitch,
+                                                     "computeArrayDepthFilled");
+    std::vector<double> unit;
+    if (route == SVA_ARRAY_GROUPS_MIXED) unit = detail::unitBaselines(fr, 1, pitch);
+    std::vector<int32_t> vs;
+    for (const Camera& c : cameras) {
+        vs.push_back(-(int32_t)std::lround((c.pos3D.x - cameras[0].pos3D.x) / pitch));
+        vs.push_back(-(int32_t)std::lround((c.pos3D.y - cameras[0].pos3D.y) / pitch));
+    }
+    const bool per_group = route != SVA_ARRAY_PAIRS;
+    const size_t np = (size_t)fr.W * fr.H;
+    std::vector<uint8_t> found(n_found ? np * (per_group ? fr.refs.size() : fr.ap.size()) : 0);
+    auto depth = detail::arrayDepth(fr, cameras, pairs.size(), per_group, maps,
+                                    [&](double f, double pixel_size, double* depth, uint16_t* all) {
+        m.check(fr.call(sva_array_depth_filled, m.handle(), route,
+                        unit.empty() ? (const double*)nullptr : (const double*)unit.data(), f,
+                        pixel_size, uniqueness, mode, depth, (uint8_t*)nullptr, (uint8_t*)nullptr,
+                        (float*)nullptr, all, (uint16_t*)nullptr, (uint16_t*)nullptr,
+                        (const int32_t*)vs.data(), sub ? 1 : 0, max_diff, min_agree, max_conflict,
+                        (uint8_t*)nullptr, (uint8_t*)nullptr, check ? 1 : 0, speckle_max_size,
+                        speckle_max_diff, (uint32_t*)nullptr, fill_max_dist, fill_min_found,
+                        fill_mode, n_found ? found.data() : (uint8_t*)nullptr));
+    });
+    if (n_found && per_group) *n_found = fr.split(found);
+    else if (n_found) fr.scatter(found, pairs.size(), n_found);
+    return depth;
+}
+
 
 // ---- refinement and 3-D output ----
 // The reference's names and argument meaning; cv::Mat becomes ImageView (u8)

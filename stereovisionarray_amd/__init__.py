@@ -45,6 +45,7 @@ SVA_DEBUG_DIAG_PAIR_MIN_PIXELS = 8
 SVA_DEBUG_REFINE_ROUTE = 9
 SVA_DEBUG_REFINE_LAST_ROUTE = 10
 SVA_DEBUG_CROSS_ORDER = 11
+SVA_DEBUG_FILL_SEGMENT = 12
 # The ABI this binding is written against (include/sva.h SVA_ABI_VERSION).
 ABI_VERSION = 6
 
@@ -75,8 +76,12 @@ EXPORTED = [
     "sva_fuse_depth_sub", "sva_fuse_depth_sub_d", "sva_fuse_depth_conf_sub",
     "sva_fuse_depth_conf_sub_d", "sva_array_depth_sub", "sva_cross_check", "sva_cross_check_d",
     "sva_array_depth_checked", "sva_filter_speckles", "sva_filter_speckles_d",
-    "sva_array_depth_filtered",
+    "sva_array_depth_filtered", "sva_fill_holes", "sva_fill_holes_d", "sva_array_depth_filled",
 ]
+SVA_FILL_MIN = 0
+SVA_FILL_SECOND = 1
+SVA_FILL_MEDIAN = 2
+SVA_FILL_MAX_DIST = 255
 SVA_FUSE_MIN_COST = 0
 SVA_FUSE_MAX_MARGIN = 1
 SVA_FUSE_MEDIAN = 2      # sva_array_depth_conf and sva_array_depth_sub only
@@ -305,6 +310,12 @@ def _load() -> ct.CDLL:
                                            i32, i32, P(dbl), dbl, dbl, i32, i32, vp, vp, vp, vp, vp,
                                            vp, vp, P(ct.c_int32), i32, i32, i32, i32, vp, vp, i32,
                                            i32, i32, vp]),
+        "sva_fill_holes_d": (i32, [vp, vp, vp, i32, i32, i32, ct.c_uint16, i32, i32, i32, vp, vp, vp]),
+        "sva_fill_holes": (i32, [vp, vp, vp, i32, i32, i32, ct.c_uint16, i32, i32, i32, vp, vp, vp]),
+        "sva_array_depth_filled": (i32, [vp, P(vp), i32, i32, i32, sz, P(ArrayPair), i32, P(i32),
+                                         i32, i32, P(dbl), dbl, dbl, i32, i32, vp, vp, vp, vp, vp,
+                                         vp, vp, P(ct.c_int32), i32, i32, i32, i32, vp, vp, i32,
+                                         i32, i32, vp, i32, i32, i32, vp]),
         "sva_resize_linear_f64_d": (i32, [vp, vp, i32, i32, vp, i32, i32]),
         "sva_resize_linear_f64": (i32, [vp, vp, i32, i32, vp, i32, i32]),
         "sva_ref_error_d": (i32, [vp, vp, i32, i32, vp, i32, i32, ct.c_double, vp]),
@@ -961,6 +972,31 @@ class Context:
                                             int(max_size), int(max_diff), _ptr(out), _ptr(out_sub),
                                             _ptr(comp_size)))
 
+    def fill_holes(self, disps: np.ndarray, max_dist, min_found=1, mode=SVA_FILL_SECOND,
+                   subpix=None, invalid=0xFFFF, want_found=True):
+        """(out, out_sub or None, n_found or None): sva_fill_holes, hole filling
+         of n maps [n][H][W] u16.  A hole (0 or `invalid`) with
+        at least min_found valid pixels within max_dist steps along the eight
+        directions takes the `mode` statistic of them (sorted by value, distance,
+        direction); out_sub (with subpix) takes the chosen source's f32 value."""
+        d = np.ascontiguousarray(disps, dtype=np.uint16)
+        s = None if subpix is None else np.ascontiguousarray(subpix, dtype=np.float32)
+        N, H, W = d.shape
+        assert s is None or s.shape == d.shape
+        out = np.zeros_like(d)
+        osub = None if s is None else np.zeros_like(s)
+        found = np.zeros(d.shape, np.uint8) if want_found else None
+        self._chk(lib.sva_fill_holes(self.h, _ptr(d), _ptr(s), N, W, H, invalid, int(max_dist),
+                                     int(min_found), int(mode), _ptr(out), _ptr(osub), _ptr(found)))
+        return out, osub, found
+
+    def fill_holes_d(self, disps, subpix, n_maps, W, H, invalid, max_dist, min_found, mode, out,
+                     out_sub=None, n_found=None):
+        """sva_fill_holes_d on device pointers; out may be disps and out_sub subpix."""
+        self._chk(lib.sva_fill_holes_d(self.h, _ptr(disps), _ptr(subpix), n_maps, W, H, invalid,
+                                       int(max_dist), int(min_found), int(mode), _ptr(out),
+                                       _ptr(out_sub), _ptr(n_found)))
+
     def disparity_to_depth(self, disp: np.ndarray, cam_distance, f, pixel_size):
         d = np.ascontiguousarray(disp, dtype=np.uint8)
         out = np.zeros(d.shape, np.float64)
@@ -1202,6 +1238,42 @@ class Multi:
             _ptr(r["maps"]), _ptr(r["cost_min"]), _ptr(r["cost_second"]), vs, int(sub),
             int(max_diff), int(min_agree), int(max_conflict), _ptr(r["agree"]), _ptr(r["conflict"]),
             int(check), int(speckle_max_size), int(speckle_max_diff), _ptr(r["comp_size"])))
+        return r
+
+    def array_depth_filled(self, images, pairs, group_start, f, pixel_size, fill_max_dist,
+                           fill_min_found=1, fill_mode=SVA_FILL_SECOND, speckle_max_size=0,
+                           speckle_max_diff=0, check=0, view_step=None, route=SVA_ARRAY_GROUPS,
+                           unit_baseline=None, uniqueness=0, mode=SVA_FUSE_MEDIAN, sub=0,
+                           max_diff=1, min_agree=1, max_conflict=0, want_sub=False,
+                           want_maps=False, want_costs=False, want_counts=False, want_size=False,
+                           want_n_valid=False, want_winner=False, want_found=False):
+        """sva_array_depth_filled: array_depth_filtered's frame with hole filling
+         over every job's map after the speckle filter and before
+        depth.  Returns array_depth_filtered's dict with n_found [jobs,H,W] u8
+        added (None unless asked for).  cost_min / cost_second stay the
+        matcher's: at a filled pixel they describe the rejected match."""
+        fr = _ArrayFrame(images, pairs, group_start)
+        nj = len(pairs) if int(route) == SVA_ARRAY_PAIRS else fr.G
+        ub = None if unit_baseline is None else \
+            (ct.c_double * max(1, len(unit_baseline)))(*[float(v) for v in unit_baseline])
+        vs = None if view_step is None else _steps(view_step, len(view_step))
+        r = dict(depth=fr.planes(fr.G, np.float64),
+                 n_valid=fr.planes(fr.G, np.uint8, want_n_valid),
+                 winner=fr.planes(fr.G, np.uint8, want_winner),
+                 subpix=fr.planes(nj, np.float32, want_sub), maps=fr.planes(nj, np.uint16, want_maps),
+                 cost_min=fr.planes(nj, np.uint16, want_costs),
+                 cost_second=fr.planes(nj, np.uint16, want_costs),
+                 agree=fr.planes(fr.G, np.uint8, want_counts),
+                 conflict=fr.planes(fr.G, np.uint8, want_counts),
+                 comp_size=fr.planes(nj, np.uint32, want_size),
+                 n_found=fr.planes(nj, np.uint8, want_found))
+        self._chk(lib.sva_array_depth_filled(
+            self.h, *fr.head, int(route), ub, f, pixel_size, int(uniqueness), int(mode),
+            _ptr(r["depth"]), _ptr(r["n_valid"]), _ptr(r["winner"]), _ptr(r["subpix"]),
+            _ptr(r["maps"]), _ptr(r["cost_min"]), _ptr(r["cost_second"]), vs, int(sub),
+            int(max_diff), int(min_agree), int(max_conflict), _ptr(r["agree"]), _ptr(r["conflict"]),
+            int(check), int(speckle_max_size), int(speckle_max_diff), _ptr(r["comp_size"]),
+            int(fill_max_dist), int(fill_min_found), int(fill_mode), _ptr(r["n_found"])))
         return r
 
     def array_depth(self, images, pairs, group_start, f, pixel_size, want_maps=False):

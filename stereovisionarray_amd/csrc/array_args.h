@@ -1,9 +1,10 @@
 // array_args.h -- the arguments of one camera-array frame (sva_array_depth,
-// _conf, _mb, _mixed, _sub, _checked and _filtered) and their
-// validation, shared by multi.cpp and the host test programs
+// _conf, _mb, _mixed, _sub, _checked, _filtered and _filled) and
+// their validation, shared by multi.cpp and the host test programs
 // (tests/test_array_args_cpu.py, tests/test_array_sub_args_cpu.py,
-// tests/test_cross_check_cpu.py and tests/test_speckle_cpu.py compile this
-// header with a C++ compiler under the sanitizers).  Plain C++: no HIP header.
+// tests/test_cross_check_cpu.py, tests/test_speckle_cpu.py and
+// tests/test_fill_cpu.py compile this header with a C++ compiler under the
+// sanitizers).  Plain C++: no HIP header.
 #pragma once
 
 #include <algorithm>
@@ -15,6 +16,7 @@
 
 #include "cost_mixed_math.h"
 #include "cross_check_math.h"
+#include "fill_math.h"
 #include "speckle_math.h"
 #include "sva.h"
 #include "sva_native_d.h"
@@ -73,6 +75,11 @@ struct ArrayArgs {
     int check = 0;                            // the entry's `check`, as given
     int speckle_max_size = 0, speckle_max_diff = 0;
     uint32_t* comp_size = nullptr;            // host, per job, nullable
+    // fill (sva_array_depth_filled; speckle is set too): the
+    // jobs' maps then go through sva_fill_holes_d in place, before depth
+    bool fill = false;
+    int fill_max_dist = 0, fill_min_found = 1, fill_mode = 0;
+    uint8_t* n_found = nullptr;               // host, per job, nullable
 };
 
 inline int check_params(const sva_sgm_params& p) {
@@ -252,7 +259,8 @@ inline int check_frame_args(const ArrayArgs& a, std::string& msg, std::vector<in
 // its rules -- those of a.cross among them, which the entry sets iff check == 1
 // -- in this order: a check outside 0 / 1; with check = 0, an agree or conflict
 // plane, then a subpix plane without sub; speckle_max_size < 0;
-// speckle_max_diff < 0.
+// speckle_max_diff < 0.  With a.fill (sva_array_depth_filled) after those:
+// fill_max_dist, fill_min_found, fill_mode out of range.
 inline int check_array_args(const ArrayArgs& a, std::string& msg, std::vector<int32_t>& ratio) {
     if (int st = check_frame_args(a, msg, ratio)) return st;
     if (!a.speckle) return SVA_OK;
@@ -266,6 +274,9 @@ inline int check_array_args(const ArrayArgs& a, std::string& msg, std::vector<in
     if (a.check == 0 && !a.sub && a.subpix) return fail("subpix needs sub = 1");
     if (const char* m = sp::thresholds_error(a.speckle_max_size, a.speckle_max_diff))
         return fail(m);
+    if (a.fill)
+        if (const char* m = fl::thresholds_error(a.fill_max_dist, a.fill_min_found, a.fill_mode))
+            return fail(m);
     return SVA_OK;
 }
 

@@ -12,7 +12,7 @@
 // through the public per-context entry points (sva_disparity_sgm_d,
 // sva_fuse_depth_d, and sva_disparity_sgm_conf_d / sva_fuse_depth_conf_d for
 // the confidence forms, whose cost planes are gathered like the maps); there
-// is no CPU path.  The seven sva_array_depth* entry points fill one ArrayArgs
+// is no CPU path.  The eight sva_array_depth* entry points fill one ArrayArgs
 // (array_args.h: the arguments and their checks, in one order) and run one
 // array_frame(): its jobs are pairs, or -- sva_array_depth_mb -- GROUPS (one
 // sva_disparity_sgm_multi_d per reference camera, DESIGN.md §2.2c;
@@ -121,6 +121,7 @@ struct Multi {
     DevBuf sub0;                       // device 0: f32 sub-pixel maps (sva_array_depth_sub)
     DevBuf cross0;                     // device 0: the checked planes (sva_array_depth_checked)
     DevBuf speckle0;                   // device 0: comp_size planes (sva_array_depth_filtered)
+    DevBuf fill0;                      // device 0: n_found planes (sva_array_depth_filled)
     PinnedBuf stage_in, stage_out;
     Rccl rccl;
     std::vector<ncclComm_t> comms;
@@ -646,6 +647,7 @@ int sva_multi_destroy(void* mp) {
         m->sub0.release();
         m->cross0.release();
         m->speckle0.release();
+        m->fill0.release();
     }
     m->stage_in.release();
     m->stage_out.release();
@@ -817,7 +819,7 @@ struct Download {
     }
 };
 
-// One camera-array frame: sva_array_depth, _conf, _mb, _mixed, _sub, _checked and _filtered (array_args.h
+// One camera-array frame: sva_array_depth, _conf, _mb, _mixed, _sub, _checked, _filtered and _filled (array_args.h
 // has their arguments and checks).  A job is a pair (ArrayRoute::Pairs: every
 // pair through sva_disparity_sgm_d or, with conf, sva_disparity_sgm_conf_d; a
 // group's maps are fused by `mode`) or a GROUP (group g's
@@ -829,7 +831,8 @@ struct Download {
 // With a.cross (sva_array_depth_checked, §2.5b) the groups' maps pass through
 // sva_cross_check_d on device 0 before step 4, which then reads the checked
 // planes.  With a.speckle (sva_array_depth_filtered, §2.5c) every job's map --
-// checked or not -- then passes through sva_filter_speckles_d in place.
+// checked or not -- then passes through sva_filter_speckles_d in place, and
+// with a.fill (sva_array_depth_filled, §2.5d) through sva_fill_holes_d after it.
 int array_frame(void* mp, const ArrayArgs& a) {
     Multi* m = as_multi(mp);
     if (!m) return SVA_ERR_INVALID_ARG;
@@ -965,6 +968,29 @@ int array_frame(void* mp, const ArrayArgs& a) {
             if (st) return m->ctx_fail(st, m->ctx[0], "speckle filter");
         }
     }
+    // 3d. hole filling, in place on the same maps (and f32 maps): one call per
+    // run of at most kFillFrameMaps jobs that share `invalid`, which bounds the
+    // context's key planes
+    uint8_t* found0 = nullptr;
+    if (a.fill) {
+        MHIP(m, hipSetDevice(m->devices[0]), "hipSetDevice");
+        if (a.n_found) {
+            MHIP(m, m->fill0.ensure(np * n_jobs), "fill workspace");
+            found0 = (uint8_t*)m->fill0.ptr;
+        }
+        for (int k = 0, k1; k < n_jobs; k = k1) {
+            const uint16_t inv = pairs[first[k]].params.invalid;
+            for (k1 = k + 1; k1 < n_jobs && k1 - k < tune::kFillFrameMaps &&
+                             pairs[first[k1]].params.invalid == inv;)
+                k1++;
+            const size_t o = (size_t)k * np;
+            float* sk = sub0 ? sub0 + o : nullptr;
+            st = sva_fill_holes_d(m->ctx[0], maps0 + o, sk, k1 - k, W, H, inv, a.fill_max_dist,
+                                  a.fill_min_found, a.fill_mode, maps0 + o, sk,
+                                  found0 ? found0 + o : nullptr);
+            if (st) return m->ctx_fail(st, m->ctx[0], "hole filling");
+        }
+    }
     // 4. depth per group on device 0 -- the fusion of its pairs' maps, or the
     // depth of its one map (the median of one is the map's own depth) -- each
     // group's download as soon as it is done, the per-job planes at the end
@@ -986,6 +1012,7 @@ int array_frame(void* mp, const ArrayArgs& a) {
     dl.add(n_groups, agree0, a.agree, np * n_groups);
     dl.add(n_groups, conflict0, a.conflict, np * n_groups);
     dl.add(n_groups, size0, a.comp_size, plane * 2);
+    dl.add(n_groups, found0, a.n_found, np * n_jobs);
     MHIP(m, m->stage_out.ensure(dl.total), "pinned staging");
     std::vector<double> bases(n_pairs);
     for (int j = 0; j < n_pairs; j++) bases[j] = pairs[j].baseline;
@@ -1024,7 +1051,7 @@ int array_frame(void* mp, const ArrayArgs& a) {
     return dl.finish(m);
 }
 
-// What the seven entry points share; as it stands, sva_array_depth's: the pair
+// What the eight entry points share; as it stands, sva_array_depth's: the pair
 // route, plain matching, median fusion.
 ArrayArgs frame_args(const uint8_t* const* images, int n_images, int W, int H, size_t pitch,
                      const sva_array_pair* pairs, int n_pairs, const int32_t* group_start,
@@ -1169,16 +1196,19 @@ int sva_array_depth_checked(void* mp, const uint8_t* const* images, int n_images
     return array_frame(mp, a);
 }
 
-int sva_array_depth_filtered(void* mp, const uint8_t* const* images, int n_images, int W, int H,
-                             size_t pitch, const sva_array_pair* pairs, int n_pairs,
-                             const int32_t* group_start, int n_groups, int route,
-                             const double* unit_baseline, double f, double pixel_size,
-                             int uniqueness, int mode, double* depth, uint8_t* n_valid,
-                             uint8_t* winner, float* subpix, uint16_t* maps, uint16_t* cost_min,
-                             uint16_t* cost_second, const int32_t* view_step, int sub,
-                             int max_diff, int min_agree, int max_conflict, uint8_t* agree,
-                             uint8_t* conflict, int check, int speckle_max_size,
-                             int speckle_max_diff, uint32_t* comp_size) {
+// sva_array_depth_filtered (fill = false: the fill's arguments are not looked
+// at) and sva_array_depth_filled.
+static int array_depth_post(void* mp, const uint8_t* const* images, int n_images, int W, int H,
+                            size_t pitch, const sva_array_pair* pairs, int n_pairs,
+                            const int32_t* group_start, int n_groups, int route,
+                            const double* unit_baseline, double f, double pixel_size,
+                            int uniqueness, int mode, double* depth, uint8_t* n_valid,
+                            uint8_t* winner, float* subpix, uint16_t* maps, uint16_t* cost_min,
+                            uint16_t* cost_second, const int32_t* view_step, int sub, int max_diff,
+                            int min_agree, int max_conflict, uint8_t* agree, uint8_t* conflict,
+                            int check, int speckle_max_size, int speckle_max_diff,
+                            uint32_t* comp_size, bool fill, int fill_max_dist, int fill_min_found,
+                            int fill_mode, uint8_t* n_found) {
     if (sub != 0 && sub != 1) {
         Multi* m = as_multi(mp);
         return m ? m->fail(SVA_ERR_INVALID_ARG, "sub must be 0 or 1") : SVA_ERR_INVALID_ARG;
@@ -1207,7 +1237,50 @@ int sva_array_depth_filtered(void* mp, const uint8_t* const* images, int n_image
     a.speckle_max_size = speckle_max_size;
     a.speckle_max_diff = speckle_max_diff;
     a.comp_size = comp_size;
+    a.fill = fill;
+    if (fill) {
+        a.fill_max_dist = fill_max_dist;
+        a.fill_min_found = fill_min_found;
+        a.fill_mode = fill_mode;
+        a.n_found = n_found;
+    }
     return array_frame(mp, a);
+}
+
+int sva_array_depth_filtered(void* mp, const uint8_t* const* images, int n_images, int W, int H,
+                             size_t pitch, const sva_array_pair* pairs, int n_pairs,
+                             const int32_t* group_start, int n_groups, int route,
+                             const double* unit_baseline, double f, double pixel_size,
+                             int uniqueness, int mode, double* depth, uint8_t* n_valid,
+                             uint8_t* winner, float* subpix, uint16_t* maps, uint16_t* cost_min,
+                             uint16_t* cost_second, const int32_t* view_step, int sub,
+                             int max_diff, int min_agree, int max_conflict, uint8_t* agree,
+                             uint8_t* conflict, int check, int speckle_max_size,
+                             int speckle_max_diff, uint32_t* comp_size) {
+    return array_depth_post(mp, images, n_images, W, H, pitch, pairs, n_pairs, group_start,
+                            n_groups, route, unit_baseline, f, pixel_size, uniqueness, mode, depth,
+                            n_valid, winner, subpix, maps, cost_min, cost_second, view_step, sub,
+                            max_diff, min_agree, max_conflict, agree, conflict, check,
+                            speckle_max_size, speckle_max_diff, comp_size, false, 0, 1, 0, nullptr);
+}
+
+int sva_array_depth_filled(void* mp, const uint8_t* const* images, int n_images, int W, int H,
+                           size_t pitch, const sva_array_pair* pairs, int n_pairs,
+                           const int32_t* group_start, int n_groups, int route,
+                           const double* unit_baseline, double f, double pixel_size,
+                           int uniqueness, int mode, double* depth, uint8_t* n_valid,
+                           uint8_t* winner, float* subpix, uint16_t* maps, uint16_t* cost_min,
+                           uint16_t* cost_second, const int32_t* view_step, int sub, int max_diff,
+                           int min_agree, int max_conflict, uint8_t* agree, uint8_t* conflict,
+                           int check, int speckle_max_size, int speckle_max_diff,
+                           uint32_t* comp_size, int fill_max_dist, int fill_min_found,
+                           int fill_mode, uint8_t* n_found) {
+    return array_depth_post(mp, images, n_images, W, H, pitch, pairs, n_pairs, group_start,
+                            n_groups, route, unit_baseline, f, pixel_size, uniqueness, mode, depth,
+                            n_valid, winner, subpix, maps, cost_min, cost_second, view_step, sub,
+                            max_diff, min_agree, max_conflict, agree, conflict, check,
+                            speckle_max_size, speckle_max_diff, comp_size, true, fill_max_dist,
+                            fill_min_found, fill_mode, n_found);
 }
 
 }  // extern "C"

@@ -17,6 +17,7 @@
 
 #include "cost_mixed_math.h"
 #include "cross_check_math.h"
+#include "fill_math.h"
 #include "speckle_math.h"
 #include "sva_internal.h"
 #include "sva_tuning.h"
@@ -692,7 +693,7 @@ int sva_destroy(void* ctx) {
     c->census_side.release();
     for (DevBuf* b : {&c->census_l, &c->census_r, &c->cost, &c->paths, &c->ckpt, &c->scratch_u16,
                       &c->disp_r, &c->in_a, &c->in_b, &c->in_mask, &c->out_a, &c->out_b,
-                      &c->out_c, &c->in_c, &c->shifted, &c->keys, &c->counts, &c->total, &c->ref_keys, &c->refine_ws, &c->speckle_ws})
+                      &c->out_c, &c->in_c, &c->shifted, &c->keys, &c->counts, &c->total, &c->ref_keys, &c->refine_ws, &c->speckle_ws, &c->fill_ws})
         b->release();
     c->timer.release_all();
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
@@ -902,6 +903,11 @@ int sva_set_debug(void* ctx, int key, int64_t value) {
                 return fail(c, SVA_ERR_INVALID_ARG, "cross order must be -1, 0 or 1");
             c->dbg_cross_order = (int)value;
             return SVA_OK;
+        case SVA_DEBUG_FILL_SEGMENT:
+            if (value < 0 || value > 65536)
+                return fail(c, SVA_ERR_INVALID_ARG, "fill segment must be 0..65536");
+            c->dbg_fill_segment = (int)value;
+            return SVA_OK;
         default:
             return fail(c, SVA_ERR_INVALID_ARG, "unknown or read-only debug key");
     }
@@ -925,6 +931,9 @@ int sva_get_debug(void* ctx, int key, int64_t* value) {
         case SVA_DEBUG_REFINE_LAST_ROUTE: *value = c->last_refine_route; return SVA_OK;
         case SVA_DEBUG_CROSS_ORDER:
             *value = c->dbg_cross_order >= 0 ? c->dbg_cross_order : tune::kCrossTileMajor;
+            return SVA_OK;
+        case SVA_DEBUG_FILL_SEGMENT:
+            *value = c->dbg_fill_segment > 0 ? c->dbg_fill_segment : tune::kFillSegment;
             return SVA_OK;
         case SVA_DEBUG_SIDE_IDLE: {
             bool idle = true;
@@ -1977,6 +1986,97 @@ int sva_filter_speckles(void* ctx, const uint16_t* disps, const float* subpix, i
     g.down(out, dd, nnp * 2);
     g.down(out_sub, ds, nnp * 4);
     g.down(comp_size, dsize, nnp * 4);
+    return g.sync();
+}
+
+// ---------------------------------------------- hole filling --
+namespace {
+// The rules of sva_fill_holes and sva_fill_holes_d, in sva.h's order; the
+// pointers are the caller's (host or device), which is where overlap matters.
+int check_fill(Ctx* c, const uint16_t* disps, const float* subpix, int n, int W, int H,
+               int max_dist, int min_found, int mode, const uint16_t* out, const float* out_sub,
+               const uint8_t* n_found) {
+    if (!disps || !out) return fail(c, SVA_ERR_INVALID_ARG, "null pointer");
+    if (n < 1) return fail(c, SVA_ERR_INVALID_ARG, "n_maps must be >= 1");
+    if (W <= 0 || H <= 0) return fail(c, SVA_ERR_INVALID_ARG, "image size must be positive");
+    if ((unsigned long long)W * (unsigned long long)H >= (1ull << 31))
+        return fail(c, SVA_ERR_UNSUPPORTED, "hole filling needs W * H < 2^31");
+    if (const char* m = fl::thresholds_error(max_dist, min_found, mode))
+        return fail(c, SVA_ERR_INVALID_ARG, m);
+    if (out_sub && !subpix) return fail(c, SVA_ERR_INVALID_ARG, "out_sub needs subpix");
+    // the byte counts saturate: a frame too large for the address space overlaps everything
+    const unsigned long long px = (unsigned long long)W * H;
+    const size_t lim = ~(size_t)0;
+    const size_t b8 = px > lim / 4 / (size_t)n ? lim / 4 : (size_t)px * (size_t)n;
+    const size_t b16 = b8 * 2, b32 = b8 * 4;
+    if ((out != disps && ranges_overlap(out, b16, disps, b16)) ||
+        ranges_overlap(out, b16, subpix, b32) || ranges_overlap(out, b16, out_sub, b32) ||
+        ranges_overlap(out, b16, n_found, b8) || ranges_overlap(out_sub, b32, disps, b16) ||
+        bad_overlap(out_sub, subpix, b32) || ranges_overlap(out_sub, b32, n_found, b8) ||
+        ranges_overlap(n_found, b8, disps, b16) || ranges_overlap(n_found, b8, subpix, b32))
+        return fail(c, SVA_ERR_INVALID_ARG,
+                    "an output overlaps an input or another output (in place: out == disps, "
+                    "out_sub == subpix)");
+    return SVA_OK;
+}
+
+// The workspace, then the launches.  max_dist = 0 is a copy and takes no workspace.
+int run_fill(Ctx* c, const uint16_t* disps, const float* subpix, int n, int W, int H,
+             uint16_t invalid, int max_dist, int min_found, int mode, uint16_t* out, float* out_sub,
+             uint8_t* n_found) {
+    uint32_t* keys = nullptr;
+    if (max_dist != 0) {
+        const unsigned long long planes = (unsigned long long)W * H * (unsigned long long)n;
+        if (planes > (~(size_t)0) / 32)
+            return fail(c, SVA_ERR_OUT_OF_MEMORY, "fill workspace: larger than the address space");
+        const hipError_t e = c->fill_ws.ensure((size_t)planes * 32);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();   // the failed allocation is reported here, not by a later call
+            return fail(c, SVA_ERR_OUT_OF_MEMORY,
+                        std::string("fill workspace: ") + hipGetErrorString(e));
+        }
+        keys = (uint32_t*)c->fill_ws.ptr;
+    }
+    const int segment = c->dbg_fill_segment > 0 ? c->dbg_fill_segment : tune::kFillSegment;
+    SVA_HIP(c, launch_fill(*c, disps, subpix, n, W, H, invalid, max_dist, min_found, mode, segment,
+                           keys, out, out_sub, n_found),
+            "fill launch");
+    return SVA_OK;
+}
+}  // namespace
+
+int sva_fill_holes_d(void* ctx, const uint16_t* disps, const float* subpix, int n, int W, int H,
+                     uint16_t invalid, int max_dist, int min_found, int mode, uint16_t* out,
+                     float* out_sub, uint8_t* n_found) {
+    Ctx* c = as_ctx(ctx);
+    SVA_CHECK_CTX(c);
+    if (int s = check_fill(c, disps, subpix, n, W, H, max_dist, min_found, mode, out, out_sub,
+                           n_found))
+        return s;
+    return run_fill(c, disps, subpix, n, W, H, invalid, max_dist, min_found, mode, out, out_sub,
+                    n_found);
+}
+
+// On the device the staged maps are filled in place.
+int sva_fill_holes(void* ctx, const uint16_t* disps, const float* subpix, int n, int W, int H,
+                   uint16_t invalid, int max_dist, int min_found, int mode, uint16_t* out,
+                   float* out_sub, uint8_t* n_found) {
+    Ctx* c = as_ctx(ctx);
+    SVA_CHECK_CTX(c);
+    if (int s = check_fill(c, disps, subpix, n, W, H, max_dist, min_found, mode, out, out_sub,
+                           n_found))
+        return s;
+    const size_t nnp = (size_t)W * H * (size_t)n;
+    Staging g{c};
+    uint16_t* dd = g.up<uint16_t>(c->in_a, disps, nnp * 2);
+    float* ds = out_sub ? g.up<float>(c->in_mask, subpix, nnp * 4) : nullptr;
+    uint8_t* dfound = n_found ? g.out<uint8_t>(c->out_c, nnp) : nullptr;
+    if (g.st) return g.st;
+    if (int s = run_fill(c, dd, ds, n, W, H, invalid, max_dist, min_found, mode, dd, ds, dfound))
+        return s;
+    g.down(out, dd, nnp * 2);
+    g.down(out_sub, ds, nnp * 4);
+    g.down(n_found, dfound, nnp);
     return g.sync();
 }
 

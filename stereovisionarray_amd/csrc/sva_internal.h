@@ -72,6 +72,10 @@ struct Ctx {
     int dbg_cross_order = -1;
     // the speckle filter's label and count planes (speckle.hip; sva.h gives the size)
     DevBuf speckle_ws;
+    // hole filling's key planes (fill.hip; sva.h gives the size), and
+    // SVA_DEBUG_FILL_SEGMENT: the scan's segment length (0 = tune::kFillSegment)
+    DevBuf fill_ws;
+    int dbg_fill_segment = 0;
     // Mode R's split plane loop: one first-minimum key per pixel (refpath.hip).
     // ref_finalize_kernel puts every key it reads back to all-ones, so after
     // the first call only a grown buffer needs the memset: ref_keys_clean =
@@ -257,6 +261,13 @@ hipError_t launch_cross_check(Ctx& c, const uint16_t* disps, const float* subpix
 hipError_t launch_speckle(Ctx& c, const uint16_t* disps, const float* subpix, int n, int W, int H,
                           uint16_t invalid, int max_size, int max_diff, uint32_t* label,
                           uint32_t* count, uint16_t* out, float* out_sub, uint32_t* comp_size);
+// fill.hip -- hole filling: n maps [n][H][W], W * H < 2^31;
+// keys: u32 workspace planes [n][8][H][W], null iff max_dist = 0 (a copy);
+// segment >= 1: the scan's segment length; subpix / out_sub (f32) and n_found
+// (u8) nullable, out_sub needs subpix; out may be disps and out_sub subpix.
+hipError_t launch_fill(Ctx& c, const uint16_t* disps, const float* subpix, int n, int W, int H,
+                       uint16_t invalid, int max_dist, int min_found, int mode, int segment,
+                       uint32_t* keys, uint16_t* out, float* out_sub, uint8_t* n_found);
 // refpath.hip
 hipError_t launch_ref_endpoints(Ctx& c, int W, int H, const sva_camera& cref,
                                 const sva_camera& coth, int k, double t_near, double t_far,

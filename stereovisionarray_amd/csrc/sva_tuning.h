@@ -281,5 +281,31 @@ constexpr int kCrossTileMajor = 1;
 // No winner where the time is (n = 25), so the shape the layout argues for stays.
 constexpr int kSpeckleTileW = 64, kSpeckleTileH = 16;
 
+// ---- fill.hip ---------------------------------------------
+// The scan cuts every line into segments of kFillSegment steps, one thread each,
+// which begins max_dist steps early: a thread's dependent chain is kFillSegment
+// + max_dist steps and it reads (kFillSegment + max_dist) / kFillSegment times
+// the map.  A short segment gives more threads and more re-reading, a long one
+// a longer chain.  kFillRing pixels are loaded ahead of the chain.
+// One sweep (tools/bench_fill.py --kernel, the segment set through
+// SVA_DEBUG_FILL_SEGMENT on one warm context in one session; 1080p, n = 25
+// synthetic maps with 5 % holes, u16 planes only, 15 calls, stream events around
+// the two launches; profiles/fill/kernel_1080p.json), ms median (min-max):
+//   segment   max_dist 16          max_dist 64          max_dist 255
+//   8         2.164 (2.152-2.173)  4.371 (4.354-4.401)  12.807 (12.789-12.824)
+//   16        1.839 (1.825-1.843)  2.819 (2.799-2.838)   6.766 (6.740-6.790)
+//   32        1.752 (1.736-1.760)  2.166 (2.142-2.185)   4.041 (4.014-4.084)
+//   64        1.631 (1.618-1.658)  1.835 (1.821-1.856)   2.893 (2.846-2.947)
+//   128       1.807 (1.786-1.876)  1.927 (1.887-1.964)   2.474 (2.430-2.538)
+// 64 wins outside the spreads at the distances an occlusion band has (16, 64);
+// 128 wins at 255 only, by 0.42 ms.  The apply launch is 0.31-0.35 ms of every
+// cell.  kFillRing was not swept.
+constexpr int kFillSegment = 64;
+constexpr int kFillRing = 4;
+// sva_array_depth_filled fills at most this many maps per call of
+// sva_fill_holes_d, which bounds the key planes (32 bytes per pixel and map) to
+// 531 MB at 1080p.
+constexpr int kFillFrameMaps = 8;
+
 }  // namespace tune
 }  // namespace sva
