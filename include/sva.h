@@ -794,6 +794,56 @@ int sva_fill_holes(void* ctx, const uint16_t* disps, const float* subpix, int n_
                    int height, uint16_t invalid, int max_dist, int min_found, int mode,
                    uint16_t* out, float* out_sub, uint8_t* n_found);
 
+/* Weighted median filter: edge-aware smoothing of n_maps >= 1
+ * disparity maps disps [n_maps][H][W] u16 (device / host) by a guide image per
+ * map, the refinement step of cost-volume filtering (Rhemann et al. 2011; Ma et
+ * al. 2013).  A pixel is valid iff d != invalid and d != 0.  guides: a HOST
+ * array of n_maps u8 images (device pointers for _d, host pointers for the host
+ * form), rows guide_pitch >= width bytes apart; weights: a HOST array of 256
+ * u16 in both forms; both are read before the call returns, and both are null
+ * for the unguided filter, whose weights are all 1: the plain (2r + 1)^2 median
+ * over the valid pixels.  select (nullable): [n_maps][H][W] u8.
+ * Pixel p is CONSIDERED iff (select is null or select[p] != 0) and (fill != 0 or
+ * p is valid).  Its CANDIDATES are the pixels q inside the frame with
+ * |qx - px| <= radius and |qy - py| <= radius, p included, that are valid and
+ * have weight w_q = weights[|g(p) - g(q)|] > 0; n is their number and T the sum
+ * of their weights.  Sorted by (d, qy, qx) ascending, the PICK is the first
+ * candidate at which 2 * (the weights summed up to and including it) >= T: the
+ * lower weighted median, from one source pixel.
+ *   considered and n >= min_support: out[p] = the pick's d
+ *   otherwise:                       out[p] = disps[p], bit for bit
+ * so fill = 1 gives a hole with enough support a value and fill = 0 leaves holes
+ * as they are.  subpix (nullable): [n_maps][H][W] f32; out_sub (nullable, needs
+ * subpix) gets the 32 bits of subpix at the pick's source pixel where p was
+ * written and those of subpix[p] elsewhere, NaN included.  support (nullable):
+ * [n_maps][H][W] u16, n at the considered pixels and 0 elsewhere.  radius in
+ * 1..SVA_WMED_MAX_RADIUS, min_support in 1..961, fill in 0..1.  Maps never
+ * interact; only the input map is read.  Integer-only and independent of any
+ * ordering: every output byte has one right value.  In place is NOT offered:
+ * the window reads neighbours that other threads would be writing.
+ * No workspace on the device form; the host form stages its planes.
+ * Returned before anything is launched, in this order: SVA_ERR_INVALID_ARG for
+ * a null disps or out, n_maps < 1, a width or height < 1; SVA_ERR_UNSUPPORTED
+ * for width * height >= 2^31; SVA_ERR_INVALID_ARG for radius outside 1..15,
+ * min_support outside 1..961, fill outside 0..1, guides without weights or
+ * weights without guides, a null entry in guides, guide_pitch < width, out_sub
+ * without subpix, or any overlap of an output (out, out_sub, support) with an
+ * input (disps, subpix, select, a guide) or with another output.  _d is
+ * asynchronous on the context stream and is timed as "wmed": one launch per
+ * 64 maps. */
+#define SVA_WMED_MAX_RADIUS 15
+int sva_weighted_median_d(void* ctx, const uint16_t* disps, const float* subpix,
+                          const uint8_t* const* guides, size_t guide_pitch,
+                          const uint16_t* weights, const uint8_t* select, int n_maps,
+                          int width, int height, uint16_t invalid, int radius,
+                          int min_support, int fill, uint16_t* out, float* out_sub,
+                          uint16_t* support);
+int sva_weighted_median(void* ctx, const uint16_t* disps, const float* subpix,
+                        const uint8_t* const* guides, size_t guide_pitch,
+                        const uint16_t* weights, const uint8_t* select, int n_maps, int width,
+                        int height, uint16_t invalid, int radius, int min_support, int fill,
+                        uint16_t* out, float* out_sub, uint16_t* support);
+
 /* Disparity -> depth, CameraStereoVision.cpp:47,98-100 (f64; 0 where disp 0). */
 int sva_disparity_to_depth_d(void* ctx, const uint8_t* disp, int n, double cam_distance,
                              double f, double pixel_size, double* depth);
@@ -1062,6 +1112,37 @@ int sva_array_depth_filled(void* multi, const uint8_t* const* images, int n_imag
                            int check, int speckle_max_size, int speckle_max_diff,
                            uint32_t* comp_size, int fill_max_dist, int fill_min_found,
                            int fill_mode, uint8_t* n_found);
+/* An array frame with the weighted median filter:
+ * sva_array_depth_filled's arguments, then wmed_radius, wmed_weights (a host
+ * array of 256 u16; null: the unguided filter), wmed_min_support, wmed_select
+ * and support (nullable): host [n_jobs][H][W] u16, one plane per map.
+ * devices[0] runs sva_weighted_median_d with fill = 1 over every job's map --
+ * and its f32 plane with sub = 1 -- after the fill and before the depth step, on
+ * every route; the guide of a job is its reference view, which is uploaded to
+ * devices[0] as well if the job ran elsewhere.  wmed_select = 0 filters every
+ * pixel; 1 filters only the pixels the fill looked at: the fill's n_found plane
+ * is the select plane (kept even if n_found is null), so with fill_max_dist = 0
+ * it changes nothing and the outputs are sva_array_depth_filled's bit for bit.
+ * maps, subpix, depth, n_valid and winner are those of the SMOOTHED maps; the
+ * cost planes stay the matcher's, so SVA_FUSE_MEDIAN is the sensible fusion mode.
+ * Bit for bit the stand-alone composition: the filled frame's maps through
+ * sva_weighted_median and the matching sva_fuse_depth*.
+ * After all of sva_array_depth_filled's rules, in this order,
+ * SVA_ERR_INVALID_ARG for: wmed_radius outside 1..15; wmed_min_support outside
+ * 1..961; wmed_select outside 0..1.  Before anything is launched. */
+int sva_array_depth_smoothed(void* multi, const uint8_t* const* images, int n_images, int width,
+                             int height, size_t pitch, const sva_array_pair* pairs, int n_pairs,
+                             const int32_t* group_start, int n_groups, int route,
+                             const double* unit_baseline, double f, double pixel_size,
+                             int uniqueness, int mode, double* depth, uint8_t* n_valid,
+                             uint8_t* winner, float* subpix, uint16_t* maps, uint16_t* cost_min,
+                             uint16_t* cost_second, const int32_t* view_step, int sub,
+                             int max_diff, int min_agree, int max_conflict, uint8_t* agree,
+                             uint8_t* conflict, int check, int speckle_max_size,
+                             int speckle_max_diff, uint32_t* comp_size, int fill_max_dist,
+                             int fill_min_found, int fill_mode, uint8_t* n_found, int wmed_radius,
+                             const uint16_t* wmed_weights, int wmed_min_support, int wmed_select,
+                             uint16_t* support);
 
 #ifdef __cplusplus
 }

@@ -1081,6 +1081,123 @@ inline std::vector<std::vector<double>> computeArrayDepthFilled(
 }
 
 
+// ---- weighted median filter --------------------------------
+
+// The weight table of weightedMedian for an intensity scale sigma > 0: entry i =
+// lround(1024 * exp(-i / sigma)), so equal intensities weigh 1024 and a
+// difference of about 7 sigma and more weighs nothing.
+inline std::array<uint16_t, 256> wmedWeights(double sigma) {
+    if (!(sigma > 0)) throw Error(SVA_ERR_INVALID_ARG, "wmedWeights: sigma must be positive");
+    std::array<uint16_t, 256> w{};
+    for (int i = 0; i < 256; i++) w[i] = (uint16_t)std::lround(1024.0 * std::exp(-i / sigma));
+    return w;
+}
+
+// What weightedMedian makes of each map: the filtered map, the optional f32 map,
+// and the number of candidates in the window (0 where the pixel was not looked at).
+struct MedianFiltered {
+    std::vector<std::vector<uint16_t>> maps;
+    std::vector<std::vector<float>> subpix;       // empty unless sub-pixel maps went in
+    std::vector<std::vector<uint16_t>> support;
+};
+
+// The weighted median filter of each map (sva_weighted_median): a pixel takes
+// the lower weighted median of the valid pixels of its (2 * radius + 1)^2
+// window, each weighted by weights[|guide(p) - guide(q)|], if at least
+// min_support of them carry weight; in subpix the source pixel's f32 value.
+// guides: empty (then weights must be null: the plain median over the valid
+// pixels), or one W x H view per map, all of one pitch.  select: empty, or one
+// u8 plane per map -- only its non-zero pixels are looked at.  fill = true also
+// gives holes a value.  maps[i] is W*H u16.
+inline MedianFiltered weightedMedian(Engine& eng, const std::vector<std::vector<uint16_t>>& maps,
+                                     const std::vector<std::vector<float>>& subpix,
+                                     const std::vector<ImageView>& guides,
+                                     const std::array<uint16_t, 256>* weights, int W, int H,
+                                     int radius, int min_support = 1, bool fill = true,
+                                     const std::vector<std::vector<uint8_t>>& select = {},
+                                     uint16_t invalid = 0xFFFF) {
+    const size_t np = (size_t)W * H, n = maps.size();
+    if (maps.empty() || (!subpix.empty() && subpix.size() != n) ||
+        (!guides.empty() && guides.size() != n) || (!select.empty() && select.size() != n))
+        throw Error(SVA_ERR_INVALID_ARG, "weightedMedian: need one plane per map");
+    std::vector<uint16_t> d(np * n), out(np * n), sup(np * n);
+    std::vector<float> s(subpix.empty() ? 0 : np * n), os(s.size());
+    std::vector<uint8_t> sel(select.empty() ? 0 : np * n);
+    std::vector<const uint8_t*> g;
+    for (size_t i = 0; i < n; i++) {
+        if (maps[i].size() != np || (!subpix.empty() && subpix[i].size() != np) ||
+            (!select.empty() && select[i].size() != np))
+            throw Error(SVA_ERR_INVALID_ARG, "weightedMedian: map size");
+        std::copy(maps[i].begin(), maps[i].end(), d.begin() + i * np);
+        if (!subpix.empty()) std::copy(subpix[i].begin(), subpix[i].end(), s.begin() + i * np);
+        if (!select.empty()) std::copy(select[i].begin(), select[i].end(), sel.begin() + i * np);
+        if (!guides.empty()) {
+            if (guides[i].width != W || guides[i].height != H || guides[i].pitch != guides[0].pitch)
+                throw Error(SVA_ERR_INVALID_ARG, "weightedMedian: guide size or pitch");
+            g.push_back(guides[i].data);
+        }
+    }
+    eng.check(sva_weighted_median(eng.handle(), d.data(), s.empty() ? nullptr : s.data(),
+                                  g.empty() ? nullptr : g.data(), g.empty() ? 0 : guides[0].pitch,
+                                  weights ? weights->data() : nullptr,
+                                  sel.empty() ? nullptr : sel.data(), (int)n, W, H, invalid, radius,
+                                  min_support, fill ? 1 : 0, out.data(),
+                                  s.empty() ? nullptr : os.data(), sup.data()));
+    MedianFiltered r;
+    for (size_t i = 0; i < n; i++) {
+        r.maps.emplace_back(out.begin() + i * np, out.begin() + (i + 1) * np);
+        if (!s.empty()) r.subpix.emplace_back(os.begin() + i * np, os.begin() + (i + 1) * np);
+        r.support.emplace_back(sup.begin() + i * np, sup.begin() + (i + 1) * np);
+    }
+    return r;
+}
+
+// computeArrayDepthFilled's frame with the weighted median filter over every
+// job's map after the fill and before depth (sva_array_depth_smoothed), guided
+// by the job's reference view; weights null: the unguided median.  wmed_select
+// false filters every pixel, true only those the fill looked at.  maps, support
+// (nullable): one plane per pair in `pairs` order, or one per reference camera.
+inline std::vector<std::vector<double>> computeArrayDepthSmoothed(
+    MultiEngine& m, const std::vector<ImageView>& images, const std::vector<Camera>& cameras,
+    const std::vector<std::array<int, 2>>& pairs, const sva_sgm_params& p, int wmed_radius,
+    const std::array<uint16_t, 256>* weights, int wmed_min_support = 1, bool wmed_select = false,
+    int fill_max_dist = 0, int fill_min_found = 1, int fill_mode = SVA_FILL_SECOND,
+    int speckle_max_size = 0, int speckle_max_diff = 0, int route = SVA_ARRAY_GROUPS,
+    bool check = false, bool sub = false, int max_diff = 1, int min_agree = 1,
+    int max_conflict = 0, int uniqueness = 0, int mode = SVA_FUSE_MEDIAN, double pitch = 0.05,
+    std::vector<std::vector<uint16_t>>* maps = nullptr,
+    std::vector<std::vector<uint16_t>>* support = nullptr) {
+    const detail::ArrayFrame fr = detail::arrayFrame(images, cameras, pairs, p, pitch,
+                                                     "computeArrayDepthSmoothed");
+    std::vector<double> unit;
+    if (route == SVA_ARRAY_GROUPS_MIXED) unit = detail::unitBaselines(fr, 1, pitch);
+    std::vector<int32_t> vs;
+    for (const Camera& c : cameras) {
+        vs.push_back(-(int32_t)std::lround((c.pos3D.x - cameras[0].pos3D.x) / pitch));
+        vs.push_back(-(int32_t)std::lround((c.pos3D.y - cameras[0].pos3D.y) / pitch));
+    }
+    const bool per_group = route != SVA_ARRAY_PAIRS;
+    const size_t np = (size_t)fr.W * fr.H;
+    std::vector<uint16_t> sup(support ? np * (per_group ? fr.refs.size() : fr.ap.size()) : 0);
+    auto depth = detail::arrayDepth(fr, cameras, pairs.size(), per_group, maps,
+                                    [&](double f, double pixel_size, double* depth, uint16_t* all) {
+        m.check(fr.call(sva_array_depth_smoothed, m.handle(), route,
+                        unit.empty() ? (const double*)nullptr : (const double*)unit.data(), f,
+                        pixel_size, uniqueness, mode, depth, (uint8_t*)nullptr, (uint8_t*)nullptr,
+                        (float*)nullptr, all, (uint16_t*)nullptr, (uint16_t*)nullptr,
+                        (const int32_t*)vs.data(), sub ? 1 : 0, max_diff, min_agree, max_conflict,
+                        (uint8_t*)nullptr, (uint8_t*)nullptr, check ? 1 : 0, speckle_max_size,
+                        speckle_max_diff, (uint32_t*)nullptr, fill_max_dist, fill_min_found,
+                        fill_mode, (uint8_t*)nullptr, wmed_radius,
+                        weights ? weights->data() : (const uint16_t*)nullptr, wmed_min_support,
+                        wmed_select ? 1 : 0, support ? sup.data() : (uint16_t*)nullptr));
+    });
+    if (support && per_group) *support = fr.split(sup);
+    else if (support) fr.scatter(sup, pairs.size(), support);
+    return depth;
+}
+
+
 // ---- refinement and 3-D output ----
 // The reference's names and argument meaning; cv::Mat becomes ImageView (u8)
 // or a dense W*H std::vector<double>.  Pixels a routine does not write keep

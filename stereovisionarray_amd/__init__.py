@@ -77,7 +77,9 @@ EXPORTED = [
     "sva_fuse_depth_conf_sub_d", "sva_array_depth_sub", "sva_cross_check", "sva_cross_check_d",
     "sva_array_depth_checked", "sva_filter_speckles", "sva_filter_speckles_d",
     "sva_array_depth_filtered", "sva_fill_holes", "sva_fill_holes_d", "sva_array_depth_filled",
+    "sva_weighted_median", "sva_weighted_median_d", "sva_array_depth_smoothed",
 ]
+SVA_WMED_MAX_RADIUS = 15
 SVA_FILL_MIN = 0
 SVA_FILL_SECOND = 1
 SVA_FILL_MEDIAN = 2
@@ -316,6 +318,14 @@ def _load() -> ct.CDLL:
                                          i32, i32, P(dbl), dbl, dbl, i32, i32, vp, vp, vp, vp, vp,
                                          vp, vp, P(ct.c_int32), i32, i32, i32, i32, vp, vp, i32,
                                          i32, i32, vp, i32, i32, i32, vp]),
+        "sva_array_depth_smoothed": (i32, [vp, P(vp), i32, i32, i32, sz, P(ArrayPair), i32, P(i32),
+                                           i32, i32, P(dbl), dbl, dbl, i32, i32, vp, vp, vp, vp, vp,
+                                           vp, vp, P(ct.c_int32), i32, i32, i32, i32, vp, vp, i32,
+                                           i32, i32, vp, i32, i32, i32, vp, i32, vp, i32, i32, vp]),
+        "sva_weighted_median_d": (i32, [vp, vp, vp, vp, sz, vp, vp, i32, i32, i32, ct.c_uint16, i32,
+                                        i32, i32, vp, vp, vp]),
+        "sva_weighted_median": (i32, [vp, vp, vp, vp, sz, vp, vp, i32, i32, i32, ct.c_uint16, i32,
+                                      i32, i32, vp, vp, vp]),
         "sva_resize_linear_f64_d": (i32, [vp, vp, i32, i32, vp, i32, i32]),
         "sva_resize_linear_f64": (i32, [vp, vp, i32, i32, vp, i32, i32]),
         "sva_ref_error_d": (i32, [vp, vp, i32, i32, vp, i32, i32, ct.c_double, vp]),
@@ -336,6 +346,15 @@ def _load() -> ct.CDLL:
 
 
 lib = _load()
+
+
+def wmed_weights(sigma) -> np.ndarray:
+    """The weight table of the weighted median filter for an
+    intensity scale sigma > 0: 256 u16, entry i = round(1024 * exp(-i / sigma))
+    (sva.hpp's wmedWeights)."""
+    if not sigma > 0:
+        raise ValueError("sigma must be positive")
+    return np.floor(1024.0 * np.exp(-np.arange(256) / float(sigma)) + 0.5).astype(np.uint16)
 
 
 def default_params(**kw) -> SgmParams:
@@ -997,6 +1016,56 @@ class Context:
                                        int(max_dist), int(min_found), int(mode), _ptr(out),
                                        _ptr(out_sub), _ptr(n_found)))
 
+    def weighted_median(self, disps: np.ndarray, radius, guides=None, weights=None, subpix=None,
+                        select=None, min_support=1, fill=1, invalid=0xFFFF, want_support=True):
+        """(out, out_sub or None, support or None): sva_weighted_median, the
+        weighted median filter of n maps [n][H][W] u16.  guides:
+        n u8 images [H][W] (views are passed with their row stride), weights: 256
+        u16 (wmed_weights); both None for the plain median over the valid pixels.
+        A considered pixel (select, fill) with at least min_support candidates in
+        its (2 * radius + 1)^2 window takes their lower weighted median; out_sub
+        (with subpix) takes the source pixel's f32 value; support counts the
+        candidates."""
+        d = np.ascontiguousarray(disps, dtype=np.uint16)
+        s = None if subpix is None else np.ascontiguousarray(subpix, dtype=np.float32)
+        sel = None if select is None else np.ascontiguousarray(select, dtype=np.uint8)
+        N, H, W = d.shape
+        assert s is None or s.shape == d.shape
+        assert sel is None or sel.shape == d.shape
+        garr, w, pitch, keep = None, None, 0, []
+        if weights is not None:
+            w = np.ascontiguousarray(weights, dtype=np.uint16)
+            assert w.shape == (256,)
+        if guides is not None:
+            assert len(guides) == N
+            for g in guides:
+                assert g.dtype == np.uint8 and g.shape == (H, W) and (W == 1 or g.strides[1] == 1)
+                keep.append(g)
+            strides = {int(g.strides[0]) for g in keep} if H > 1 else {W}
+            if len(strides) != 1 or min(strides) < W:
+                keep = [np.ascontiguousarray(g) for g in keep]
+                strides = {W}
+            pitch = strides.pop()
+            garr = (ct.c_void_p * N)(*[g.ctypes.data for g in keep])
+        out = np.zeros_like(d)
+        osub = None if s is None else np.zeros_like(s)
+        sup = np.zeros(d.shape, np.uint16) if want_support else None
+        self._chk(lib.sva_weighted_median(self.h, _ptr(d), _ptr(s), garr, pitch, _ptr(w), _ptr(sel),
+                                          N, W, H, invalid, int(radius), int(min_support),
+                                          int(fill), _ptr(out), _ptr(osub), _ptr(sup)))
+        return out, osub, sup
+
+    def weighted_median_d(self, disps, subpix, guides, guide_pitch, weights, select, n_maps, W, H,
+                          invalid, radius, min_support, fill, out, out_sub=None, support=None):
+        """sva_weighted_median_d on device pointers; guides: a sequence of n_maps
+        device addresses or None, weights: a numpy array of 256 u16 or None."""
+        garr = None if guides is None else (ct.c_void_p * len(guides))(*[None if g is None else int(g) for g in guides])
+        w = None if weights is None else np.ascontiguousarray(weights, dtype=np.uint16)
+        self._chk(lib.sva_weighted_median_d(self.h, _ptr(disps), _ptr(subpix), garr,
+                                            int(guide_pitch), _ptr(w), _ptr(select), n_maps, W, H,
+                                            invalid, int(radius), int(min_support), int(fill),
+                                            _ptr(out), _ptr(out_sub), _ptr(support)))
+
     def disparity_to_depth(self, disp: np.ndarray, cam_distance, f, pixel_size):
         d = np.ascontiguousarray(disp, dtype=np.uint8)
         out = np.zeros(d.shape, np.float64)
@@ -1274,6 +1343,50 @@ class Multi:
             int(max_diff), int(min_agree), int(max_conflict), _ptr(r["agree"]), _ptr(r["conflict"]),
             int(check), int(speckle_max_size), int(speckle_max_diff), _ptr(r["comp_size"]),
             int(fill_max_dist), int(fill_min_found), int(fill_mode), _ptr(r["n_found"])))
+        return r
+
+    def array_depth_smoothed(self, images, pairs, group_start, f, pixel_size, wmed_radius,
+                             wmed_weights=None, wmed_min_support=1, wmed_select=0,
+                             fill_max_dist=0, fill_min_found=1, fill_mode=SVA_FILL_SECOND,
+                             speckle_max_size=0, speckle_max_diff=0, check=0, view_step=None,
+                             route=SVA_ARRAY_GROUPS, unit_baseline=None, uniqueness=0,
+                             mode=SVA_FUSE_MEDIAN, sub=0, max_diff=1, min_agree=1, max_conflict=0,
+                             want_sub=False, want_maps=False, want_costs=False, want_counts=False,
+                             want_size=False, want_n_valid=False, want_winner=False,
+                             want_found=False, want_support=False):
+        """sva_array_depth_smoothed: array_depth_filled's frame with the weighted
+        median filter over every job's map after the fill and
+        before depth, guided by the job's reference view (wmed_weights None: the
+        unguided median).  wmed_select 0 filters every pixel, 1 only those the fill
+        looked at.  Returns array_depth_filled's dict with support [jobs,H,W] u16
+        added (None unless asked for)."""
+        fr = _ArrayFrame(images, pairs, group_start)
+        nj = len(pairs) if int(route) == SVA_ARRAY_PAIRS else fr.G
+        ub = None if unit_baseline is None else \
+            (ct.c_double * max(1, len(unit_baseline)))(*[float(v) for v in unit_baseline])
+        vs = None if view_step is None else _steps(view_step, len(view_step))
+        w = None if wmed_weights is None else np.ascontiguousarray(wmed_weights, dtype=np.uint16)
+        assert w is None or w.shape == (256,)
+        r = dict(depth=fr.planes(fr.G, np.float64),
+                 n_valid=fr.planes(fr.G, np.uint8, want_n_valid),
+                 winner=fr.planes(fr.G, np.uint8, want_winner),
+                 subpix=fr.planes(nj, np.float32, want_sub), maps=fr.planes(nj, np.uint16, want_maps),
+                 cost_min=fr.planes(nj, np.uint16, want_costs),
+                 cost_second=fr.planes(nj, np.uint16, want_costs),
+                 agree=fr.planes(fr.G, np.uint8, want_counts),
+                 conflict=fr.planes(fr.G, np.uint8, want_counts),
+                 comp_size=fr.planes(nj, np.uint32, want_size),
+                 n_found=fr.planes(nj, np.uint8, want_found),
+                 support=fr.planes(nj, np.uint16, want_support))
+        self._chk(lib.sva_array_depth_smoothed(
+            self.h, *fr.head, int(route), ub, f, pixel_size, int(uniqueness), int(mode),
+            _ptr(r["depth"]), _ptr(r["n_valid"]), _ptr(r["winner"]), _ptr(r["subpix"]),
+            _ptr(r["maps"]), _ptr(r["cost_min"]), _ptr(r["cost_second"]), vs, int(sub),
+            int(max_diff), int(min_agree), int(max_conflict), _ptr(r["agree"]), _ptr(r["conflict"]),
+            int(check), int(speckle_max_size), int(speckle_max_diff), _ptr(r["comp_size"]),
+            int(fill_max_dist), int(fill_min_found), int(fill_mode), _ptr(r["n_found"]),
+            int(wmed_radius), _ptr(w), int(wmed_min_support), int(wmed_select),
+            _ptr(r["support"])))
         return r
 
     def array_depth(self, images, pairs, group_start, f, pixel_size, want_maps=False):

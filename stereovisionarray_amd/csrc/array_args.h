@@ -1,5 +1,5 @@
 // array_args.h -- the arguments of one camera-array frame (sva_array_depth,
-// _conf, _mb, _mixed, _sub, _checked, _filtered and _filled) and
+// _conf, _mb, _mixed, _sub, _checked, _filtered, _filled and _smoothed) and
 // their validation, shared by multi.cpp and the host test programs
 // (tests/test_array_args_cpu.py, tests/test_array_sub_args_cpu.py,
 // tests/test_cross_check_cpu.py, tests/test_speckle_cpu.py and
@@ -20,6 +20,7 @@
 #include "speckle_math.h"
 #include "sva.h"
 #include "sva_native_d.h"
+#include "wmedian_math.h"
 
 namespace sva {
 
@@ -80,6 +81,14 @@ struct ArrayArgs {
     bool fill = false;
     int fill_max_dist = 0, fill_min_found = 1, fill_mode = 0;
     uint8_t* n_found = nullptr;               // host, per job, nullable
+    // wmed (sva_array_depth_smoothed; fill is set too): the jobs'
+    // maps then go through sva_weighted_median_d, guided by each job's reference
+    // view (wmed_weights null: unguided), into a workspace that step 4 reads.
+    // wmed_select 0: every pixel, fill = 1; 1: only the pixels the fill looked at
+    bool wmed = false;
+    int wmed_radius = 1, wmed_min_support = 1, wmed_select = 0;
+    const uint16_t* wmed_weights = nullptr;   // host, 256 entries, nullable
+    uint16_t* support = nullptr;              // host, per job, nullable
 };
 
 inline int check_params(const sva_sgm_params& p) {
@@ -260,7 +269,9 @@ inline int check_frame_args(const ArrayArgs& a, std::string& msg, std::vector<in
 // -- in this order: a check outside 0 / 1; with check = 0, an agree or conflict
 // plane, then a subpix plane without sub; speckle_max_size < 0;
 // speckle_max_diff < 0.  With a.fill (sva_array_depth_filled) after those:
-// fill_max_dist, fill_min_found, fill_mode out of range.
+// fill_max_dist, fill_min_found, fill_mode out of range.  With a.wmed
+// (sva_array_depth_smoothed) after those: wmed_radius, wmed_min_support out of
+// range, wmed_select outside 0 / 1.
 inline int check_array_args(const ArrayArgs& a, std::string& msg, std::vector<int32_t>& ratio) {
     if (int st = check_frame_args(a, msg, ratio)) return st;
     if (!a.speckle) return SVA_OK;
@@ -277,7 +288,38 @@ inline int check_array_args(const ArrayArgs& a, std::string& msg, std::vector<in
     if (a.fill)
         if (const char* m = fl::thresholds_error(a.fill_max_dist, a.fill_min_found, a.fill_mode))
             return fail(m);
+    if (a.wmed) {
+        if (const char* m = wm::thresholds_error(a.wmed_radius, a.wmed_min_support, 1))
+            return fail(m);
+        if (a.wmed_select != 0 && a.wmed_select != 1) return fail("wmed select must be 0 or 1");
+    }
     return SVA_OK;
+}
+
+// Which views does each device need?  Pair j runs on device dev_of[j] and needs
+// its ref and its other there.  With refs_on_0 (sva_array_depth_smoothed: the
+// guide of a job is its reference view, and the filter runs on device 0) the
+// reference view of every pair is needed on device 0 as well.  Out: slot_of[d][v],
+// the slot of view v in device d's image buffer (-1: not needed there), slots
+// numbered in the order the pairs name them, the extra references of device 0
+// last; n_need[d], the number of slots; used[v], whether any device needs v.
+inline void plan_views(int n_devices, int n_images, const sva_array_pair* pairs, int n_pairs,
+                       const int32_t* dev_of, bool refs_on_0,
+                       std::vector<std::vector<int>>& slot_of, std::vector<int>& n_need,
+                       std::vector<char>& used) {
+    slot_of.assign(n_devices, std::vector<int>(n_images, -1));
+    n_need.assign(n_devices, 0);
+    used.assign(n_images, 0);
+    auto need = [&](int d, int v) {
+        used[v] = 1;
+        int& s = slot_of[d][v];
+        if (s < 0) s = n_need[d]++;
+    };
+    for (int j = 0; j < n_pairs; j++) {
+        need(dev_of[j], pairs[j].ref);
+        need(dev_of[j], pairs[j].other);
+    }
+    for (int j = 0; refs_on_0 && j < n_pairs; j++) need(0, pairs[j].ref);
 }
 
 }  // namespace sva

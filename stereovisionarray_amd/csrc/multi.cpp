@@ -12,7 +12,7 @@
 // through the public per-context entry points (sva_disparity_sgm_d,
 // sva_fuse_depth_d, and sva_disparity_sgm_conf_d / sva_fuse_depth_conf_d for
 // the confidence forms, whose cost planes are gathered like the maps); there
-// is no CPU path.  The eight sva_array_depth* entry points fill one ArrayArgs
+// is no CPU path.  The nine sva_array_depth* entry points fill one ArrayArgs
 // (array_args.h: the arguments and their checks, in one order) and run one
 // array_frame(): its jobs are pairs, or -- sva_array_depth_mb -- GROUPS (one
 // sva_disparity_sgm_multi_d per reference camera, DESIGN.md §2.2c;
@@ -122,6 +122,7 @@ struct Multi {
     DevBuf cross0;                     // device 0: the checked planes (sva_array_depth_checked)
     DevBuf speckle0;                   // device 0: comp_size planes (sva_array_depth_filtered)
     DevBuf fill0;                      // device 0: n_found planes (sva_array_depth_filled)
+    DevBuf wmed0;                      // device 0: the smoothed planes (sva_array_depth_smoothed)
     PinnedBuf stage_in, stage_out;
     Rccl rccl;
     std::vector<ncclComm_t> comms;
@@ -648,6 +649,7 @@ int sva_multi_destroy(void* mp) {
         m->cross0.release();
         m->speckle0.release();
         m->fill0.release();
+        m->wmed0.release();
     }
     m->stage_in.release();
     m->stage_out.release();
@@ -727,10 +729,11 @@ int batch_sgm_d(void* mp, const sva_pair_d* jobs, int n_jobs, int W, int H, size
 // The host views of an array frame onto the devices that need them
 // (sva_array_depth*): pair j runs on device dev_of[j].  Out: slot_of[d][v], the
 // slot of view v in m->images[d] (-1: not needed there), and up_ev[d][v], the
-// event of its upload on the device's copy stream.
+// event of its upload on the device's copy stream.  plan_views (array_args.h)
+// decides who needs what; refs_on_0: every reference view on device 0 too.
 int upload_views(Multi* m, const uint8_t* const* images, int n_images, int W, int H, size_t pitch,
                  const sva_array_pair* pairs, int n_pairs, const std::vector<int32_t>& dev_of,
-                 std::vector<std::vector<int>>& slot_of,
+                 bool refs_on_0, std::vector<std::vector<int>>& slot_of,
                  std::vector<std::vector<hipEvent_t>>& up_ev) {
     const size_t np = (size_t)W * H;
     if (m->copy.empty()) {
@@ -743,15 +746,9 @@ int upload_views(Multi* m, const uint8_t* const* images, int n_images, int W, in
         }
     }
     // 1. which views each device needs, staged once into pinned memory
-    slot_of.assign(m->nd(), std::vector<int>(n_images, -1));
-    std::vector<int> n_need(m->nd(), 0);
-    std::vector<char> used(n_images, 0);
-    for (int j = 0; j < n_pairs; j++)
-        for (int v : {pairs[j].ref, pairs[j].other}) {
-            used[v] = 1;
-            int& s = slot_of[dev_of[j]][v];
-            if (s < 0) s = n_need[dev_of[j]]++;
-        }
+    std::vector<int> n_need;
+    std::vector<char> used;
+    plan_views(m->nd(), n_images, pairs, n_pairs, dev_of.data(), refs_on_0, slot_of, n_need, used);
     std::vector<int> pin_slot(n_images, -1);
     int n_pin = 0;
     for (int v = 0; v < n_images; v++)
@@ -819,7 +816,7 @@ struct Download {
     }
 };
 
-// One camera-array frame: sva_array_depth, _conf, _mb, _mixed, _sub, _checked, _filtered and _filled (array_args.h
+// One camera-array frame: sva_array_depth, _conf, _mb, _mixed, _sub, _checked, _filtered, _filled and _smoothed (array_args.h
 // has their arguments and checks).  A job is a pair (ArrayRoute::Pairs: every
 // pair through sva_disparity_sgm_d or, with conf, sva_disparity_sgm_conf_d; a
 // group's maps are fused by `mode`) or a GROUP (group g's
@@ -832,7 +829,8 @@ struct Download {
 // sva_cross_check_d on device 0 before step 4, which then reads the checked
 // planes.  With a.speckle (sva_array_depth_filtered, §2.5c) every job's map --
 // checked or not -- then passes through sva_filter_speckles_d in place, and
-// with a.fill (sva_array_depth_filled, §2.5d) through sva_fill_holes_d after it.
+// with a.fill (sva_array_depth_filled, §2.5d) through sva_fill_holes_d after it,
+// and with a.wmed (sva_array_depth_smoothed, §2.5e) through sva_weighted_median_d.
 int array_frame(void* mp, const ArrayArgs& a) {
     Multi* m = as_multi(mp);
     if (!m) return SVA_ERR_INVALID_ARG;
@@ -857,7 +855,7 @@ int array_frame(void* mp, const ArrayArgs& a) {
     std::vector<std::vector<int>> slot_of;
     std::vector<std::vector<hipEvent_t>> up_ev;
     if (int st = upload_views(m, a.images, a.n_images, W, H, a.pitch, pairs, n_pairs, dev_of,
-                              slot_of, up_ev))
+                              a.wmed, slot_of, up_ev))
         return st;
     // 3. jobs + gather into maps0 on device 0
     MHIP(m, hipSetDevice(m->devices[0]), "hipSetDevice");
@@ -974,7 +972,8 @@ int array_frame(void* mp, const ArrayArgs& a) {
     uint8_t* found0 = nullptr;
     if (a.fill) {
         MHIP(m, hipSetDevice(m->devices[0]), "hipSetDevice");
-        if (a.n_found) {
+        // the plane is kept for step 3e's select even if the caller did not ask for it
+        if (a.n_found || (a.wmed && a.wmed_select == 1)) {
             MHIP(m, m->fill0.ensure(np * n_jobs), "fill workspace");
             found0 = (uint8_t*)m->fill0.ptr;
         }
@@ -990,6 +989,40 @@ int array_frame(void* mp, const ArrayArgs& a) {
                                   found0 ? found0 + o : nullptr);
             if (st) return m->ctx_fail(st, m->ctx[0], "hole filling");
         }
+    }
+    // 3e. the weighted median filter, guided by each job's reference view on
+    // device 0, into planes of wmed0 -- f32 maps (sub), u16 maps, support -- which
+    // take the place of maps0 / sub0 from here on: one call per run of jobs that
+    // share `invalid`
+    uint16_t* support0 = nullptr;
+    if (a.wmed) {
+        MHIP(m, hipSetDevice(m->devices[0]), "hipSetDevice");
+        MHIP(m, m->wmed0.ensure(plane * (a.sub ? 3 : 1) + (a.support ? plane : 0)), "wmed workspace");
+        uint8_t* w = (uint8_t*)m->wmed0.ptr;
+        float* wsub = a.sub ? (float*)w : nullptr;             // the f32 planes first: aligned
+        uint16_t* wmaps = (uint16_t*)(w + (a.sub ? plane * 2 : 0));
+        if (a.support) support0 = wmaps + np * n_jobs;
+        std::vector<const uint8_t*> guides(n_jobs);
+        for (int k = 0; k < n_jobs; k++) {
+            const int v = pairs[first[k]].ref;
+            guides[k] = (const uint8_t*)m->images[0].ptr + (size_t)slot_of[0][v] * np;
+            if (a.wmed_weights)
+                MHIP(m, hipStreamWaitEvent(m->st(0, 0), up_ev[0][v], 0), "wait");
+        }
+        const uint8_t* sel0 = a.wmed_select == 1 ? found0 : nullptr;
+        for (int k = 0, k1; k < n_jobs; k = k1) {
+            const uint16_t inv = pairs[first[k]].params.invalid;
+            for (k1 = k + 1; k1 < n_jobs && pairs[first[k1]].params.invalid == inv;) k1++;
+            const size_t o = (size_t)k * np;
+            st = sva_weighted_median_d(m->ctx[0], maps0 + o, sub0 ? sub0 + o : nullptr,
+                                       a.wmed_weights ? guides.data() + k : nullptr, (size_t)W,
+                                       a.wmed_weights, sel0 ? sel0 + o : nullptr, k1 - k, W, H, inv,
+                                       a.wmed_radius, a.wmed_min_support, 1, wmaps + o,
+                                       wsub ? wsub + o : nullptr, support0 ? support0 + o : nullptr);
+            if (st) return m->ctx_fail(st, m->ctx[0], "weighted median");
+        }
+        maps0 = wmaps;
+        sub0 = wsub;
     }
     // 4. depth per group on device 0 -- the fusion of its pairs' maps, or the
     // depth of its one map (the median of one is the map's own depth) -- each
@@ -1013,6 +1046,7 @@ int array_frame(void* mp, const ArrayArgs& a) {
     dl.add(n_groups, conflict0, a.conflict, np * n_groups);
     dl.add(n_groups, size0, a.comp_size, plane * 2);
     dl.add(n_groups, found0, a.n_found, np * n_jobs);
+    dl.add(n_groups, support0, a.support, plane);
     MHIP(m, m->stage_out.ensure(dl.total), "pinned staging");
     std::vector<double> bases(n_pairs);
     for (int j = 0; j < n_pairs; j++) bases[j] = pairs[j].baseline;
@@ -1051,7 +1085,7 @@ int array_frame(void* mp, const ArrayArgs& a) {
     return dl.finish(m);
 }
 
-// What the eight entry points share; as it stands, sva_array_depth's: the pair
+// What the nine entry points share; as it stands, sva_array_depth's: the pair
 // route, plain matching, median fusion.
 ArrayArgs frame_args(const uint8_t* const* images, int n_images, int W, int H, size_t pitch,
                      const sva_array_pair* pairs, int n_pairs, const int32_t* group_start,
@@ -1197,7 +1231,7 @@ int sva_array_depth_checked(void* mp, const uint8_t* const* images, int n_images
 }
 
 // sva_array_depth_filtered (fill = false: the fill's arguments are not looked
-// at) and sva_array_depth_filled.
+// at), sva_array_depth_filled and sva_array_depth_smoothed (wmed = true).
 static int array_depth_post(void* mp, const uint8_t* const* images, int n_images, int W, int H,
                             size_t pitch, const sva_array_pair* pairs, int n_pairs,
                             const int32_t* group_start, int n_groups, int route,
@@ -1208,7 +1242,9 @@ static int array_depth_post(void* mp, const uint8_t* const* images, int n_images
                             int min_agree, int max_conflict, uint8_t* agree, uint8_t* conflict,
                             int check, int speckle_max_size, int speckle_max_diff,
                             uint32_t* comp_size, bool fill, int fill_max_dist, int fill_min_found,
-                            int fill_mode, uint8_t* n_found) {
+                            int fill_mode, uint8_t* n_found, bool wmed = false, int wmed_radius = 1,
+                            const uint16_t* wmed_weights = nullptr, int wmed_min_support = 1,
+                            int wmed_select = 0, uint16_t* support = nullptr) {
     if (sub != 0 && sub != 1) {
         Multi* m = as_multi(mp);
         return m ? m->fail(SVA_ERR_INVALID_ARG, "sub must be 0 or 1") : SVA_ERR_INVALID_ARG;
@@ -1243,6 +1279,14 @@ static int array_depth_post(void* mp, const uint8_t* const* images, int n_images
         a.fill_min_found = fill_min_found;
         a.fill_mode = fill_mode;
         a.n_found = n_found;
+    }
+    a.wmed = wmed;
+    if (wmed) {
+        a.wmed_radius = wmed_radius;
+        a.wmed_weights = wmed_weights;
+        a.wmed_min_support = wmed_min_support;
+        a.wmed_select = wmed_select;
+        a.support = support;
     }
     return array_frame(mp, a);
 }
@@ -1281,6 +1325,28 @@ int sva_array_depth_filled(void* mp, const uint8_t* const* images, int n_images,
                             max_diff, min_agree, max_conflict, agree, conflict, check,
                             speckle_max_size, speckle_max_diff, comp_size, true, fill_max_dist,
                             fill_min_found, fill_mode, n_found);
+}
+
+int sva_array_depth_smoothed(void* mp, const uint8_t* const* images, int n_images, int W, int H,
+                             size_t pitch, const sva_array_pair* pairs, int n_pairs,
+                             const int32_t* group_start, int n_groups, int route,
+                             const double* unit_baseline, double f, double pixel_size,
+                             int uniqueness, int mode, double* depth, uint8_t* n_valid,
+                             uint8_t* winner, float* subpix, uint16_t* maps, uint16_t* cost_min,
+                             uint16_t* cost_second, const int32_t* view_step, int sub,
+                             int max_diff, int min_agree, int max_conflict, uint8_t* agree,
+                             uint8_t* conflict, int check, int speckle_max_size,
+                             int speckle_max_diff, uint32_t* comp_size, int fill_max_dist,
+                             int fill_min_found, int fill_mode, uint8_t* n_found, int wmed_radius,
+                             const uint16_t* wmed_weights, int wmed_min_support, int wmed_select,
+                             uint16_t* support) {
+    return array_depth_post(mp, images, n_images, W, H, pitch, pairs, n_pairs, group_start,
+                            n_groups, route, unit_baseline, f, pixel_size, uniqueness, mode, depth,
+                            n_valid, winner, subpix, maps, cost_min, cost_second, view_step, sub,
+                            max_diff, min_agree, max_conflict, agree, conflict, check,
+                            speckle_max_size, speckle_max_diff, comp_size, true, fill_max_dist,
+                            fill_min_found, fill_mode, n_found, true, wmed_radius, wmed_weights,
+                            wmed_min_support, wmed_select, support);
 }
 
 }  // extern "C"

@@ -21,6 +21,7 @@
 #include "speckle_math.h"
 #include "sva_internal.h"
 #include "sva_tuning.h"
+#include "wmedian_math.h"
 
 using namespace sva;
 
@@ -693,7 +694,7 @@ int sva_destroy(void* ctx) {
     c->census_side.release();
     for (DevBuf* b : {&c->census_l, &c->census_r, &c->cost, &c->paths, &c->ckpt, &c->scratch_u16,
                       &c->disp_r, &c->in_a, &c->in_b, &c->in_mask, &c->out_a, &c->out_b,
-                      &c->out_c, &c->in_c, &c->shifted, &c->keys, &c->counts, &c->total, &c->ref_keys, &c->refine_ws, &c->speckle_ws, &c->fill_ws})
+                      &c->out_c, &c->in_c, &c->shifted, &c->keys, &c->counts, &c->total, &c->ref_keys, &c->refine_ws, &c->speckle_ws, &c->fill_ws, &c->wmed_guides})
         b->release();
     c->timer.release_all();
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
@@ -2077,6 +2078,111 @@ int sva_fill_holes(void* ctx, const uint16_t* disps, const float* subpix, int n,
     g.down(out, dd, nnp * 2);
     g.down(out_sub, ds, nnp * 4);
     g.down(n_found, dfound, nnp);
+    return g.sync();
+}
+
+// -------------------------------- weighted median filter --
+namespace {
+// The rules of sva_weighted_median and sva_weighted_median_d, in sva.h's order;
+// the pointers are the caller's (host or device), which is where overlap matters.
+int check_wmed(Ctx* c, const uint16_t* disps, const float* subpix, const uint8_t* const* guides,
+               size_t guide_pitch, const uint16_t* weights, const uint8_t* select, int n, int W,
+               int H, int radius, int min_support, int fill, const uint16_t* out,
+               const float* out_sub, const uint16_t* support) {
+    if (!disps || !out) return fail(c, SVA_ERR_INVALID_ARG, "null pointer");
+    if (n < 1) return fail(c, SVA_ERR_INVALID_ARG, "n_maps must be >= 1");
+    if (W <= 0 || H <= 0) return fail(c, SVA_ERR_INVALID_ARG, "image size must be positive");
+    if ((unsigned long long)W * (unsigned long long)H >= (1ull << 31))
+        return fail(c, SVA_ERR_UNSUPPORTED, "the weighted median needs W * H < 2^31");
+    if (const char* m = wm::thresholds_error(radius, min_support, fill))
+        return fail(c, SVA_ERR_INVALID_ARG, m);
+    if ((guides == nullptr) != (weights == nullptr))
+        return fail(c, SVA_ERR_INVALID_ARG, "guides and weights go together");
+    if (guides) {
+        for (int i = 0; i < n; i++)
+            if (!guides[i]) return fail(c, SVA_ERR_INVALID_ARG, "null guide image");
+        if (guide_pitch < (size_t)W) return fail(c, SVA_ERR_INVALID_ARG, "guide pitch < width");
+    }
+    if (out_sub && !subpix) return fail(c, SVA_ERR_INVALID_ARG, "out_sub needs subpix");
+    // the byte counts saturate: a frame too large for the address space overlaps everything
+    const unsigned long long px = (unsigned long long)W * H;
+    const size_t lim = ~(size_t)0;
+    const size_t b8 = px > lim / 4 / (size_t)n ? lim / 4 : (size_t)px * (size_t)n;
+    const size_t b16 = b8 * 2, b32 = b8 * 4;
+    const size_t bg = guides && (size_t)(H - 1) <= (lim / 4 - (size_t)W) / guide_pitch
+                          ? (size_t)(H - 1) * guide_pitch + (size_t)W
+                          : lim / 4;
+    const void* outs[3] = {out, out_sub, support};
+    const size_t out_bytes[3] = {b16, b32, b16};
+    bool bad = false;
+    for (int o = 0; o < 3; o++) {
+        bad = bad || ranges_overlap(outs[o], out_bytes[o], disps, b16) ||
+              ranges_overlap(outs[o], out_bytes[o], subpix, b32) ||
+              ranges_overlap(outs[o], out_bytes[o], select, b8);
+        for (int i = 0; guides && i < n; i++)
+            bad = bad || ranges_overlap(outs[o], out_bytes[o], guides[i], bg);
+        for (int q = o + 1; q < 3; q++)
+            bad = bad || ranges_overlap(outs[o], out_bytes[o], outs[q], out_bytes[q]);
+    }
+    if (bad)
+        return fail(c, SVA_ERR_INVALID_ARG,
+                    "an output overlaps an input or another output (in place is not offered)");
+    return SVA_OK;
+}
+}  // namespace
+
+int sva_weighted_median_d(void* ctx, const uint16_t* disps, const float* subpix,
+                          const uint8_t* const* guides, size_t guide_pitch,
+                          const uint16_t* weights, const uint8_t* select, int n, int W, int H,
+                          uint16_t invalid, int radius, int min_support, int fill, uint16_t* out,
+                          float* out_sub, uint16_t* support) {
+    Ctx* c = as_ctx(ctx);
+    SVA_CHECK_CTX(c);
+    if (int s = check_wmed(c, disps, subpix, guides, guide_pitch, weights, select, n, W, H, radius,
+                           min_support, fill, out, out_sub, support))
+        return s;
+    SVA_HIP(c, launch_wmedian(*c, disps, subpix, guides, guide_pitch, weights, select, n, W, H,
+                              invalid, radius, min_support, fill, out, out_sub, support),
+            "wmed launch");
+    return SVA_OK;
+}
+
+// The guides are packed on the device, one W x H image per map.
+int sva_weighted_median(void* ctx, const uint16_t* disps, const float* subpix,
+                        const uint8_t* const* guides, size_t guide_pitch, const uint16_t* weights,
+                        const uint8_t* select, int n, int W, int H, uint16_t invalid, int radius,
+                        int min_support, int fill, uint16_t* out, float* out_sub,
+                        uint16_t* support) {
+    Ctx* c = as_ctx(ctx);
+    SVA_CHECK_CTX(c);
+    if (int s = check_wmed(c, disps, subpix, guides, guide_pitch, weights, select, n, W, H, radius,
+                           min_support, fill, out, out_sub, support))
+        return s;
+    const size_t np = (size_t)W * H, nnp = np * (size_t)n;
+    Staging g{c};
+    uint16_t* dd = g.up<uint16_t>(c->in_a, disps, nnp * 2);
+    float* ds = out_sub ? g.up<float>(c->in_mask, subpix, nnp * 4) : nullptr;
+    uint8_t* dsel = select ? g.up<uint8_t>(c->in_c, select, nnp) : nullptr;
+    std::vector<const uint8_t*> dguides;
+    if (guides) {
+        uint8_t* dg = g.out<uint8_t>(c->wmed_guides, nnp);
+        for (int i = 0; i < n && g.st == SVA_OK; i++) {
+            g.note(hipMemcpy2DAsync(dg + (size_t)i * np, W, guides[i], guide_pitch, W, H,
+                                    hipMemcpyHostToDevice, c->stream),
+                   "upload");
+            dguides.push_back(dg + (size_t)i * np);
+        }
+    }
+    uint16_t* dout = g.out<uint16_t>(c->out_a, nnp * 2);
+    float* dosub = out_sub ? g.out<float>(c->out_b, nnp * 4) : nullptr;
+    uint16_t* dsup = support ? g.out<uint16_t>(c->out_c, nnp * 2) : nullptr;
+    if (g.st) return g.st;
+    SVA_HIP(c, launch_wmedian(*c, dd, ds, guides ? dguides.data() : nullptr, (size_t)W, weights,
+                              dsel, n, W, H, invalid, radius, min_support, fill, dout, dosub, dsup),
+            "wmed launch");
+    g.down(out, dout, nnp * 2);
+    g.down(out_sub, dosub, nnp * 4);
+    g.down(support, dsup, nnp * 2);
     return g.sync();
 }
 

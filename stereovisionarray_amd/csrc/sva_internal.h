@@ -75,6 +75,8 @@ struct Ctx {
     // hole filling's key planes (fill.hip; sva.h gives the size), and
     // SVA_DEBUG_FILL_SEGMENT: the scan's segment length (0 = tune::kFillSegment)
     DevBuf fill_ws;
+    // the host entry of the weighted median filter packs its guides here
+    DevBuf wmed_guides;
     int dbg_fill_segment = 0;
     // Mode R's split plane loop: one first-minimum key per pixel (refpath.hip).
     // ref_finalize_kernel puts every key it reads back to all-ones, so after
@@ -268,6 +270,16 @@ hipError_t launch_speckle(Ctx& c, const uint16_t* disps, const float* subpix, in
 hipError_t launch_fill(Ctx& c, const uint16_t* disps, const float* subpix, int n, int W, int H,
                        uint16_t invalid, int max_dist, int min_found, int mode, int segment,
                        uint32_t* keys, uint16_t* out, float* out_sub, uint8_t* n_found);
+// wmedian.hip -- the weighted median filter: n maps [n][H][W],
+// W * H < 2^31; guides: a HOST array of n device images, `guide_pitch` >= W bytes a
+// row, and weights a HOST array of 256, both null for the unguided filter, both
+// read before the call returns; select (u8), subpix / out_sub (f32) and support
+// (u16) nullable, out_sub needs subpix; no output may overlap an input.
+hipError_t launch_wmedian(Ctx& c, const uint16_t* disps, const float* subpix,
+                          const uint8_t* const* guides, size_t guide_pitch, const uint16_t* weights,
+                          const uint8_t* select, int n, int W, int H, uint16_t invalid, int radius,
+                          int min_support, int fill, uint16_t* out, float* out_sub,
+                          uint16_t* support);
 // refpath.hip
 hipError_t launch_ref_endpoints(Ctx& c, int W, int H, const sva_camera& cref,
                                 const sva_camera& coth, int k, double t_near, double t_far,

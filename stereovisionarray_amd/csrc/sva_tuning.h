@@ -307,5 +307,30 @@ constexpr int kFillRing = 4;
 // 531 MB at 1080p.
 constexpr int kFillFrameMaps = 8;
 
+// ---- wmedian.hip ------------------------------------------
+// A workgroup of kWmedTileW x kWmedTileH threads stages its tile and an r-wide
+// halo in LDS: (W + 2r)(H + 2r) cells for W * H outputs, 9.2 staged cells per
+// output at r = 15 for 32 x 8.  A row of kWmedTileW = 32 threads reads 32
+// neighbouring u16 cells, 16 LDS banks, without a conflict.
+// One sweep (a build with the five shapes as template instances behind a debug
+// key, since removed, and its window loops unrolled four times; the shape set on
+// one warm context in one session, the first shape again at the end; 1080p, n = 25 synthetic maps with 5 % holes, guided, u16 planes
+// only, 15 calls, stream events around the launch;
+// profiles/wmed/tile_sweep_1080p.json), ms median [min-max]:
+//   tile     r = 2                            r = 5                            r = 15
+//   32 x 8                           13.5578 [13.5384-13.8955]        35.4873 [35.4606-35.4976]        296.1375 [295.6524-296.3237]
+//   16 x 16                          13.5420 [13.5249-13.5823]        35.4307 [35.4001-35.4851]        295.8513 [295.4726-296.4768]
+//   64 x 4                           13.5765 [13.5145-13.6744]        35.4563 [35.3929-35.4849]        295.6263 [295.3668-296.0222]
+//   32 x 16                          13.5934 [13.5467-13.6528]        35.5451 [35.4950-36.4595]        296.2917 [295.9060-296.9395]
+//   64 x 8                           13.5669 [13.5344-13.5957]        35.5113 [35.4484-35.6298]        295.8739 [295.6601-296.3386]
+//   32 x 8                           13.5992 [13.5267-13.7458]        35.4634 [35.3888-35.5464]        295.2286 [295.0656-296.0691]
+// No winner: every shape is within 0.3 % of the others, inside the spread of the
+// two 32 x 8 legs -- the time is the window loops', not the staging's.  The
+// shape the LDS layout argues for stays.
+constexpr int kWmedTileW = 32, kWmedTileH = 8;
+// The guides of one launch travel in the kernel's arguments (8 bytes each beside
+// the 512-byte table): n_maps beyond this take a further launch.
+constexpr int kWmedLaunchMaps = 64;
+
 }  // namespace tune
 }  // namespace sva
