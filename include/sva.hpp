@@ -809,6 +809,103 @@ inline std::vector<std::vector<double>> computeArrayDepthSub(
     });
 }
 
+// ---- the post-filter chain: what its filters and frames share ---------------
+
+namespace detail {
+// The packing the four map filters share: maps[i] (W*H u16 each) and, unless
+// empty, subpix[i] back to back as the C calls take them.  need: what is thrown
+// when there is no map, or not one sub-pixel map per map.
+struct PackedMaps {
+    size_t np = 0, n = 0;
+    std::vector<uint16_t> d;
+    std::vector<float> s;
+    float* sub() { return s.empty() ? nullptr : s.data(); }
+};
+inline PackedMaps packFilterMaps(const std::string& who, const char* need,
+                                 const std::vector<std::vector<uint16_t>>& maps,
+                                 const std::vector<std::vector<float>>& subpix, int W, int H) {
+    PackedMaps p;
+    p.np = (size_t)W * H;
+    p.n = maps.size();
+    if (maps.empty() || (!subpix.empty() && subpix.size() != p.n))
+        throw Error(SVA_ERR_INVALID_ARG, who + ": " + need);
+    p.d.resize(p.np * p.n);
+    p.s.resize(subpix.empty() ? 0 : p.np * p.n);
+    for (size_t i = 0; i < p.n; i++) {
+        if (maps[i].size() != p.np || (!subpix.empty() && subpix[i].size() != p.np))
+            throw Error(SVA_ERR_INVALID_ARG, who + ": map size");
+        std::copy(maps[i].begin(), maps[i].end(), p.d.begin() + i * p.np);
+        if (!subpix.empty()) std::copy(subpix[i].begin(), subpix[i].end(), p.s.begin() + i * p.np);
+    }
+    return p;
+}
+
+// n planes of np back to back, one vector each (nothing of an empty `all`).
+template <typename T>
+inline std::vector<std::vector<T>> unpackPlanes(const std::vector<T>& all, size_t np, size_t n) {
+    std::vector<std::vector<T>> out;
+    for (size_t i = 0; i < n && !all.empty(); i++)
+        out.emplace_back(all.begin() + i * np, all.begin() + (i + 1) * np);
+    return out;
+}
+
+// What the post-filter chain's frames (computeArrayDepthChecked, Filtered,
+// Filled, Smoothed) share around their one C call.  Every camera's view_step is
+// minus its grid offset from cameras[0], in units of `pitch`, and the mixed
+// route's unit baseline is `pitch`.
+struct ChainFrame {
+    ArrayFrame fr;
+    size_t n_pairs;
+    bool per_group;                  // one job per reference camera, else per pair
+    std::vector<double> unit;
+    std::vector<int32_t> vs;
+
+    ChainFrame(const std::vector<ImageView>& images, const std::vector<Camera>& cameras,
+               const std::vector<std::array<int, 2>>& pairs, const sva_sgm_params& p, int route,
+               double pitch, const char* who)
+        : fr(arrayFrame(images, cameras, pairs, p, pitch, who)), n_pairs(pairs.size()),
+          per_group(route != SVA_ARRAY_PAIRS) {
+        if (route == SVA_ARRAY_GROUPS_MIXED) unit = unitBaselines(fr, 1, pitch);
+        for (const Camera& c : cameras) {
+            vs.push_back(-(int32_t)std::lround((c.pos3D.x - cameras[0].pos3D.x) / pitch));
+            vs.push_back(-(int32_t)std::lround((c.pos3D.y - cameras[0].pos3D.y) / pitch));
+        }
+    }
+    // A stage's per-job plane: its storage (empty unless asked for), what the C
+    // call takes, and the planes given back per reference camera or in `pairs` order.
+    template <typename T>
+    std::vector<T> plane(const std::vector<std::vector<T>>* asked) const {
+        return std::vector<T>(asked ? (size_t)fr.W * fr.H * (per_group ? fr.refs.size() : fr.ap.size())
+                                    : 0);
+    }
+    template <typename T>
+    static T* ptr(std::vector<T>& all) { return all.empty() ? nullptr : all.data(); }
+    template <typename T>
+    void give(const std::vector<T>& all, std::vector<std::vector<T>>* asked) const {
+        if (asked && per_group) *asked = fr.split(all);
+        else if (asked) fr.scatter(all, n_pairs, asked);
+    }
+    // fn: one of the chain's entries; its arguments from `route` to the check's
+    // conflict plane, every optional plane but maps left out, then tail...
+    template <typename Fn, typename... Tail>
+    std::vector<std::vector<double>> depth(MultiEngine& m, const std::vector<Camera>& cameras, Fn fn,
+                                           int route, int uniqueness, int mode,
+                                           std::vector<std::vector<uint16_t>>* maps, bool sub,
+                                           int max_diff, int min_agree, int max_conflict,
+                                           uint8_t* agree, uint8_t* conflict, Tail... tail) const {
+        return arrayDepth(fr, cameras, n_pairs, per_group, maps,
+                          [&](double f, double pixel_size, double* depth, uint16_t* all) {
+            m.check(fr.call(fn, m.handle(), route,
+                            unit.empty() ? (const double*)nullptr : (const double*)unit.data(), f,
+                            pixel_size, uniqueness, mode, depth, (uint8_t*)nullptr, (uint8_t*)nullptr,
+                            (float*)nullptr, all, (uint16_t*)nullptr, (uint16_t*)nullptr,
+                            (const int32_t*)vs.data(), sub ? 1 : 0, max_diff, min_agree, max_conflict,
+                            agree, conflict, tail...));
+        });
+    }
+};
+}  // namespace detail
+
 // ---- cross-view consistency check ------------------------
 
 // What crossCheck keeps of each view: the checked map, and the optional planes.
@@ -831,33 +928,21 @@ inline CrossChecked crossCheck(Engine& eng, const std::vector<std::vector<uint16
                                const std::vector<std::array<int32_t, 2>>& view_step,
                                int max_diff = 1, int min_agree = 1, int max_conflict = 0,
                                uint16_t invalid = 0xFFFF) {
-    const size_t np = (size_t)W * H, n = maps.size();
-    if (maps.empty() || view_step.size() != n || (!subpix.empty() && subpix.size() != n))
-        throw Error(SVA_ERR_INVALID_ARG,
-                    "crossCheck: need one view_step (and sub-pixel map) per map");
-    std::vector<uint16_t> d(np * n), out(np * n);
-    std::vector<float> s(subpix.empty() ? 0 : np * n), out_s(s.size());
+    const char* need = "need one view_step (and sub-pixel map) per map";
+    if (view_step.size() != maps.size())
+        throw Error(SVA_ERR_INVALID_ARG, std::string("crossCheck: ") + need);
+    detail::PackedMaps in = detail::packFilterMaps("crossCheck", need, maps, subpix, W, H);
+    const size_t np = in.np, n = in.n;
+    std::vector<uint16_t> out(np * n);
+    std::vector<float> out_s(in.s.size());
     std::vector<uint8_t> ag(np * n), cf(np * n);
     std::vector<int32_t> vs;
-    for (size_t i = 0; i < n; i++) {
-        if (maps[i].size() != np || (!subpix.empty() && subpix[i].size() != np))
-            throw Error(SVA_ERR_INVALID_ARG, "crossCheck: map size");
-        std::copy(maps[i].begin(), maps[i].end(), d.begin() + i * np);
-        if (!subpix.empty()) std::copy(subpix[i].begin(), subpix[i].end(), s.begin() + i * np);
-        vs.push_back(view_step[i][0]);
-        vs.push_back(view_step[i][1]);
-    }
-    eng.check(sva_cross_check(eng.handle(), d.data(), s.empty() ? nullptr : s.data(), (int)n, W, H,
-                              vs.data(), invalid, max_diff, min_agree, max_conflict, out.data(),
-                              s.empty() ? nullptr : out_s.data(), ag.data(), cf.data()));
-    CrossChecked r;
-    for (size_t i = 0; i < n; i++) {
-        r.maps.emplace_back(out.begin() + i * np, out.begin() + (i + 1) * np);
-        if (!s.empty()) r.subpix.emplace_back(out_s.begin() + i * np, out_s.begin() + (i + 1) * np);
-        r.agree.emplace_back(ag.begin() + i * np, ag.begin() + (i + 1) * np);
-        r.conflict.emplace_back(cf.begin() + i * np, cf.begin() + (i + 1) * np);
-    }
-    return r;
+    for (const auto& v : view_step) vs.insert(vs.end(), {v[0], v[1]});
+    eng.check(sva_cross_check(eng.handle(), in.d.data(), in.sub(), (int)n, W, H, vs.data(), invalid,
+                              max_diff, min_agree, max_conflict, out.data(),
+                              in.s.empty() ? nullptr : out_s.data(), ag.data(), cf.data()));
+    return {detail::unpackPlanes(out, np, n), detail::unpackPlanes(out_s, np, n),
+            detail::unpackPlanes(ag, np, n), detail::unpackPlanes(cf, np, n)};
 }
 
 // computeArrayDepthMulti / Mixed (sub = false) or the group routes of
@@ -878,29 +963,14 @@ inline std::vector<std::vector<double>> computeArrayDepthChecked(
     std::vector<std::vector<uint16_t>>* maps = nullptr,
     std::vector<std::vector<uint8_t>>* agree = nullptr,
     std::vector<std::vector<uint8_t>>* conflict = nullptr) {
-    const detail::ArrayFrame fr = detail::arrayFrame(images, cameras, pairs, p, pitch,
-                                                     "computeArrayDepthChecked");
-    std::vector<double> unit;
-    if (route == SVA_ARRAY_GROUPS_MIXED) unit = detail::unitBaselines(fr, 1, pitch);
-    std::vector<int32_t> vs;
-    for (const Camera& c : cameras) {
-        vs.push_back(-(int32_t)std::lround((c.pos3D.x - cameras[0].pos3D.x) / pitch));
-        vs.push_back(-(int32_t)std::lround((c.pos3D.y - cameras[0].pos3D.y) / pitch));
-    }
-    const size_t np = (size_t)fr.W * fr.H, ng = fr.refs.size();
-    std::vector<uint8_t> ag(agree ? np * ng : 0), cf(conflict ? np * ng : 0);
-    auto depth = detail::arrayDepth(fr, cameras, pairs.size(), route != SVA_ARRAY_PAIRS, maps,
-                                    [&](double f, double pixel_size, double* depth, uint16_t* all) {
-        m.check(fr.call(sva_array_depth_checked, m.handle(), route,
-                        unit.empty() ? (const double*)nullptr : (const double*)unit.data(), f,
-                        pixel_size, uniqueness, (int)SVA_FUSE_MEDIAN, depth, (uint8_t*)nullptr,
-                        (uint8_t*)nullptr, (float*)nullptr, all, (uint16_t*)nullptr,
-                        (uint16_t*)nullptr, (const int32_t*)vs.data(), sub ? 1 : 0, max_diff,
-                        min_agree, max_conflict, agree ? ag.data() : (uint8_t*)nullptr,
-                        conflict ? cf.data() : (uint8_t*)nullptr));
-    });
-    if (agree) *agree = fr.split(ag);
-    if (conflict) *conflict = fr.split(cf);
+    const detail::ChainFrame cf(images, cameras, pairs, p, route, pitch, "computeArrayDepthChecked");
+    const size_t planes = (size_t)cf.fr.W * cf.fr.H * cf.fr.refs.size();
+    std::vector<uint8_t> ag(agree ? planes : 0), cn(conflict ? planes : 0);
+    auto depth = cf.depth(m, cameras, sva_array_depth_checked, route, uniqueness,
+                          (int)SVA_FUSE_MEDIAN, maps, sub, max_diff, min_agree, max_conflict,
+                          cf.ptr(ag), cf.ptr(cn));
+    if (agree) *agree = cf.fr.split(ag);
+    if (conflict) *conflict = cf.fr.split(cn);
     return depth;
 }
 
@@ -922,29 +992,14 @@ struct SpeckleFiltered {
 inline SpeckleFiltered filterSpeckles(Engine& eng, const std::vector<std::vector<uint16_t>>& maps,
                                       const std::vector<std::vector<float>>& subpix, int W, int H,
                                       int max_size, int max_diff, uint16_t invalid = 0xFFFF) {
-    const size_t np = (size_t)W * H, n = maps.size();
-    if (maps.empty() || (!subpix.empty() && subpix.size() != n))
-        throw Error(SVA_ERR_INVALID_ARG, "filterSpeckles: need one sub-pixel map per map");
-    std::vector<uint16_t> d(np * n);
-    std::vector<float> s(subpix.empty() ? 0 : np * n);
-    std::vector<uint32_t> size(np * n);
-    for (size_t i = 0; i < n; i++) {
-        if (maps[i].size() != np || (!subpix.empty() && subpix[i].size() != np))
-            throw Error(SVA_ERR_INVALID_ARG, "filterSpeckles: map size");
-        std::copy(maps[i].begin(), maps[i].end(), d.begin() + i * np);
-        if (!subpix.empty()) std::copy(subpix[i].begin(), subpix[i].end(), s.begin() + i * np);
-    }
+    detail::PackedMaps io = detail::packFilterMaps("filterSpeckles", "need one sub-pixel map per map",
+                                                   maps, subpix, W, H);
+    std::vector<uint32_t> size(io.np * io.n);
     // in place on the packed copies
-    eng.check(sva_filter_speckles(eng.handle(), d.data(), s.empty() ? nullptr : s.data(), (int)n, W,
-                                  H, invalid, max_size, max_diff, d.data(),
-                                  s.empty() ? nullptr : s.data(), size.data()));
-    SpeckleFiltered r;
-    for (size_t i = 0; i < n; i++) {
-        r.maps.emplace_back(d.begin() + i * np, d.begin() + (i + 1) * np);
-        if (!s.empty()) r.subpix.emplace_back(s.begin() + i * np, s.begin() + (i + 1) * np);
-        r.comp_size.emplace_back(size.begin() + i * np, size.begin() + (i + 1) * np);
-    }
-    return r;
+    eng.check(sva_filter_speckles(eng.handle(), io.d.data(), io.sub(), (int)io.n, W, H, invalid,
+                                  max_size, max_diff, io.d.data(), io.sub(), size.data()));
+    return {detail::unpackPlanes(io.d, io.np, io.n), detail::unpackPlanes(io.s, io.np, io.n),
+            detail::unpackPlanes(size, io.np, io.n)};
 }
 
 // An array frame with the speckle filter over every job's map before depth
@@ -964,30 +1019,12 @@ inline std::vector<std::vector<double>> computeArrayDepthFiltered(
     int mode = SVA_FUSE_MEDIAN, double pitch = 0.05,
     std::vector<std::vector<uint16_t>>* maps = nullptr,
     std::vector<std::vector<uint32_t>>* comp_size = nullptr) {
-    const detail::ArrayFrame fr = detail::arrayFrame(images, cameras, pairs, p, pitch,
-                                                     "computeArrayDepthFiltered");
-    std::vector<double> unit;
-    if (route == SVA_ARRAY_GROUPS_MIXED) unit = detail::unitBaselines(fr, 1, pitch);
-    std::vector<int32_t> vs;
-    for (const Camera& c : cameras) {
-        vs.push_back(-(int32_t)std::lround((c.pos3D.x - cameras[0].pos3D.x) / pitch));
-        vs.push_back(-(int32_t)std::lround((c.pos3D.y - cameras[0].pos3D.y) / pitch));
-    }
-    const bool per_group = route != SVA_ARRAY_PAIRS;
-    const size_t np = (size_t)fr.W * fr.H;
-    std::vector<uint32_t> size(comp_size ? np * (per_group ? fr.refs.size() : fr.ap.size()) : 0);
-    auto depth = detail::arrayDepth(fr, cameras, pairs.size(), per_group, maps,
-                                    [&](double f, double pixel_size, double* depth, uint16_t* all) {
-        m.check(fr.call(sva_array_depth_filtered, m.handle(), route,
-                        unit.empty() ? (const double*)nullptr : (const double*)unit.data(), f,
-                        pixel_size, uniqueness, mode, depth, (uint8_t*)nullptr, (uint8_t*)nullptr,
-                        (float*)nullptr, all, (uint16_t*)nullptr, (uint16_t*)nullptr,
-                        (const int32_t*)vs.data(), sub ? 1 : 0, max_diff, min_agree, max_conflict,
-                        (uint8_t*)nullptr, (uint8_t*)nullptr, check ? 1 : 0, speckle_max_size,
-                        speckle_max_diff, comp_size ? size.data() : (uint32_t*)nullptr));
-    });
-    if (comp_size && per_group) *comp_size = fr.split(size);
-    else if (comp_size) fr.scatter(size, pairs.size(), comp_size);
+    const detail::ChainFrame cf(images, cameras, pairs, p, route, pitch, "computeArrayDepthFiltered");
+    std::vector<uint32_t> size = cf.plane(comp_size);
+    auto depth = cf.depth(m, cameras, sva_array_depth_filtered, route, uniqueness, mode, maps, sub,
+                          max_diff, min_agree, max_conflict, (uint8_t*)nullptr, (uint8_t*)nullptr,
+                          check ? 1 : 0, speckle_max_size, speckle_max_diff, cf.ptr(size));
+    cf.give(size, comp_size);
     return depth;
 }
 
@@ -1012,29 +1049,14 @@ inline HolesFilled fillHoles(Engine& eng, const std::vector<std::vector<uint16_t
                              const std::vector<std::vector<float>>& subpix, int W, int H,
                              int max_dist, int min_found = 1, int mode = SVA_FILL_SECOND,
                              uint16_t invalid = 0xFFFF) {
-    const size_t np = (size_t)W * H, n = maps.size();
-    if (maps.empty() || (!subpix.empty() && subpix.size() != n))
-        throw Error(SVA_ERR_INVALID_ARG, "fillHoles: need one sub-pixel map per map");
-    std::vector<uint16_t> d(np * n);
-    std::vector<float> s(subpix.empty() ? 0 : np * n);
-    std::vector<uint8_t> found(np * n);
-    for (size_t i = 0; i < n; i++) {
-        if (maps[i].size() != np || (!subpix.empty() && subpix[i].size() != np))
-            throw Error(SVA_ERR_INVALID_ARG, "fillHoles: map size");
-        std::copy(maps[i].begin(), maps[i].end(), d.begin() + i * np);
-        if (!subpix.empty()) std::copy(subpix[i].begin(), subpix[i].end(), s.begin() + i * np);
-    }
+    detail::PackedMaps io = detail::packFilterMaps("fillHoles", "need one sub-pixel map per map",
+                                                   maps, subpix, W, H);
+    std::vector<uint8_t> found(io.np * io.n);
     // in place on the packed copies
-    eng.check(sva_fill_holes(eng.handle(), d.data(), s.empty() ? nullptr : s.data(), (int)n, W, H,
-                             invalid, max_dist, min_found, mode, d.data(),
-                             s.empty() ? nullptr : s.data(), found.data()));
-    HolesFilled r;
-    for (size_t i = 0; i < n; i++) {
-        r.maps.emplace_back(d.begin() + i * np, d.begin() + (i + 1) * np);
-        if (!s.empty()) r.subpix.emplace_back(s.begin() + i * np, s.begin() + (i + 1) * np);
-        r.n_found.emplace_back(found.begin() + i * np, found.begin() + (i + 1) * np);
-    }
-    return r;
+    eng.check(sva_fill_holes(eng.handle(), io.d.data(), io.sub(), (int)io.n, W, H, invalid, max_dist,
+                             min_found, mode, io.d.data(), io.sub(), found.data()));
+    return {detail::unpackPlanes(io.d, io.np, io.n), detail::unpackPlanes(io.s, io.np, io.n),
+            detail::unpackPlanes(found, io.np, io.n)};
 }
 
 // computeArrayDepthFiltered's frame with hole filling over every job's map
@@ -1052,34 +1074,15 @@ inline std::vector<std::vector<double>> computeArrayDepthFilled(
     int mode = SVA_FUSE_MEDIAN, double pitch = 0.05,
     std::vector<std::vector<uint16_t>>* maps = nullptr,
     std::vector<std::vector<uint8_t>>* n_found = nullptr) {
-    const detail::ArrayFrame fr = detail::arrayFrame(images, cameras, pairs, p, pitch,
-                                                     "computeArrayDepthFilled");
-    std::vector<double> unit;
-    if (route == SVA_ARRAY_GROUPS_MIXED) unit = detail::unitBaselines(fr, 1, pitch);
-    std::vector<int32_t> vs;
-    for (const Camera& c : cameras) {
-        vs.push_back(-(int32_t)std::lround((c.pos3D.x - cameras[0].pos3D.x) / pitch));
-        vs.push_back(-(int32_t)std::lround((c.pos3D.y - cameras[0].pos3D.y) / pitch));
-    }
-    const bool per_group = route != SVA_ARRAY_PAIRS;
-    const size_t np = (size_t)fr.W * fr.H;
-    std::vector<uint8_t> found(n_found ? np * (per_group ? fr.refs.size() : fr.ap.size()) : 0);
-    auto depth = detail::arrayDepth(fr, cameras, pairs.size(), per_group, maps,
-                                    [&](double f, double pixel_size, double* depth, uint16_t* all) {
-        m.check(fr.call(sva_array_depth_filled, m.handle(), route,
-                        unit.empty() ? (const double*)nullptr : (const double*)unit.data(), f,
-                        pixel_size, uniqueness, mode, depth, (uint8_t*)nullptr, (uint8_t*)nullptr,
-                        (float*)nullptr, all, (uint16_t*)nullptr, (uint16_t*)nullptr,
-                        (const int32_t*)vs.data(), sub ? 1 : 0, max_diff, min_agree, max_conflict,
-                        (uint8_t*)nullptr, (uint8_t*)nullptr, check ? 1 : 0, speckle_max_size,
-                        speckle_max_diff, (uint32_t*)nullptr, fill_max_dist, fill_min_found,
-                        fill_mode, n_found ? found.data() : (uint8_t*)nullptr));
-    });
-    if (n_found && per_group) *n_found = fr.split(found);
-    else if (n_found) fr.scatter(found, pairs.size(), n_found);
+    const detail::ChainFrame cf(images, cameras, pairs, p, route, pitch, "computeArrayDepthFilled");
+    std::vector<uint8_t> found = cf.plane(n_found);
+    auto depth = cf.depth(m, cameras, sva_array_depth_filled, route, uniqueness, mode, maps, sub,
+                          max_diff, min_agree, max_conflict, (uint8_t*)nullptr, (uint8_t*)nullptr,
+                          check ? 1 : 0, speckle_max_size, speckle_max_diff, (uint32_t*)nullptr,
+                          fill_max_dist, fill_min_found, fill_mode, cf.ptr(found));
+    cf.give(found, n_found);
     return depth;
 }
-
 
 // ---- weighted median filter --------------------------------
 
@@ -1117,39 +1120,31 @@ inline MedianFiltered weightedMedian(Engine& eng, const std::vector<std::vector<
                                      const std::vector<std::vector<uint8_t>>& select = {},
                                      uint16_t invalid = 0xFFFF) {
     const size_t np = (size_t)W * H, n = maps.size();
-    if (maps.empty() || (!subpix.empty() && subpix.size() != n) ||
-        (!guides.empty() && guides.size() != n) || (!select.empty() && select.size() != n))
-        throw Error(SVA_ERR_INVALID_ARG, "weightedMedian: need one plane per map");
-    std::vector<uint16_t> d(np * n), out(np * n), sup(np * n);
-    std::vector<float> s(subpix.empty() ? 0 : np * n), os(s.size());
-    std::vector<uint8_t> sel(select.empty() ? 0 : np * n);
+    const char* need = "need one plane per map";
+    if ((!guides.empty() && guides.size() != n) || (!select.empty() && select.size() != n))
+        throw Error(SVA_ERR_INVALID_ARG, std::string("weightedMedian: ") + need);
+    detail::PackedMaps in = detail::packFilterMaps("weightedMedian", need, maps, subpix, W, H);
+    std::vector<uint8_t> sel;
     std::vector<const uint8_t*> g;
     for (size_t i = 0; i < n; i++) {
-        if (maps[i].size() != np || (!subpix.empty() && subpix[i].size() != np) ||
-            (!select.empty() && select[i].size() != np))
+        if (!select.empty() && select[i].size() != np)
             throw Error(SVA_ERR_INVALID_ARG, "weightedMedian: map size");
-        std::copy(maps[i].begin(), maps[i].end(), d.begin() + i * np);
-        if (!subpix.empty()) std::copy(subpix[i].begin(), subpix[i].end(), s.begin() + i * np);
-        if (!select.empty()) std::copy(select[i].begin(), select[i].end(), sel.begin() + i * np);
-        if (!guides.empty()) {
-            if (guides[i].width != W || guides[i].height != H || guides[i].pitch != guides[0].pitch)
-                throw Error(SVA_ERR_INVALID_ARG, "weightedMedian: guide size or pitch");
-            g.push_back(guides[i].data);
-        }
+        if (!select.empty()) sel.insert(sel.end(), select[i].begin(), select[i].end());
+        if (guides.empty()) continue;
+        if (guides[i].width != W || guides[i].height != H || guides[i].pitch != guides[0].pitch)
+            throw Error(SVA_ERR_INVALID_ARG, "weightedMedian: guide size or pitch");
+        g.push_back(guides[i].data);
     }
-    eng.check(sva_weighted_median(eng.handle(), d.data(), s.empty() ? nullptr : s.data(),
-                                  g.empty() ? nullptr : g.data(), g.empty() ? 0 : guides[0].pitch,
+    std::vector<uint16_t> out(np * n), sup(np * n);
+    std::vector<float> os(in.s.size());
+    eng.check(sva_weighted_median(eng.handle(), in.d.data(), in.sub(), g.empty() ? nullptr : g.data(),
+                                  g.empty() ? 0 : guides[0].pitch,
                                   weights ? weights->data() : nullptr,
                                   sel.empty() ? nullptr : sel.data(), (int)n, W, H, invalid, radius,
                                   min_support, fill ? 1 : 0, out.data(),
-                                  s.empty() ? nullptr : os.data(), sup.data()));
-    MedianFiltered r;
-    for (size_t i = 0; i < n; i++) {
-        r.maps.emplace_back(out.begin() + i * np, out.begin() + (i + 1) * np);
-        if (!s.empty()) r.subpix.emplace_back(os.begin() + i * np, os.begin() + (i + 1) * np);
-        r.support.emplace_back(sup.begin() + i * np, sup.begin() + (i + 1) * np);
-    }
-    return r;
+                                  in.s.empty() ? nullptr : os.data(), sup.data()));
+    return {detail::unpackPlanes(out, np, n), detail::unpackPlanes(os, np, n),
+            detail::unpackPlanes(sup, np, n)};
 }
 
 // computeArrayDepthFilled's frame with the weighted median filter over every
@@ -1167,36 +1162,17 @@ inline std::vector<std::vector<double>> computeArrayDepthSmoothed(
     int max_conflict = 0, int uniqueness = 0, int mode = SVA_FUSE_MEDIAN, double pitch = 0.05,
     std::vector<std::vector<uint16_t>>* maps = nullptr,
     std::vector<std::vector<uint16_t>>* support = nullptr) {
-    const detail::ArrayFrame fr = detail::arrayFrame(images, cameras, pairs, p, pitch,
-                                                     "computeArrayDepthSmoothed");
-    std::vector<double> unit;
-    if (route == SVA_ARRAY_GROUPS_MIXED) unit = detail::unitBaselines(fr, 1, pitch);
-    std::vector<int32_t> vs;
-    for (const Camera& c : cameras) {
-        vs.push_back(-(int32_t)std::lround((c.pos3D.x - cameras[0].pos3D.x) / pitch));
-        vs.push_back(-(int32_t)std::lround((c.pos3D.y - cameras[0].pos3D.y) / pitch));
-    }
-    const bool per_group = route != SVA_ARRAY_PAIRS;
-    const size_t np = (size_t)fr.W * fr.H;
-    std::vector<uint16_t> sup(support ? np * (per_group ? fr.refs.size() : fr.ap.size()) : 0);
-    auto depth = detail::arrayDepth(fr, cameras, pairs.size(), per_group, maps,
-                                    [&](double f, double pixel_size, double* depth, uint16_t* all) {
-        m.check(fr.call(sva_array_depth_smoothed, m.handle(), route,
-                        unit.empty() ? (const double*)nullptr : (const double*)unit.data(), f,
-                        pixel_size, uniqueness, mode, depth, (uint8_t*)nullptr, (uint8_t*)nullptr,
-                        (float*)nullptr, all, (uint16_t*)nullptr, (uint16_t*)nullptr,
-                        (const int32_t*)vs.data(), sub ? 1 : 0, max_diff, min_agree, max_conflict,
-                        (uint8_t*)nullptr, (uint8_t*)nullptr, check ? 1 : 0, speckle_max_size,
-                        speckle_max_diff, (uint32_t*)nullptr, fill_max_dist, fill_min_found,
-                        fill_mode, (uint8_t*)nullptr, wmed_radius,
-                        weights ? weights->data() : (const uint16_t*)nullptr, wmed_min_support,
-                        wmed_select ? 1 : 0, support ? sup.data() : (uint16_t*)nullptr));
-    });
-    if (support && per_group) *support = fr.split(sup);
-    else if (support) fr.scatter(sup, pairs.size(), support);
+    const detail::ChainFrame cf(images, cameras, pairs, p, route, pitch, "computeArrayDepthSmoothed");
+    std::vector<uint16_t> sup = cf.plane(support);
+    auto depth = cf.depth(m, cameras, sva_array_depth_smoothed, route, uniqueness, mode, maps, sub,
+                          max_diff, min_agree, max_conflict, (uint8_t*)nullptr, (uint8_t*)nullptr,
+                          check ? 1 : 0, speckle_max_size, speckle_max_diff, (uint32_t*)nullptr,
+                          fill_max_dist, fill_min_found, fill_mode, (uint8_t*)nullptr, wmed_radius,
+                          weights ? weights->data() : (const uint16_t*)nullptr, wmed_min_support,
+                          wmed_select ? 1 : 0, cf.ptr(sup));
+    cf.give(sup, support);
     return depth;
 }
-
 
 // ---- refinement and 3-D output ----
 // The reference's names and argument meaning; cv::Mat becomes ImageView (u8)

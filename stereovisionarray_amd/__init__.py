@@ -189,6 +189,14 @@ def _load() -> ct.CDLL:
     lib = ct.CDLL(LIB_PATH)
     vp, i32, sz, dbl = ct.c_void_p, ct.c_int, ct.c_size_t, ct.c_double
     P = ct.POINTER
+    # the entries that take a route: the frame (ctx .. n_groups), then route .. cost_second;
+    # the chain's entries add one argument group per stage
+    frame = [vp, P(vp), i32, i32, i32, sz, P(ArrayPair), i32, P(i32), i32]
+    routed = frame + [i32, P(dbl), dbl, dbl, i32, i32, vp, vp, vp, vp, vp, vp, vp]
+    check_tail = [P(ct.c_int32), i32, i32, i32, i32, vp, vp]
+    speckle_tail = [i32, i32, i32, vp]
+    fill_tail = [i32, i32, i32, vp]
+    wmed_tail = [i32, vp, i32, i32, vp]
     sig = {
         "sva_sgm_params_default": (None, [P(SgmParams)]),
         "sva_abi_version": (i32, []),
@@ -296,32 +304,21 @@ def _load() -> ct.CDLL:
                                             ct.c_uint16, i32, vp, vp, vp]),
         "sva_fuse_depth_conf_sub": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, P(dbl), dbl, dbl,
                                           ct.c_uint16, i32, vp, vp, vp]),
-        "sva_array_depth_sub": (i32, [vp, P(vp), i32, i32, i32, sz, P(ArrayPair), i32, P(i32), i32,
-                                      i32, P(dbl), dbl, dbl, i32, i32, vp, vp, vp, vp, vp, vp, vp]),
+        "sva_array_depth_sub": (i32, routed),
         "sva_cross_check_d": (i32, [vp, vp, vp, i32, i32, i32, P(ct.c_int32), ct.c_uint16, i32, i32,
                                     i32, vp, vp, vp, vp]),
         "sva_cross_check": (i32, [vp, vp, vp, i32, i32, i32, P(ct.c_int32), ct.c_uint16, i32, i32,
                                   i32, vp, vp, vp, vp]),
-        "sva_array_depth_checked": (i32, [vp, P(vp), i32, i32, i32, sz, P(ArrayPair), i32, P(i32),
-                                          i32, i32, P(dbl), dbl, dbl, i32, i32, vp, vp, vp, vp, vp,
-                                          vp, vp, P(ct.c_int32), i32, i32, i32, i32, vp, vp]),
+        "sva_array_depth_checked": (i32, routed + check_tail),
         "sva_filter_speckles_d": (i32, [vp, vp, vp, i32, i32, i32, ct.c_uint16, i32, i32, vp, vp,
                                         vp]),
         "sva_filter_speckles": (i32, [vp, vp, vp, i32, i32, i32, ct.c_uint16, i32, i32, vp, vp, vp]),
-        "sva_array_depth_filtered": (i32, [vp, P(vp), i32, i32, i32, sz, P(ArrayPair), i32, P(i32),
-                                           i32, i32, P(dbl), dbl, dbl, i32, i32, vp, vp, vp, vp, vp,
-                                           vp, vp, P(ct.c_int32), i32, i32, i32, i32, vp, vp, i32,
-                                           i32, i32, vp]),
+        "sva_array_depth_filtered": (i32, routed + check_tail + speckle_tail),
         "sva_fill_holes_d": (i32, [vp, vp, vp, i32, i32, i32, ct.c_uint16, i32, i32, i32, vp, vp, vp]),
         "sva_fill_holes": (i32, [vp, vp, vp, i32, i32, i32, ct.c_uint16, i32, i32, i32, vp, vp, vp]),
-        "sva_array_depth_filled": (i32, [vp, P(vp), i32, i32, i32, sz, P(ArrayPair), i32, P(i32),
-                                         i32, i32, P(dbl), dbl, dbl, i32, i32, vp, vp, vp, vp, vp,
-                                         vp, vp, P(ct.c_int32), i32, i32, i32, i32, vp, vp, i32,
-                                         i32, i32, vp, i32, i32, i32, vp]),
-        "sva_array_depth_smoothed": (i32, [vp, P(vp), i32, i32, i32, sz, P(ArrayPair), i32, P(i32),
-                                           i32, i32, P(dbl), dbl, dbl, i32, i32, vp, vp, vp, vp, vp,
-                                           vp, vp, P(ct.c_int32), i32, i32, i32, i32, vp, vp, i32,
-                                           i32, i32, vp, i32, i32, i32, vp, i32, vp, i32, i32, vp]),
+        "sva_array_depth_filled": (i32, routed + check_tail + speckle_tail + fill_tail),
+        "sva_array_depth_smoothed": (i32, routed + check_tail + speckle_tail + fill_tail +
+                                     wmed_tail),
         "sva_weighted_median_d": (i32, [vp, vp, vp, vp, sz, vp, vp, i32, i32, i32, ct.c_uint16, i32,
                                         i32, i32, vp, vp, vp]),
         "sva_weighted_median": (i32, [vp, vp, vp, vp, sz, vp, vp, i32, i32, i32, ct.c_uint16, i32,
@@ -940,6 +937,17 @@ class Context:
         self._fuse_d(lib.sva_fuse_depth_conf_sub_d, [disps, subpix, cost_min, cost_second], n_maps,
                      W, H, baselines, f, pixel_size, invalid, mode, [depth, n_valid, winner])
 
+    @staticmethod
+    def _filter_maps(disps, subpix):
+        """What the four map filters' host forms share: (d, s, N, H, W, out, osub) --
+        the [N][H][W] u16 maps and f32 maps (or None) as C arrays, and zeroed outputs
+        of their shapes."""
+        d = np.ascontiguousarray(disps, dtype=np.uint16)
+        s = None if subpix is None else np.ascontiguousarray(subpix, dtype=np.float32)
+        N, H, W = d.shape
+        assert s is None or s.shape == d.shape
+        return d, s, N, H, W, np.zeros_like(d), None if s is None else np.zeros_like(s)
+
     def cross_check(self, disps: np.ndarray, view_step, subpix=None, invalid=0xFFFF, max_diff=1,
                     min_agree=1, max_conflict=0, want_agree=True, want_conflict=True):
         """(out, out_sub or None, agree, conflict): sva_cross_check, the cross-view
@@ -947,12 +955,7 @@ class Context:
         baseline; view_step: n (x, y) positions in unit baselines.  A pixel stays
         where at least min_agree other views agree within max_diff and at most
         max_conflict see through it; out_sub (with subpix) is NaN where rejected."""
-        d = np.ascontiguousarray(disps, dtype=np.uint16)
-        s = None if subpix is None else np.ascontiguousarray(subpix, dtype=np.float32)
-        N, H, W = d.shape
-        assert s is None or s.shape == d.shape
-        out = np.zeros_like(d)
-        osub = None if s is None else np.zeros_like(s)
+        d, s, N, H, W, out, osub = self._filter_maps(disps, subpix)
         ag = np.zeros(d.shape, np.uint8) if want_agree else None
         cf = np.zeros(d.shape, np.uint8) if want_conflict else None
         self._chk(lib.sva_cross_check(self.h, _ptr(d), _ptr(s), N, W, H, _steps(view_step, N),
@@ -973,12 +976,7 @@ class Context:
         speckle filter of n maps [n][H][W] u16.  A valid pixel
         whose 4-connected component (neighbours within max_diff) has at most
         max_size pixels becomes `invalid`; out_sub (with subpix) is NaN there."""
-        d = np.ascontiguousarray(disps, dtype=np.uint16)
-        s = None if subpix is None else np.ascontiguousarray(subpix, dtype=np.float32)
-        N, H, W = d.shape
-        assert s is None or s.shape == d.shape
-        out = np.zeros_like(d)
-        osub = None if s is None else np.zeros_like(s)
+        d, s, N, H, W, out, osub = self._filter_maps(disps, subpix)
         size = np.zeros(d.shape, np.uint32) if want_size else None
         self._chk(lib.sva_filter_speckles(self.h, _ptr(d), _ptr(s), N, W, H, invalid, int(max_size),
                                           int(max_diff), _ptr(out), _ptr(osub), _ptr(size)))
@@ -998,12 +996,7 @@ class Context:
         at least min_found valid pixels within max_dist steps along the eight
         directions takes the `mode` statistic of them (sorted by value, distance,
         direction); out_sub (with subpix) takes the chosen source's f32 value."""
-        d = np.ascontiguousarray(disps, dtype=np.uint16)
-        s = None if subpix is None else np.ascontiguousarray(subpix, dtype=np.float32)
-        N, H, W = d.shape
-        assert s is None or s.shape == d.shape
-        out = np.zeros_like(d)
-        osub = None if s is None else np.zeros_like(s)
+        d, s, N, H, W, out, osub = self._filter_maps(disps, subpix)
         found = np.zeros(d.shape, np.uint8) if want_found else None
         self._chk(lib.sva_fill_holes(self.h, _ptr(d), _ptr(s), N, W, H, invalid, int(max_dist),
                                      int(min_found), int(mode), _ptr(out), _ptr(osub), _ptr(found)))
@@ -1026,11 +1019,8 @@ class Context:
         its (2 * radius + 1)^2 window takes their lower weighted median; out_sub
         (with subpix) takes the source pixel's f32 value; support counts the
         candidates."""
-        d = np.ascontiguousarray(disps, dtype=np.uint16)
-        s = None if subpix is None else np.ascontiguousarray(subpix, dtype=np.float32)
+        d, s, N, H, W, out, osub = self._filter_maps(disps, subpix)
         sel = None if select is None else np.ascontiguousarray(select, dtype=np.uint8)
-        N, H, W = d.shape
-        assert s is None or s.shape == d.shape
         assert sel is None or sel.shape == d.shape
         garr, w, pitch, keep = None, None, 0, []
         if weights is not None:
@@ -1047,8 +1037,6 @@ class Context:
                 strides = {W}
             pitch = strides.pop()
             garr = (ct.c_void_p * N)(*[g.ctypes.data for g in keep])
-        out = np.zeros_like(d)
-        osub = None if s is None else np.zeros_like(s)
         sup = np.zeros(d.shape, np.uint16) if want_support else None
         self._chk(lib.sva_weighted_median(self.h, _ptr(d), _ptr(s), garr, pitch, _ptr(w), _ptr(sel),
                                           N, W, H, invalid, int(radius), int(min_support),
@@ -1248,6 +1236,41 @@ class Multi:
                                           _ptr(win), _ptr(sub), _ptr(maps), _ptr(cmin), _ptr(csec)))
         return depth, nv, win, sub, maps, cmin, csec
 
+    # the planes of the post-filter chain's entries, in the order of their results:
+    # name, one per job (else per group), dtype
+    _CHAIN_PLANES = (("depth", False, np.float64), ("n_valid", False, np.uint8),
+                     ("winner", False, np.uint8), ("subpix", True, np.float32),
+                     ("maps", True, np.uint16), ("cost_min", True, np.uint16),
+                     ("cost_second", True, np.uint16), ("agree", False, np.uint8),
+                     ("conflict", False, np.uint8), ("comp_size", True, np.uint32),
+                     ("n_found", True, np.uint8), ("support", True, np.uint16))
+
+    def _array_depth_chain(self, fn, images, pairs, group_start, f, pixel_size, route,
+                           unit_baseline, uniqueness, mode, view_step, sub, cross, want, stages=()):
+        """One call of sva_array_depth_checked, _filtered, _filled or _smoothed.
+        cross: (max_diff, min_agree, max_conflict); want: plane name -> asked for,
+        for the planes the entry can return besides depth; stages: for each stage
+        after the check, its argument group as (the scalars in C order, the name
+        of the plane that ends it).  Returns the planes as a dict, None where not
+        asked for."""
+        fr = _ArrayFrame(images, pairs, group_start)
+        # jobs: pairs on the pair route, which only the entries after the check take
+        nj = len(pairs) if stages and int(route) == SVA_ARRAY_PAIRS else fr.G
+        ub = None if unit_baseline is None else \
+            (ct.c_double * max(1, len(unit_baseline)))(*[float(v) for v in unit_baseline])
+        vs = None if view_step is None else _steps(view_step, len(view_step))
+        want = dict(want, depth=True)
+        r = {name: fr.planes(nj if per_job else fr.G, dtype, want[name])
+             for name, per_job, dtype in self._CHAIN_PLANES if name in want}
+        tail = [_ptr(r.get(name)) for name in ("depth", "n_valid", "winner", "subpix", "maps",
+                                               "cost_min", "cost_second")]
+        tail += [vs, int(sub), *map(int, cross), _ptr(r["agree"]), _ptr(r["conflict"])]
+        for scalars, plane in stages:
+            tail += [*scalars, _ptr(r[plane])]
+        self._chk(fn(self.h, *fr.head, int(route), ub, f, pixel_size, int(uniqueness), int(mode),
+                     *tail))
+        return r
+
     def array_depth_checked(self, images, pairs, group_start, f, pixel_size, view_step,
                             route=SVA_ARRAY_GROUPS, unit_baseline=None, uniqueness=0, sub=0,
                             max_diff=1, min_agree=1, max_conflict=0, want_sub=False,
@@ -1259,20 +1282,14 @@ class Multi:
         subpix [G,H,W] f32, maps, cost_min, cost_second [G,H,W] u16, agree,
         conflict [G,H,W] u8), each but depth None unless asked for; maps, subpix
         and depth are the checked ones."""
-        fr = _ArrayFrame(images, pairs, group_start)
-        ub = None if unit_baseline is None else \
-            (ct.c_double * max(1, len(unit_baseline)))(*[float(v) for v in unit_baseline])
-        vs = None if view_step is None else _steps(view_step, len(view_step))
-        depth = fr.planes(fr.G, np.float64)
-        subp = fr.planes(fr.G, np.float32, want_sub)
-        maps = fr.planes(fr.G, np.uint16, want_maps)
-        cmin, csec = fr.planes(fr.G, np.uint16, want_costs), fr.planes(fr.G, np.uint16, want_costs)
-        ag, cf = fr.planes(fr.G, np.uint8, want_counts), fr.planes(fr.G, np.uint8, want_counts)
-        self._chk(lib.sva_array_depth_checked(
-            self.h, *fr.head, int(route), ub, f, pixel_size, int(uniqueness), SVA_FUSE_MEDIAN,
-            _ptr(depth), None, None, _ptr(subp), _ptr(maps), _ptr(cmin), _ptr(csec), vs, int(sub),
-            int(max_diff), int(min_agree), int(max_conflict), _ptr(ag), _ptr(cf)))
-        return depth, subp, maps, cmin, csec, ag, cf
+        r = self._array_depth_chain(
+            lib.sva_array_depth_checked, images, pairs, group_start, f, pixel_size, route,
+            unit_baseline, uniqueness, SVA_FUSE_MEDIAN, view_step, sub,
+            (max_diff, min_agree, max_conflict),
+            dict(subpix=want_sub, maps=want_maps, cost_min=want_costs, cost_second=want_costs,
+                 agree=want_counts, conflict=want_counts))
+        return tuple(r[k] for k in ("depth", "subpix", "maps", "cost_min", "cost_second", "agree",
+                                    "conflict"))
 
     def array_depth_filtered(self, images, pairs, group_start, f, pixel_size, speckle_max_size,
                              speckle_max_diff, check=0, view_step=None, route=SVA_ARRAY_GROUPS,
@@ -1287,27 +1304,13 @@ class Multi:
         Returns a dict: depth [G,H,W] f64, and where asked for n_valid, winner
         [G,H,W] u8, subpix f32, maps, cost_min, cost_second u16, comp_size u32
         [jobs,H,W], agree, conflict [G,H,W] u8; None where not."""
-        fr = _ArrayFrame(images, pairs, group_start)
-        nj = len(pairs) if int(route) == SVA_ARRAY_PAIRS else fr.G
-        ub = None if unit_baseline is None else \
-            (ct.c_double * max(1, len(unit_baseline)))(*[float(v) for v in unit_baseline])
-        vs = None if view_step is None else _steps(view_step, len(view_step))
-        r = dict(depth=fr.planes(fr.G, np.float64),
-                 n_valid=fr.planes(fr.G, np.uint8, want_n_valid),
-                 winner=fr.planes(fr.G, np.uint8, want_winner),
-                 subpix=fr.planes(nj, np.float32, want_sub), maps=fr.planes(nj, np.uint16, want_maps),
-                 cost_min=fr.planes(nj, np.uint16, want_costs),
-                 cost_second=fr.planes(nj, np.uint16, want_costs),
-                 agree=fr.planes(fr.G, np.uint8, want_counts),
-                 conflict=fr.planes(fr.G, np.uint8, want_counts),
-                 comp_size=fr.planes(nj, np.uint32, want_size))
-        self._chk(lib.sva_array_depth_filtered(
-            self.h, *fr.head, int(route), ub, f, pixel_size, int(uniqueness), int(mode),
-            _ptr(r["depth"]), _ptr(r["n_valid"]), _ptr(r["winner"]), _ptr(r["subpix"]),
-            _ptr(r["maps"]), _ptr(r["cost_min"]), _ptr(r["cost_second"]), vs, int(sub),
-            int(max_diff), int(min_agree), int(max_conflict), _ptr(r["agree"]), _ptr(r["conflict"]),
-            int(check), int(speckle_max_size), int(speckle_max_diff), _ptr(r["comp_size"])))
-        return r
+        return self._array_depth_chain(
+            lib.sva_array_depth_filtered, images, pairs, group_start, f, pixel_size, route,
+            unit_baseline, uniqueness, mode, view_step, sub, (max_diff, min_agree, max_conflict),
+            dict(n_valid=want_n_valid, winner=want_winner, subpix=want_sub, maps=want_maps,
+                 cost_min=want_costs, cost_second=want_costs, agree=want_counts,
+                 conflict=want_counts, comp_size=want_size),
+            [((int(check), int(speckle_max_size), int(speckle_max_diff)), "comp_size")])
 
     def array_depth_filled(self, images, pairs, group_start, f, pixel_size, fill_max_dist,
                            fill_min_found=1, fill_mode=SVA_FILL_SECOND, speckle_max_size=0,
@@ -1321,29 +1324,14 @@ class Multi:
         depth.  Returns array_depth_filtered's dict with n_found [jobs,H,W] u8
         added (None unless asked for).  cost_min / cost_second stay the
         matcher's: at a filled pixel they describe the rejected match."""
-        fr = _ArrayFrame(images, pairs, group_start)
-        nj = len(pairs) if int(route) == SVA_ARRAY_PAIRS else fr.G
-        ub = None if unit_baseline is None else \
-            (ct.c_double * max(1, len(unit_baseline)))(*[float(v) for v in unit_baseline])
-        vs = None if view_step is None else _steps(view_step, len(view_step))
-        r = dict(depth=fr.planes(fr.G, np.float64),
-                 n_valid=fr.planes(fr.G, np.uint8, want_n_valid),
-                 winner=fr.planes(fr.G, np.uint8, want_winner),
-                 subpix=fr.planes(nj, np.float32, want_sub), maps=fr.planes(nj, np.uint16, want_maps),
-                 cost_min=fr.planes(nj, np.uint16, want_costs),
-                 cost_second=fr.planes(nj, np.uint16, want_costs),
-                 agree=fr.planes(fr.G, np.uint8, want_counts),
-                 conflict=fr.planes(fr.G, np.uint8, want_counts),
-                 comp_size=fr.planes(nj, np.uint32, want_size),
-                 n_found=fr.planes(nj, np.uint8, want_found))
-        self._chk(lib.sva_array_depth_filled(
-            self.h, *fr.head, int(route), ub, f, pixel_size, int(uniqueness), int(mode),
-            _ptr(r["depth"]), _ptr(r["n_valid"]), _ptr(r["winner"]), _ptr(r["subpix"]),
-            _ptr(r["maps"]), _ptr(r["cost_min"]), _ptr(r["cost_second"]), vs, int(sub),
-            int(max_diff), int(min_agree), int(max_conflict), _ptr(r["agree"]), _ptr(r["conflict"]),
-            int(check), int(speckle_max_size), int(speckle_max_diff), _ptr(r["comp_size"]),
-            int(fill_max_dist), int(fill_min_found), int(fill_mode), _ptr(r["n_found"])))
-        return r
+        return self._array_depth_chain(
+            lib.sva_array_depth_filled, images, pairs, group_start, f, pixel_size, route,
+            unit_baseline, uniqueness, mode, view_step, sub, (max_diff, min_agree, max_conflict),
+            dict(n_valid=want_n_valid, winner=want_winner, subpix=want_sub, maps=want_maps,
+                 cost_min=want_costs, cost_second=want_costs, agree=want_counts,
+                 conflict=want_counts, comp_size=want_size, n_found=want_found),
+            [((int(check), int(speckle_max_size), int(speckle_max_diff)), "comp_size"),
+             ((int(fill_max_dist), int(fill_min_found), int(fill_mode)), "n_found")])
 
     def array_depth_smoothed(self, images, pairs, group_start, f, pixel_size, wmed_radius,
                              wmed_weights=None, wmed_min_support=1, wmed_select=0,
@@ -1360,34 +1348,18 @@ class Multi:
         unguided median).  wmed_select 0 filters every pixel, 1 only those the fill
         looked at.  Returns array_depth_filled's dict with support [jobs,H,W] u16
         added (None unless asked for)."""
-        fr = _ArrayFrame(images, pairs, group_start)
-        nj = len(pairs) if int(route) == SVA_ARRAY_PAIRS else fr.G
-        ub = None if unit_baseline is None else \
-            (ct.c_double * max(1, len(unit_baseline)))(*[float(v) for v in unit_baseline])
-        vs = None if view_step is None else _steps(view_step, len(view_step))
         w = None if wmed_weights is None else np.ascontiguousarray(wmed_weights, dtype=np.uint16)
         assert w is None or w.shape == (256,)
-        r = dict(depth=fr.planes(fr.G, np.float64),
-                 n_valid=fr.planes(fr.G, np.uint8, want_n_valid),
-                 winner=fr.planes(fr.G, np.uint8, want_winner),
-                 subpix=fr.planes(nj, np.float32, want_sub), maps=fr.planes(nj, np.uint16, want_maps),
-                 cost_min=fr.planes(nj, np.uint16, want_costs),
-                 cost_second=fr.planes(nj, np.uint16, want_costs),
-                 agree=fr.planes(fr.G, np.uint8, want_counts),
-                 conflict=fr.planes(fr.G, np.uint8, want_counts),
-                 comp_size=fr.planes(nj, np.uint32, want_size),
-                 n_found=fr.planes(nj, np.uint8, want_found),
-                 support=fr.planes(nj, np.uint16, want_support))
-        self._chk(lib.sva_array_depth_smoothed(
-            self.h, *fr.head, int(route), ub, f, pixel_size, int(uniqueness), int(mode),
-            _ptr(r["depth"]), _ptr(r["n_valid"]), _ptr(r["winner"]), _ptr(r["subpix"]),
-            _ptr(r["maps"]), _ptr(r["cost_min"]), _ptr(r["cost_second"]), vs, int(sub),
-            int(max_diff), int(min_agree), int(max_conflict), _ptr(r["agree"]), _ptr(r["conflict"]),
-            int(check), int(speckle_max_size), int(speckle_max_diff), _ptr(r["comp_size"]),
-            int(fill_max_dist), int(fill_min_found), int(fill_mode), _ptr(r["n_found"]),
-            int(wmed_radius), _ptr(w), int(wmed_min_support), int(wmed_select),
-            _ptr(r["support"])))
-        return r
+        return self._array_depth_chain(
+            lib.sva_array_depth_smoothed, images, pairs, group_start, f, pixel_size, route,
+            unit_baseline, uniqueness, mode, view_step, sub, (max_diff, min_agree, max_conflict),
+            dict(n_valid=want_n_valid, winner=want_winner, subpix=want_sub, maps=want_maps,
+                 cost_min=want_costs, cost_second=want_costs, agree=want_counts,
+                 conflict=want_counts, comp_size=want_size,
+                 n_found=want_found, support=want_support),
+            [((int(check), int(speckle_max_size), int(speckle_max_diff)), "comp_size"),
+             ((int(fill_max_dist), int(fill_min_found), int(fill_mode)), "n_found"),
+             ((int(wmed_radius), _ptr(w), int(wmed_min_support), int(wmed_select)), "support")])
 
     def array_depth(self, images, pairs, group_start, f, pixel_size, want_maps=False):
         """images: list of HxW u8 numpy views; pairs: list of (ref, other,

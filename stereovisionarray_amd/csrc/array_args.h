@@ -1,10 +1,14 @@
-// array_args.h -- the arguments of one camera-array frame (sva_array_depth,
-// _conf, _mb, _mixed, _sub, _checked, _filtered, _filled and _smoothed) and
-// their validation, shared by multi.cpp and the host test programs
-// (tests/test_array_args_cpu.py, tests/test_array_sub_args_cpu.py,
-// tests/test_cross_check_cpu.py, tests/test_speckle_cpu.py and
-// tests/test_fill_cpu.py compile this header with a C++ compiler under the
+// array_args.h -- the arguments of one camera-array frame (the sva_array_depth*
+// entries) and their validation, shared by multi.cpp and the host
+// test programs (tests/test_array_args_cpu.py, test_array_sub_args_cpu.py,
+// test_cross_check_cpu.py, test_speckle_cpu.py, test_fill_cpu.py and
+// test_wmed_cpu.py compile this header with a C++ compiler under the
 // sanitizers).  Plain C++: no HIP header.
+//
+// The post-filter chain (DESIGN.md §7 has its table): between its jobs and its
+// depth step a frame passes the jobs' maps through the cross-view check, the
+// speckle filter, hole filling and the weighted median, in this order, each
+// enabled by its flag below (cross, speckle, fill, wmed) with its argument group.
 #pragma once
 
 #include <algorithm>
@@ -63,27 +67,26 @@ struct ArrayArgs {
     uint8_t *n_valid = nullptr, *winner = nullptr;
     uint16_t *maps = nullptr, *cost_min = nullptr, *cost_second = nullptr;
     float* subpix = nullptr;                  // per job; sub only
-    // cross (sva_array_depth_checked): the groups' maps go
-    // through sva_cross_check_d before depth; group routes only
+    // cross: the groups' maps go through sva_cross_check_d
+    // into a workspace that the later steps read; group routes only
     bool cross = false;
     const int32_t* view_step = nullptr;       // [n_images][2], unit baselines
     int max_diff = 0, min_agree = 0, max_conflict = 0;
     uint8_t *agree = nullptr, *conflict = nullptr;   // host, per group, nullable
-    // speckle (sva_array_depth_filtered): the jobs' maps go
-    // through sva_filter_speckles_d in place, after the check (check = 1: cross
-    // is set too) and before depth; every route
+    // speckle: the jobs' maps go through sva_filter_speckles_d
+    // in place (check = 1: cross is set too); every route
     bool speckle = false;
     int check = 0;                            // the entry's `check`, as given
     int speckle_max_size = 0, speckle_max_diff = 0;
     uint32_t* comp_size = nullptr;            // host, per job, nullable
-    // fill (sva_array_depth_filled; speckle is set too): the
-    // jobs' maps then go through sva_fill_holes_d in place, before depth
+    // fill (speckle is set too): the jobs' maps go through
+    // sva_fill_holes_d in place
     bool fill = false;
     int fill_max_dist = 0, fill_min_found = 1, fill_mode = 0;
     uint8_t* n_found = nullptr;               // host, per job, nullable
-    // wmed (sva_array_depth_smoothed; fill is set too): the jobs'
-    // maps then go through sva_weighted_median_d, guided by each job's reference
-    // view (wmed_weights null: unguided), into a workspace that step 4 reads.
+    // wmed (fill is set too): the jobs' maps go through
+    // sva_weighted_median_d, guided by each job's reference view (wmed_weights
+    // null: unguided), into a workspace that the depth step reads.
     // wmed_select 0: every pixel, fill = 1; 1: only the pixels the fill looked at
     bool wmed = false;
     int wmed_radius = 1, wmed_min_support = 1, wmed_select = 0;
@@ -264,14 +267,13 @@ inline int check_frame_args(const ArrayArgs& a, std::string& msg, std::vector<in
     return SVA_OK;
 }
 
-// check_frame_args, and with a.speckle (sva_array_depth_filtered) after all of
-// its rules -- those of a.cross among them, which the entry sets iff check == 1
-// -- in this order: a check outside 0 / 1; with check = 0, an agree or conflict
-// plane, then a subpix plane without sub; speckle_max_size < 0;
-// speckle_max_diff < 0.  With a.fill (sva_array_depth_filled) after those:
-// fill_max_dist, fill_min_found, fill_mode out of range.  With a.wmed
-// (sva_array_depth_smoothed) after those: wmed_radius, wmed_min_support out of
-// range, wmed_select outside 0 / 1.
+// check_frame_args, and with a.speckle after all of its rules -- those of
+// a.cross among them, which the entry sets iff check == 1 -- in this order: a
+// check outside 0 / 1; with check = 0, an agree or conflict plane, then a subpix
+// plane without sub; speckle_max_size < 0; speckle_max_diff < 0.  With a.fill
+// after those: fill_max_dist, fill_min_found, fill_mode out of range.  With
+// a.wmed after those: wmed_radius, wmed_min_support out of range, wmed_select
+// outside 0 / 1.
 inline int check_array_args(const ArrayArgs& a, std::string& msg, std::vector<int32_t>& ratio) {
     if (int st = check_frame_args(a, msg, ratio)) return st;
     if (!a.speckle) return SVA_OK;
@@ -297,7 +299,7 @@ inline int check_array_args(const ArrayArgs& a, std::string& msg, std::vector<in
 }
 
 // Which views does each device need?  Pair j runs on device dev_of[j] and needs
-// its ref and its other there.  With refs_on_0 (sva_array_depth_smoothed: the
+// its ref and its other there.  With refs_on_0 (the weighted median stage: the
 // guide of a job is its reference view, and the filter runs on device 0) the
 // reference view of every pair is needed on device 0 as well.  Out: slot_of[d][v],
 // the slot of view v in device d's image buffer (-1: not needed there), slots

@@ -12,7 +12,7 @@
 // through the public per-context entry points (sva_disparity_sgm_d,
 // sva_fuse_depth_d, and sva_disparity_sgm_conf_d / sva_fuse_depth_conf_d for
 // the confidence forms, whose cost planes are gathered like the maps); there
-// is no CPU path.  The nine sva_array_depth* entry points fill one ArrayArgs
+// is no CPU path.  The sva_array_depth* entry points fill one ArrayArgs
 // (array_args.h: the arguments and their checks, in one order) and run one
 // array_frame(): its jobs are pairs, or -- sva_array_depth_mb -- GROUPS (one
 // sva_disparity_sgm_multi_d per reference camera, DESIGN.md §2.2c;
@@ -816,8 +816,8 @@ struct Download {
     }
 };
 
-// One camera-array frame: sva_array_depth, _conf, _mb, _mixed, _sub, _checked, _filtered, _filled and _smoothed (array_args.h
-// has their arguments and checks).  A job is a pair (ArrayRoute::Pairs: every
+// One camera-array frame, behind every sva_array_depth* entry (array_args.h has
+// their arguments and checks).  A job is a pair (ArrayRoute::Pairs: every
 // pair through sva_disparity_sgm_d or, with conf, sva_disparity_sgm_conf_d; a
 // group's maps are fused by `mode`) or a GROUP (group g's
 // pairs go through one sva_disparity_sgm_multi_d on device g mod n_devices,
@@ -1085,7 +1085,7 @@ int array_frame(void* mp, const ArrayArgs& a) {
     return dl.finish(m);
 }
 
-// What the nine entry points share; as it stands, sva_array_depth's: the pair
+// What every entry point shares; as it stands, sva_array_depth's: the pair
 // route, plain matching, median fusion.
 ArrayArgs frame_args(const uint8_t* const* images, int n_images, int W, int H, size_t pitch,
                      const sva_array_pair* pairs, int n_pairs, const int32_t* group_start,
@@ -1109,6 +1109,80 @@ ArrayArgs frame_args(const uint8_t* const* images, int n_images, int W, int H, s
     a.cost_min = cost_min;
     a.cost_second = cost_second;
     return a;
+}
+
+// frame_args and the arguments of the entries that take a route
+// (sva_array_depth_sub and the four after it): the confidence instance, `mode`
+// as given.  Then one setter per argument group of the post-filter chain.
+ArrayArgs routed_args(const uint8_t* const* images, int n_images, int W, int H, size_t pitch,
+                      const sva_array_pair* pairs, int n_pairs, const int32_t* group_start,
+                      int n_groups, int route, const double* unit_baseline, double f,
+                      double pixel_size, int uniqueness, int mode, double* depth, uint8_t* n_valid,
+                      uint8_t* winner, float* subpix, uint16_t* maps, uint16_t* cost_min,
+                      uint16_t* cost_second) {
+    ArrayArgs a = frame_args(images, n_images, W, H, pitch, pairs, n_pairs, group_start, n_groups,
+                             f, pixel_size, uniqueness, depth, maps, cost_min, cost_second);
+    a.route = array_route_of(route);
+    a.conf = true;
+    a.mode = mode;
+    a.unit_baseline = unit_baseline;
+    a.n_valid = n_valid;
+    a.winner = winner;
+    a.subpix = subpix;
+    return a;
+}
+
+// on = false (check = 0) ignores the check's arguments; the planes stay, for
+// check_array_args to refuse.
+void set_cross(ArrayArgs& a, bool on, const int32_t* view_step, int max_diff, int min_agree,
+               int max_conflict, uint8_t* agree, uint8_t* conflict) {
+    a.cross = on;
+    if (on) {
+        a.view_step = view_step;
+        a.max_diff = max_diff;
+        a.min_agree = min_agree;
+        a.max_conflict = max_conflict;
+    }
+    a.agree = agree;
+    a.conflict = conflict;
+}
+
+void set_speckle(ArrayArgs& a, int check, int max_size, int max_diff, uint32_t* comp_size) {
+    a.speckle = true;
+    a.check = check;
+    a.speckle_max_size = max_size;
+    a.speckle_max_diff = max_diff;
+    a.comp_size = comp_size;
+}
+
+// (an entry without the fill does not call this: its arguments keep their defaults)
+void set_fill(ArrayArgs& a, int max_dist, int min_found, int mode, uint8_t* n_found) {
+    a.fill = true;
+    a.fill_max_dist = max_dist;
+    a.fill_min_found = min_found;
+    a.fill_mode = mode;
+    a.n_found = n_found;
+}
+
+void set_wmed(ArrayArgs& a, int radius, const uint16_t* weights, int min_support, int select,
+              uint16_t* support) {
+    a.wmed = true;
+    a.wmed_radius = radius;
+    a.wmed_weights = weights;
+    a.wmed_min_support = min_support;
+    a.wmed_select = select;
+    a.support = support;
+}
+
+// The frame of an entry that takes `sub` as a number: one outside 0 / 1 is
+// refused here, before it becomes ArrayArgs::sub, whatever else is wrong.
+int sub_frame(void* mp, ArrayArgs& a, int sub) {
+    if (sub != 0 && sub != 1) {
+        Multi* m = as_multi(mp);
+        return m ? m->fail(SVA_ERR_INVALID_ARG, "sub must be 0 or 1") : SVA_ERR_INVALID_ARG;
+    }
+    a.sub = sub != 0;
+    return array_frame(mp, a);
 }
 }  // namespace
 
@@ -1185,17 +1259,10 @@ int sva_array_depth_sub(void* mp, const uint8_t* const* images, int n_images, in
                         const double* unit_baseline, double f, double pixel_size, int uniqueness,
                         int mode, double* depth, uint8_t* n_valid, uint8_t* winner, float* subpix,
                         uint16_t* maps, uint16_t* cost_min, uint16_t* cost_second) {
-    ArrayArgs a = frame_args(images, n_images, W, H, pitch, pairs, n_pairs, group_start, n_groups,
-                             f, pixel_size, uniqueness, depth, maps, cost_min, cost_second);
-    a.route = array_route_of(route);
-    a.conf = true;
-    a.sub = true;
-    a.mode = mode;
-    a.unit_baseline = unit_baseline;
-    a.n_valid = n_valid;
-    a.winner = winner;
-    a.subpix = subpix;
-    return array_frame(mp, a);
+    ArrayArgs a = routed_args(images, n_images, W, H, pitch, pairs, n_pairs, group_start, n_groups,
+                              route, unit_baseline, f, pixel_size, uniqueness, mode, depth, n_valid,
+                              winner, subpix, maps, cost_min, cost_second);
+    return sub_frame(mp, a, 1);
 }
 
 int sva_array_depth_checked(void* mp, const uint8_t* const* images, int n_images, int W, int H,
@@ -1206,125 +1273,49 @@ int sva_array_depth_checked(void* mp, const uint8_t* const* images, int n_images
                             uint8_t* winner, float* subpix, uint16_t* maps, uint16_t* cost_min,
                             uint16_t* cost_second, const int32_t* view_step, int sub, int max_diff,
                             int min_agree, int max_conflict, uint8_t* agree, uint8_t* conflict) {
-    if (sub != 0 && sub != 1) {
-        Multi* m = as_multi(mp);
-        return m ? m->fail(SVA_ERR_INVALID_ARG, "sub must be 0 or 1") : SVA_ERR_INVALID_ARG;
-    }
-    ArrayArgs a = frame_args(images, n_images, W, H, pitch, pairs, n_pairs, group_start, n_groups,
-                             f, pixel_size, uniqueness, depth, maps, cost_min, cost_second);
-    a.route = array_route_of(route);
-    a.conf = true;
-    a.sub = sub != 0;
-    a.mode = mode;
-    a.unit_baseline = unit_baseline;
-    a.n_valid = n_valid;
-    a.winner = winner;
-    a.subpix = subpix;
-    a.cross = true;
-    a.view_step = view_step;
-    a.max_diff = max_diff;
-    a.min_agree = min_agree;
-    a.max_conflict = max_conflict;
-    a.agree = agree;
-    a.conflict = conflict;
-    return array_frame(mp, a);
+    ArrayArgs a = routed_args(images, n_images, W, H, pitch, pairs, n_pairs, group_start, n_groups,
+                              route, unit_baseline, f, pixel_size, uniqueness, mode, depth, n_valid,
+                              winner, subpix, maps, cost_min, cost_second);
+    set_cross(a, true, view_step, max_diff, min_agree, max_conflict, agree, conflict);
+    return sub_frame(mp, a, sub);
 }
 
-// sva_array_depth_filtered (fill = false: the fill's arguments are not looked
-// at), sva_array_depth_filled and sva_array_depth_smoothed (wmed = true).
-static int array_depth_post(void* mp, const uint8_t* const* images, int n_images, int W, int H,
-                            size_t pitch, const sva_array_pair* pairs, int n_pairs,
-                            const int32_t* group_start, int n_groups, int route,
-                            const double* unit_baseline, double f, double pixel_size,
-                            int uniqueness, int mode, double* depth, uint8_t* n_valid,
-                            uint8_t* winner, float* subpix, uint16_t* maps, uint16_t* cost_min,
-                            uint16_t* cost_second, const int32_t* view_step, int sub, int max_diff,
-                            int min_agree, int max_conflict, uint8_t* agree, uint8_t* conflict,
-                            int check, int speckle_max_size, int speckle_max_diff,
-                            uint32_t* comp_size, bool fill, int fill_max_dist, int fill_min_found,
-                            int fill_mode, uint8_t* n_found, bool wmed = false, int wmed_radius = 1,
-                            const uint16_t* wmed_weights = nullptr, int wmed_min_support = 1,
-                            int wmed_select = 0, uint16_t* support = nullptr) {
-    if (sub != 0 && sub != 1) {
-        Multi* m = as_multi(mp);
-        return m ? m->fail(SVA_ERR_INVALID_ARG, "sub must be 0 or 1") : SVA_ERR_INVALID_ARG;
-    }
-    ArrayArgs a = frame_args(images, n_images, W, H, pitch, pairs, n_pairs, group_start, n_groups,
-                             f, pixel_size, uniqueness, depth, maps, cost_min, cost_second);
-    a.route = array_route_of(route);
-    a.conf = true;
-    a.sub = sub != 0;
-    a.mode = mode;
-    a.unit_baseline = unit_baseline;
-    a.n_valid = n_valid;
-    a.winner = winner;
-    a.subpix = subpix;
-    a.cross = check == 1;
-    if (a.cross) {   // check = 0 ignores the check's arguments
-        a.view_step = view_step;
-        a.max_diff = max_diff;
-        a.min_agree = min_agree;
-        a.max_conflict = max_conflict;
-    }
-    a.agree = agree;
-    a.conflict = conflict;
-    a.speckle = true;
-    a.check = check;
-    a.speckle_max_size = speckle_max_size;
-    a.speckle_max_diff = speckle_max_diff;
-    a.comp_size = comp_size;
-    a.fill = fill;
-    if (fill) {
-        a.fill_max_dist = fill_max_dist;
-        a.fill_min_found = fill_min_found;
-        a.fill_mode = fill_mode;
-        a.n_found = n_found;
-    }
-    a.wmed = wmed;
-    if (wmed) {
-        a.wmed_radius = wmed_radius;
-        a.wmed_weights = wmed_weights;
-        a.wmed_min_support = wmed_min_support;
-        a.wmed_select = wmed_select;
-        a.support = support;
-    }
-    return array_frame(mp, a);
-}
-
+// check = 0: the check's arguments are not looked at.
 int sva_array_depth_filtered(void* mp, const uint8_t* const* images, int n_images, int W, int H,
                              size_t pitch, const sva_array_pair* pairs, int n_pairs,
                              const int32_t* group_start, int n_groups, int route,
                              const double* unit_baseline, double f, double pixel_size,
                              int uniqueness, int mode, double* depth, uint8_t* n_valid,
                              uint8_t* winner, float* subpix, uint16_t* maps, uint16_t* cost_min,
-                             uint16_t* cost_second, const int32_t* view_step, int sub,
-                             int max_diff, int min_agree, int max_conflict, uint8_t* agree,
-                             uint8_t* conflict, int check, int speckle_max_size,
-                             int speckle_max_diff, uint32_t* comp_size) {
-    return array_depth_post(mp, images, n_images, W, H, pitch, pairs, n_pairs, group_start,
-                            n_groups, route, unit_baseline, f, pixel_size, uniqueness, mode, depth,
-                            n_valid, winner, subpix, maps, cost_min, cost_second, view_step, sub,
-                            max_diff, min_agree, max_conflict, agree, conflict, check,
-                            speckle_max_size, speckle_max_diff, comp_size, false, 0, 1, 0, nullptr);
+                             uint16_t* cost_second, const int32_t* view_step, int sub, int max_diff,
+                             int min_agree, int max_conflict, uint8_t* agree, uint8_t* conflict,
+                             int check, int speckle_max_size, int speckle_max_diff,
+                             uint32_t* comp_size) {
+    ArrayArgs a = routed_args(images, n_images, W, H, pitch, pairs, n_pairs, group_start, n_groups,
+                              route, unit_baseline, f, pixel_size, uniqueness, mode, depth, n_valid,
+                              winner, subpix, maps, cost_min, cost_second);
+    set_cross(a, check == 1, view_step, max_diff, min_agree, max_conflict, agree, conflict);
+    set_speckle(a, check, speckle_max_size, speckle_max_diff, comp_size);
+    return sub_frame(mp, a, sub);
 }
 
 int sva_array_depth_filled(void* mp, const uint8_t* const* images, int n_images, int W, int H,
                            size_t pitch, const sva_array_pair* pairs, int n_pairs,
                            const int32_t* group_start, int n_groups, int route,
-                           const double* unit_baseline, double f, double pixel_size,
-                           int uniqueness, int mode, double* depth, uint8_t* n_valid,
-                           uint8_t* winner, float* subpix, uint16_t* maps, uint16_t* cost_min,
-                           uint16_t* cost_second, const int32_t* view_step, int sub, int max_diff,
-                           int min_agree, int max_conflict, uint8_t* agree, uint8_t* conflict,
-                           int check, int speckle_max_size, int speckle_max_diff,
-                           uint32_t* comp_size, int fill_max_dist, int fill_min_found,
-                           int fill_mode, uint8_t* n_found) {
-    return array_depth_post(mp, images, n_images, W, H, pitch, pairs, n_pairs, group_start,
-                            n_groups, route, unit_baseline, f, pixel_size, uniqueness, mode, depth,
-                            n_valid, winner, subpix, maps, cost_min, cost_second, view_step, sub,
-                            max_diff, min_agree, max_conflict, agree, conflict, check,
-                            speckle_max_size, speckle_max_diff, comp_size, true, fill_max_dist,
-                            fill_min_found, fill_mode, n_found);
+                           const double* unit_baseline, double f, double pixel_size, int uniqueness,
+                           int mode, double* depth, uint8_t* n_valid, uint8_t* winner,
+                           float* subpix, uint16_t* maps, uint16_t* cost_min, uint16_t* cost_second,
+                           const int32_t* view_step, int sub, int max_diff, int min_agree,
+                           int max_conflict, uint8_t* agree, uint8_t* conflict, int check,
+                           int speckle_max_size, int speckle_max_diff, uint32_t* comp_size,
+                           int fill_max_dist, int fill_min_found, int fill_mode, uint8_t* n_found) {
+    ArrayArgs a = routed_args(images, n_images, W, H, pitch, pairs, n_pairs, group_start, n_groups,
+                              route, unit_baseline, f, pixel_size, uniqueness, mode, depth, n_valid,
+                              winner, subpix, maps, cost_min, cost_second);
+    set_cross(a, check == 1, view_step, max_diff, min_agree, max_conflict, agree, conflict);
+    set_speckle(a, check, speckle_max_size, speckle_max_diff, comp_size);
+    set_fill(a, fill_max_dist, fill_min_found, fill_mode, n_found);
+    return sub_frame(mp, a, sub);
 }
 
 int sva_array_depth_smoothed(void* mp, const uint8_t* const* images, int n_images, int W, int H,
@@ -1333,20 +1324,21 @@ int sva_array_depth_smoothed(void* mp, const uint8_t* const* images, int n_image
                              const double* unit_baseline, double f, double pixel_size,
                              int uniqueness, int mode, double* depth, uint8_t* n_valid,
                              uint8_t* winner, float* subpix, uint16_t* maps, uint16_t* cost_min,
-                             uint16_t* cost_second, const int32_t* view_step, int sub,
-                             int max_diff, int min_agree, int max_conflict, uint8_t* agree,
-                             uint8_t* conflict, int check, int speckle_max_size,
-                             int speckle_max_diff, uint32_t* comp_size, int fill_max_dist,
-                             int fill_min_found, int fill_mode, uint8_t* n_found, int wmed_radius,
+                             uint16_t* cost_second, const int32_t* view_step, int sub, int max_diff,
+                             int min_agree, int max_conflict, uint8_t* agree, uint8_t* conflict,
+                             int check, int speckle_max_size, int speckle_max_diff,
+                             uint32_t* comp_size, int fill_max_dist, int fill_min_found,
+                             int fill_mode, uint8_t* n_found, int wmed_radius,
                              const uint16_t* wmed_weights, int wmed_min_support, int wmed_select,
                              uint16_t* support) {
-    return array_depth_post(mp, images, n_images, W, H, pitch, pairs, n_pairs, group_start,
-                            n_groups, route, unit_baseline, f, pixel_size, uniqueness, mode, depth,
-                            n_valid, winner, subpix, maps, cost_min, cost_second, view_step, sub,
-                            max_diff, min_agree, max_conflict, agree, conflict, check,
-                            speckle_max_size, speckle_max_diff, comp_size, true, fill_max_dist,
-                            fill_min_found, fill_mode, n_found, true, wmed_radius, wmed_weights,
-                            wmed_min_support, wmed_select, support);
+    ArrayArgs a = routed_args(images, n_images, W, H, pitch, pairs, n_pairs, group_start, n_groups,
+                              route, unit_baseline, f, pixel_size, uniqueness, mode, depth, n_valid,
+                              winner, subpix, maps, cost_min, cost_second);
+    set_cross(a, check == 1, view_step, max_diff, min_agree, max_conflict, agree, conflict);
+    set_speckle(a, check, speckle_max_size, speckle_max_diff, comp_size);
+    set_fill(a, fill_max_dist, fill_min_found, fill_mode, n_found);
+    set_wmed(a, wmed_radius, wmed_weights, wmed_min_support, wmed_select, support);
+    return sub_frame(mp, a, sub);
 }
 
 }  // extern "C"

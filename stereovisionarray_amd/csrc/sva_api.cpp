@@ -16,12 +16,9 @@
 #include <vector>
 
 #include "cost_mixed_math.h"
-#include "cross_check_math.h"
-#include "fill_math.h"
-#include "speckle_math.h"
+#include "map_filter_args.h"
 #include "sva_internal.h"
 #include "sva_tuning.h"
-#include "wmedian_math.h"
 
 using namespace sva;
 
@@ -617,6 +614,180 @@ struct Staging {
     }
 };
 
+}  // namespace
+
+// ------------------------------------- the map filters --
+// Behind the eight entries near the end of this file; a template, so outside extern "C".
+namespace {
+
+// A filter's workspace of `per` bytes for every pixel of the n maps, grown with
+// its own out-of-memory report.
+int filter_workspace(Ctx* c, DevBuf& ws, const MapArgs& m, size_t per, const char* name,
+                     uint32_t** out) {
+    const unsigned long long planes = (unsigned long long)m.W * m.H * (unsigned long long)m.n;
+    if (planes > (~(size_t)0) / per)
+        return fail(c, SVA_ERR_OUT_OF_MEMORY,
+                    std::string(name) + " workspace: larger than the address space");
+    const hipError_t e = ws.ensure((size_t)planes * per);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();   // the failed allocation is reported here, not by a later call
+        return fail(c, SVA_ERR_OUT_OF_MEMORY,
+                    std::string(name) + " workspace: " + hipGetErrorString(e));
+    }
+    *out = (uint32_t*)ws.ptr;
+    return SVA_OK;
+}
+
+// Each run_x: a checked call on device planes.
+int run_cross(Ctx* c, const CrossArgs& a) {
+    const MapArgs& m = a.m;
+    const int order = c->dbg_cross_order >= 0 ? c->dbg_cross_order : tune::kCrossTileMajor;
+    SVA_HIP(c, launch_cross_check(*c, m.disps, m.subpix, m.n, m.W, m.H, a.view_step, m.invalid,
+                                  a.max_diff, a.min_agree, a.max_conflict, order, m.out, m.out_sub,
+                                  a.agree, a.conflict),
+            "cross-check launch");
+    return SVA_OK;
+}
+
+// The label and count planes, then the launches.  max_size = 0 without comp_size
+// is a copy and takes no workspace.
+int run_speckle(Ctx* c, const SpeckleArgs& a) {
+    const MapArgs& m = a.m;
+    uint32_t *label = nullptr, *count = nullptr;
+    if (a.max_size != 0 || a.comp_size) {
+        if (int s = filter_workspace(c, c->speckle_ws, m, 8, "speckle", &label)) return s;
+        count = label + (size_t)m.W * m.H * (size_t)m.n;
+    }
+    SVA_HIP(c, launch_speckle(*c, m.disps, m.subpix, m.n, m.W, m.H, m.invalid, a.max_size,
+                              a.max_diff, label, count, m.out, m.out_sub, a.comp_size),
+            "speckle launch");
+    return SVA_OK;
+}
+
+// The key planes, then the launches.  max_dist = 0 is a copy and takes no workspace.
+int run_fill(Ctx* c, const FillArgs& a) {
+    const MapArgs& m = a.m;
+    uint32_t* keys = nullptr;
+    if (a.max_dist != 0)
+        if (int s = filter_workspace(c, c->fill_ws, m, 32, "fill", &keys)) return s;
+    const int segment = c->dbg_fill_segment > 0 ? c->dbg_fill_segment : tune::kFillSegment;
+    SVA_HIP(c, launch_fill(*c, m.disps, m.subpix, m.n, m.W, m.H, m.invalid, a.max_dist, a.min_found,
+                           a.mode, segment, keys, m.out, m.out_sub, a.n_found),
+            "fill launch");
+    return SVA_OK;
+}
+
+int run_wmed(Ctx* c, const WmedArgs& a) {
+    const MapArgs& m = a.m;
+    SVA_HIP(c, launch_wmedian(*c, m.disps, m.subpix, a.guides, a.guide_pitch, a.weights, a.select,
+                              m.n, m.W, m.H, m.invalid, a.radius, a.min_support, a.fill, m.out,
+                              m.out_sub, a.support),
+            "wmed launch");
+    return SVA_OK;
+}
+
+// The common planes of a host call on the device: the u16 maps through in_a and
+// the f32 maps (sub_in: whether the filter takes them) through in_mask; in_place:
+// the filter runs in place on them, else into out_a and out_b.  A host entry
+// stages its own planes through g as well, runs run_x on the device form of its
+// arguments, downloads its own planes and returns done().
+struct StagedMaps {
+    Staging g;
+    const MapArgs& host;
+    size_t nnp;
+    MapArgs d;
+    StagedMaps(Ctx* c, const MapArgs& m, bool in_place, bool sub_in)
+        : g{c}, host(m), nnp((size_t)m.W * m.H * (size_t)m.n), d(m) {
+        uint16_t* dd = g.up<uint16_t>(c->in_a, m.disps, nnp * 2);
+        float* ds = sub_in ? g.up<float>(c->in_mask, m.subpix, nnp * 4) : nullptr;
+        d.disps = dd;
+        d.subpix = ds;
+        d.out = in_place ? dd : g.out<uint16_t>(c->out_a, nnp * 2);
+        d.out_sub = !m.out_sub ? nullptr : in_place ? ds : g.out<float>(c->out_b, nnp * 4);
+    }
+    int done() {
+        g.down(host.out, d.out, nnp * 2);
+        g.down(host.out_sub, d.out_sub, nnp * 4);
+        return g.sync();
+    }
+};
+
+// The count planes stage through out_c, agree first.
+int cross_host(Ctx* c, const CrossArgs& a) {
+    StagedMaps s(c, a.m, false, a.m.subpix != nullptr);
+    uint8_t* cnt = a.agree || a.conflict ? s.g.out<uint8_t>(c->out_c, s.nnp * 2) : nullptr;
+    CrossArgs d = a;
+    d.m = s.d;
+    d.agree = a.agree ? cnt : nullptr;
+    d.conflict = a.conflict ? cnt + s.nnp : nullptr;
+    if (s.g.st) return s.g.st;
+    if (int st = run_cross(c, d)) return st;
+    s.g.down(a.agree, d.agree, s.nnp);
+    s.g.down(a.conflict, d.conflict, s.nnp);
+    return s.done();
+}
+
+int speckle_host(Ctx* c, const SpeckleArgs& a) {
+    StagedMaps s(c, a.m, true, a.m.out_sub != nullptr);
+    SpeckleArgs d = a;
+    d.m = s.d;
+    d.comp_size = a.comp_size ? s.g.out<uint32_t>(c->out_c, s.nnp * 4) : nullptr;
+    if (s.g.st) return s.g.st;
+    if (int st = run_speckle(c, d)) return st;
+    s.g.down(a.comp_size, d.comp_size, s.nnp * 4);
+    return s.done();
+}
+
+int fill_host(Ctx* c, const FillArgs& a) {
+    StagedMaps s(c, a.m, true, a.m.out_sub != nullptr);
+    FillArgs d = a;
+    d.m = s.d;
+    d.n_found = a.n_found ? s.g.out<uint8_t>(c->out_c, s.nnp) : nullptr;
+    if (s.g.st) return s.g.st;
+    if (int st = run_fill(c, d)) return st;
+    s.g.down(a.n_found, d.n_found, s.nnp);
+    return s.done();
+}
+
+// select stages through in_c and support through out_c; the guides are packed
+// on the device, one W x H image per map (weights stays the caller's host table).
+int wmed_host(Ctx* c, const WmedArgs& a) {
+    const MapArgs& m = a.m;
+    StagedMaps s(c, m, false, m.out_sub != nullptr);
+    const size_t np = (size_t)m.W * m.H;
+    WmedArgs d = a;
+    d.m = s.d;
+    d.select = a.select ? s.g.up<uint8_t>(c->in_c, a.select, s.nnp) : nullptr;
+    std::vector<const uint8_t*> dguides;
+    if (a.guides) {
+        uint8_t* dg = s.g.out<uint8_t>(c->wmed_guides, s.nnp);
+        for (int i = 0; i < m.n && s.g.st == SVA_OK; i++) {
+            s.g.note(hipMemcpy2DAsync(dg + (size_t)i * np, m.W, a.guides[i], a.guide_pitch, m.W,
+                                      m.H, hipMemcpyHostToDevice, c->stream),
+                     "upload");
+            dguides.push_back(dg + (size_t)i * np);
+        }
+        d.guides = dguides.data();
+    }
+    d.guide_pitch = (size_t)m.W;
+    d.support = a.support ? s.g.out<uint16_t>(c->out_c, s.nnp * 2) : nullptr;
+    if (s.g.st) return s.g.st;
+    if (int st = run_wmed(c, d)) return st;
+    s.g.down(a.support, d.support, s.nnp * 2);
+    return s.done();
+}
+
+// One entry: the context, the rules, then the call on device planes (host null)
+// or on host planes.
+template <class Args>
+int filter_entry(void* ctx, const Args& a, int (*check)(const Args&, std::string&),
+                 int (*run)(Ctx*, const Args&), int (*host)(Ctx*, const Args&)) {
+    Ctx* c = as_ctx(ctx);
+    SVA_CHECK_CTX(c);
+    std::string msg;
+    if (int s = check(a, msg)) return fail(c, s, msg);
+    return host ? host(c, a) : run(c, a);
+}
 }  // namespace
 
 // ------------------------------------------------------------------ ABI --
@@ -1812,378 +1983,81 @@ int sva_fuse_depth_conf_sub(void* ctx, const uint16_t* disps, const float* subpi
                       kFuseByCost | kFuseSub | kFuseHost);
 }
 
-// ------------------------- cross-view consistency check --
-namespace {
-bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return a && b && x < y + nb && y < x + na;
-}
-
-// The rules of sva_cross_check and sva_cross_check_d, in sva.h's order; the
-// pointers are the caller's (host or device), which is where overlap matters.
-int check_cross(Ctx* c, const uint16_t* disps, const float* subpix, int n, int W, int H,
-                const int32_t* view_step, int max_diff, int min_agree, int max_conflict,
-                const uint16_t* out, const float* out_sub) {
-    if (!disps || !view_step || !out) return fail(c, SVA_ERR_INVALID_ARG, "null pointer");
-    if (n < 1 || n > cc::kMaxViews) return fail(c, SVA_ERR_INVALID_ARG, "n_views must be 1..32");
-    if (W <= 0 || H <= 0) return fail(c, SVA_ERR_INVALID_ARG, "image size must be positive");
-    if ((unsigned long long)W * (unsigned long long)H >= (1ull << 31))
-        return fail(c, SVA_ERR_UNSUPPORTED, "the cross-view check needs W * H < 2^31");
-    const char* m = cc::step_range_error(view_step, n);
-    if (!m) m = cc::step_distinct_error(view_step, n);
-    if (!m) m = cc::thresholds_error(max_diff, min_agree, max_conflict);
-    if (m) return fail(c, SVA_ERR_INVALID_ARG, m);
-    if (out_sub && !subpix) return fail(c, SVA_ERR_INVALID_ARG, "out_sub needs subpix");
-    const size_t b16 = (size_t)W * H * 2 * (size_t)n, b32 = b16 * 2;
-    if (ranges_overlap(out, b16, disps, b16) || ranges_overlap(out, b16, subpix, b32) ||
-        ranges_overlap(out_sub, b32, disps, b16) || ranges_overlap(out_sub, b32, subpix, b32))
-        return fail(c, SVA_ERR_INVALID_ARG, "an output overlaps an input");
-    return SVA_OK;
-}
-
-int run_cross(Ctx* c, const uint16_t* disps, const float* subpix, int n, int W, int H,
-              const int32_t* view_step, uint16_t invalid, int max_diff, int min_agree,
-              int max_conflict, uint16_t* out, float* out_sub, uint8_t* agree, uint8_t* conflict) {
-    const int order = c->dbg_cross_order >= 0 ? c->dbg_cross_order : tune::kCrossTileMajor;
-    SVA_HIP(c, launch_cross_check(*c, disps, subpix, n, W, H, view_step, invalid, max_diff,
-                                  min_agree, max_conflict, order, out, out_sub, agree, conflict),
-            "cross-check launch");
-    return SVA_OK;
-}
-}  // namespace
-
+// ----------------- the map filters of the post-filter chain --
+// sva_cross_check, sva_filter_speckles, sva_fill_holes, sva_weighted_median and
+// their _d twins.  Each builds its args struct (map_filter_args.h, which also
+// has check_x, the rules) from the positional ABI and goes through filter_entry
+// (above, with run_x and the host staging).
 int sva_cross_check_d(void* ctx, const uint16_t* disps, const float* subpix, int n, int W, int H,
                       const int32_t* view_step, uint16_t invalid, int max_diff, int min_agree,
                       int max_conflict, uint16_t* out, float* out_sub, uint8_t* agree,
                       uint8_t* conflict) {
-    Ctx* c = as_ctx(ctx);
-    SVA_CHECK_CTX(c);
-    if (int s = check_cross(c, disps, subpix, n, W, H, view_step, max_diff, min_agree, max_conflict,
-                            out, out_sub))
-        return s;
-    return run_cross(c, disps, subpix, n, W, H, view_step, invalid, max_diff, min_agree,
-                     max_conflict, out, out_sub, agree, conflict);
+    return filter_entry<CrossArgs>(ctx, {{disps, subpix, n, W, H, invalid, out, out_sub}, view_step,
+                                         max_diff, min_agree, max_conflict, agree, conflict},
+                                   check_cross, run_cross, nullptr);
 }
 
-// The count planes stage through out_c, agree first.
 int sva_cross_check(void* ctx, const uint16_t* disps, const float* subpix, int n, int W, int H,
                     const int32_t* view_step, uint16_t invalid, int max_diff, int min_agree,
                     int max_conflict, uint16_t* out, float* out_sub, uint8_t* agree,
                     uint8_t* conflict) {
-    Ctx* c = as_ctx(ctx);
-    SVA_CHECK_CTX(c);
-    if (int s = check_cross(c, disps, subpix, n, W, H, view_step, max_diff, min_agree, max_conflict,
-                            out, out_sub))
-        return s;
-    const size_t nnp = (size_t)W * H * (size_t)n;
-    Staging g{c};
-    const uint16_t* dd = g.up<uint16_t>(c->in_a, disps, nnp * 2);
-    const float* ds = subpix ? g.up<float>(c->in_mask, subpix, nnp * 4) : nullptr;
-    uint16_t* dout = g.out<uint16_t>(c->out_a, nnp * 2);
-    float* dsub = out_sub ? g.out<float>(c->out_b, nnp * 4) : nullptr;
-    uint8_t* cnt = agree || conflict ? g.out<uint8_t>(c->out_c, nnp * 2) : nullptr;
-    uint8_t* dag = agree ? cnt : nullptr;
-    uint8_t* dcf = conflict ? cnt + nnp : nullptr;
-    if (g.st) return g.st;
-    if (int s = run_cross(c, dd, ds, n, W, H, view_step, invalid, max_diff, min_agree, max_conflict,
-                          dout, dsub, dag, dcf))
-        return s;
-    g.down(out, dout, nnp * 2);
-    g.down(out_sub, dsub, nnp * 4);
-    g.down(agree, dag, nnp);
-    g.down(conflict, dcf, nnp);
-    return g.sync();
+    return filter_entry<CrossArgs>(ctx, {{disps, subpix, n, W, H, invalid, out, out_sub}, view_step,
+                                         max_diff, min_agree, max_conflict, agree, conflict},
+                                   check_cross, run_cross, cross_host);
 }
-
-// ------------------------------------------- speckle filter --
-namespace {
-// a and b may be the same plane (in place), and nothing else
-bool bad_overlap(const void* a, const void* b, size_t nb_each) {
-    return a != b && ranges_overlap(a, nb_each, b, nb_each);
-}
-
-// The rules of sva_filter_speckles and sva_filter_speckles_d, in sva.h's order;
-// the pointers are the caller's (host or device), which is where overlap matters.
-int check_speckle(Ctx* c, const uint16_t* disps, const float* subpix, int n, int W, int H,
-                  int max_size, int max_diff, const uint16_t* out, const float* out_sub,
-                  const uint32_t* comp_size) {
-    if (!disps || !out) return fail(c, SVA_ERR_INVALID_ARG, "null pointer");
-    if (n < 1) return fail(c, SVA_ERR_INVALID_ARG, "n_maps must be >= 1");
-    if (W <= 0 || H <= 0) return fail(c, SVA_ERR_INVALID_ARG, "image size must be positive");
-    if ((unsigned long long)W * (unsigned long long)H >= (1ull << 31))
-        return fail(c, SVA_ERR_UNSUPPORTED, "the speckle filter needs W * H < 2^31");
-    if (const char* m = sp::thresholds_error(max_size, max_diff))
-        return fail(c, SVA_ERR_INVALID_ARG, m);
-    if (out_sub && !subpix) return fail(c, SVA_ERR_INVALID_ARG, "out_sub needs subpix");
-    // the byte counts saturate: a frame too large for the address space overlaps everything
-    const unsigned long long px = (unsigned long long)W * H;
-    const size_t lim = ~(size_t)0;
-    const size_t b16 = px > lim / 2 / (size_t)n ? lim : (size_t)px * 2 * (size_t)n;
-    const size_t b32 = b16 > lim / 2 ? lim : b16 * 2;
-    if ((out != disps && ranges_overlap(out, b16, disps, b16)) ||
-        ranges_overlap(out, b16, subpix, b32) || ranges_overlap(out, b16, out_sub, b32) ||
-        ranges_overlap(out, b16, comp_size, b32) || ranges_overlap(out_sub, b32, disps, b16) ||
-        bad_overlap(out_sub, subpix, b32) || ranges_overlap(out_sub, b32, comp_size, b32) ||
-        ranges_overlap(comp_size, b32, disps, b16) || ranges_overlap(comp_size, b32, subpix, b32))
-        return fail(c, SVA_ERR_INVALID_ARG,
-                    "an output overlaps an input or another output (in place: out == disps, "
-                    "out_sub == subpix)");
-    return SVA_OK;
-}
-
-// The workspace, then the launches.  max_size = 0 without comp_size is a copy
-// and takes no workspace.
-int run_speckle(Ctx* c, const uint16_t* disps, const float* subpix, int n, int W, int H,
-                uint16_t invalid, int max_size, int max_diff, uint16_t* out, float* out_sub,
-                uint32_t* comp_size) {
-    uint32_t *label = nullptr, *count = nullptr;
-    if (max_size != 0 || comp_size) {
-        const unsigned long long planes = (unsigned long long)W * H * (unsigned long long)n;
-        if (planes > (~(size_t)0) / 8)
-            return fail(c, SVA_ERR_OUT_OF_MEMORY, "speckle workspace: larger than the address space");
-        const hipError_t e = c->speckle_ws.ensure((size_t)planes * 8);
-        if (e != hipSuccess) {
-            (void)hipGetLastError();   // the failed allocation is reported here, not by a later call
-            return fail(c, SVA_ERR_OUT_OF_MEMORY,
-                        std::string("speckle workspace: ") + hipGetErrorString(e));
-        }
-        label = (uint32_t*)c->speckle_ws.ptr;
-        count = label + planes;
-    }
-    SVA_HIP(c, launch_speckle(*c, disps, subpix, n, W, H, invalid, max_size, max_diff, label, count,
-                              out, out_sub, comp_size),
-            "speckle launch");
-    return SVA_OK;
-}
-}  // namespace
 
 int sva_filter_speckles_d(void* ctx, const uint16_t* disps, const float* subpix, int n, int W,
                           int H, uint16_t invalid, int max_size, int max_diff, uint16_t* out,
                           float* out_sub, uint32_t* comp_size) {
-    Ctx* c = as_ctx(ctx);
-    SVA_CHECK_CTX(c);
-    if (int s = check_speckle(c, disps, subpix, n, W, H, max_size, max_diff, out, out_sub, comp_size))
-        return s;
-    return run_speckle(c, disps, subpix, n, W, H, invalid, max_size, max_diff, out, out_sub,
-                       comp_size);
+    return filter_entry<SpeckleArgs>(ctx, {{disps, subpix, n, W, H, invalid, out, out_sub}, max_size,
+                                           max_diff, comp_size},
+                                     check_speckle, run_speckle, nullptr);
 }
 
-// On the device the staged maps are filtered in place.
 int sva_filter_speckles(void* ctx, const uint16_t* disps, const float* subpix, int n, int W, int H,
                         uint16_t invalid, int max_size, int max_diff, uint16_t* out, float* out_sub,
                         uint32_t* comp_size) {
-    Ctx* c = as_ctx(ctx);
-    SVA_CHECK_CTX(c);
-    if (int s = check_speckle(c, disps, subpix, n, W, H, max_size, max_diff, out, out_sub, comp_size))
-        return s;
-    const size_t nnp = (size_t)W * H * (size_t)n;
-    Staging g{c};
-    uint16_t* dd = g.up<uint16_t>(c->in_a, disps, nnp * 2);
-    float* ds = out_sub ? g.up<float>(c->in_mask, subpix, nnp * 4) : nullptr;
-    uint32_t* dsize = comp_size ? g.out<uint32_t>(c->out_c, nnp * 4) : nullptr;
-    if (g.st) return g.st;
-    if (int s = run_speckle(c, dd, ds, n, W, H, invalid, max_size, max_diff, dd, ds, dsize))
-        return s;
-    g.down(out, dd, nnp * 2);
-    g.down(out_sub, ds, nnp * 4);
-    g.down(comp_size, dsize, nnp * 4);
-    return g.sync();
+    return filter_entry<SpeckleArgs>(ctx, {{disps, subpix, n, W, H, invalid, out, out_sub}, max_size,
+                                           max_diff, comp_size},
+                                     check_speckle, run_speckle, speckle_host);
 }
-
-// ---------------------------------------------- hole filling --
-namespace {
-// The rules of sva_fill_holes and sva_fill_holes_d, in sva.h's order; the
-// pointers are the caller's (host or device), which is where overlap matters.
-int check_fill(Ctx* c, const uint16_t* disps, const float* subpix, int n, int W, int H,
-               int max_dist, int min_found, int mode, const uint16_t* out, const float* out_sub,
-               const uint8_t* n_found) {
-    if (!disps || !out) return fail(c, SVA_ERR_INVALID_ARG, "null pointer");
-    if (n < 1) return fail(c, SVA_ERR_INVALID_ARG, "n_maps must be >= 1");
-    if (W <= 0 || H <= 0) return fail(c, SVA_ERR_INVALID_ARG, "image size must be positive");
-    if ((unsigned long long)W * (unsigned long long)H >= (1ull << 31))
-        return fail(c, SVA_ERR_UNSUPPORTED, "hole filling needs W * H < 2^31");
-    if (const char* m = fl::thresholds_error(max_dist, min_found, mode))
-        return fail(c, SVA_ERR_INVALID_ARG, m);
-    if (out_sub && !subpix) return fail(c, SVA_ERR_INVALID_ARG, "out_sub needs subpix");
-    // the byte counts saturate: a frame too large for the address space overlaps everything
-    const unsigned long long px = (unsigned long long)W * H;
-    const size_t lim = ~(size_t)0;
-    const size_t b8 = px > lim / 4 / (size_t)n ? lim / 4 : (size_t)px * (size_t)n;
-    const size_t b16 = b8 * 2, b32 = b8 * 4;
-    if ((out != disps && ranges_overlap(out, b16, disps, b16)) ||
-        ranges_overlap(out, b16, subpix, b32) || ranges_overlap(out, b16, out_sub, b32) ||
-        ranges_overlap(out, b16, n_found, b8) || ranges_overlap(out_sub, b32, disps, b16) ||
-        bad_overlap(out_sub, subpix, b32) || ranges_overlap(out_sub, b32, n_found, b8) ||
-        ranges_overlap(n_found, b8, disps, b16) || ranges_overlap(n_found, b8, subpix, b32))
-        return fail(c, SVA_ERR_INVALID_ARG,
-                    "an output overlaps an input or another output (in place: out == disps, "
-                    "out_sub == subpix)");
-    return SVA_OK;
-}
-
-// The workspace, then the launches.  max_dist = 0 is a copy and takes no workspace.
-int run_fill(Ctx* c, const uint16_t* disps, const float* subpix, int n, int W, int H,
-             uint16_t invalid, int max_dist, int min_found, int mode, uint16_t* out, float* out_sub,
-             uint8_t* n_found) {
-    uint32_t* keys = nullptr;
-    if (max_dist != 0) {
-        const unsigned long long planes = (unsigned long long)W * H * (unsigned long long)n;
-        if (planes > (~(size_t)0) / 32)
-            return fail(c, SVA_ERR_OUT_OF_MEMORY, "fill workspace: larger than the address space");
-        const hipError_t e = c->fill_ws.ensure((size_t)planes * 32);
-        if (e != hipSuccess) {
-            (void)hipGetLastError();   // the failed allocation is reported here, not by a later call
-            return fail(c, SVA_ERR_OUT_OF_MEMORY,
-                        std::string("fill workspace: ") + hipGetErrorString(e));
-        }
-        keys = (uint32_t*)c->fill_ws.ptr;
-    }
-    const int segment = c->dbg_fill_segment > 0 ? c->dbg_fill_segment : tune::kFillSegment;
-    SVA_HIP(c, launch_fill(*c, disps, subpix, n, W, H, invalid, max_dist, min_found, mode, segment,
-                           keys, out, out_sub, n_found),
-            "fill launch");
-    return SVA_OK;
-}
-}  // namespace
 
 int sva_fill_holes_d(void* ctx, const uint16_t* disps, const float* subpix, int n, int W, int H,
                      uint16_t invalid, int max_dist, int min_found, int mode, uint16_t* out,
                      float* out_sub, uint8_t* n_found) {
-    Ctx* c = as_ctx(ctx);
-    SVA_CHECK_CTX(c);
-    if (int s = check_fill(c, disps, subpix, n, W, H, max_dist, min_found, mode, out, out_sub,
-                           n_found))
-        return s;
-    return run_fill(c, disps, subpix, n, W, H, invalid, max_dist, min_found, mode, out, out_sub,
-                    n_found);
+    return filter_entry<FillArgs>(ctx, {{disps, subpix, n, W, H, invalid, out, out_sub}, max_dist,
+                                        min_found, mode, n_found},
+                                  check_fill, run_fill, nullptr);
 }
 
-// On the device the staged maps are filled in place.
 int sva_fill_holes(void* ctx, const uint16_t* disps, const float* subpix, int n, int W, int H,
                    uint16_t invalid, int max_dist, int min_found, int mode, uint16_t* out,
                    float* out_sub, uint8_t* n_found) {
-    Ctx* c = as_ctx(ctx);
-    SVA_CHECK_CTX(c);
-    if (int s = check_fill(c, disps, subpix, n, W, H, max_dist, min_found, mode, out, out_sub,
-                           n_found))
-        return s;
-    const size_t nnp = (size_t)W * H * (size_t)n;
-    Staging g{c};
-    uint16_t* dd = g.up<uint16_t>(c->in_a, disps, nnp * 2);
-    float* ds = out_sub ? g.up<float>(c->in_mask, subpix, nnp * 4) : nullptr;
-    uint8_t* dfound = n_found ? g.out<uint8_t>(c->out_c, nnp) : nullptr;
-    if (g.st) return g.st;
-    if (int s = run_fill(c, dd, ds, n, W, H, invalid, max_dist, min_found, mode, dd, ds, dfound))
-        return s;
-    g.down(out, dd, nnp * 2);
-    g.down(out_sub, ds, nnp * 4);
-    g.down(n_found, dfound, nnp);
-    return g.sync();
+    return filter_entry<FillArgs>(ctx, {{disps, subpix, n, W, H, invalid, out, out_sub}, max_dist,
+                                        min_found, mode, n_found},
+                                  check_fill, run_fill, fill_host);
 }
-
-// -------------------------------- weighted median filter --
-namespace {
-// The rules of sva_weighted_median and sva_weighted_median_d, in sva.h's order;
-// the pointers are the caller's (host or device), which is where overlap matters.
-int check_wmed(Ctx* c, const uint16_t* disps, const float* subpix, const uint8_t* const* guides,
-               size_t guide_pitch, const uint16_t* weights, const uint8_t* select, int n, int W,
-               int H, int radius, int min_support, int fill, const uint16_t* out,
-               const float* out_sub, const uint16_t* support) {
-    if (!disps || !out) return fail(c, SVA_ERR_INVALID_ARG, "null pointer");
-    if (n < 1) return fail(c, SVA_ERR_INVALID_ARG, "n_maps must be >= 1");
-    if (W <= 0 || H <= 0) return fail(c, SVA_ERR_INVALID_ARG, "image size must be positive");
-    if ((unsigned long long)W * (unsigned long long)H >= (1ull << 31))
-        return fail(c, SVA_ERR_UNSUPPORTED, "the weighted median needs W * H < 2^31");
-    if (const char* m = wm::thresholds_error(radius, min_support, fill))
-        return fail(c, SVA_ERR_INVALID_ARG, m);
-    if ((guides == nullptr) != (weights == nullptr))
-        return fail(c, SVA_ERR_INVALID_ARG, "guides and weights go together");
-    if (guides) {
-        for (int i = 0; i < n; i++)
-            if (!guides[i]) return fail(c, SVA_ERR_INVALID_ARG, "null guide image");
-        if (guide_pitch < (size_t)W) return fail(c, SVA_ERR_INVALID_ARG, "guide pitch < width");
-    }
-    if (out_sub && !subpix) return fail(c, SVA_ERR_INVALID_ARG, "out_sub needs subpix");
-    // the byte counts saturate: a frame too large for the address space overlaps everything
-    const unsigned long long px = (unsigned long long)W * H;
-    const size_t lim = ~(size_t)0;
-    const size_t b8 = px > lim / 4 / (size_t)n ? lim / 4 : (size_t)px * (size_t)n;
-    const size_t b16 = b8 * 2, b32 = b8 * 4;
-    const size_t bg = guides && (size_t)(H - 1) <= (lim / 4 - (size_t)W) / guide_pitch
-                          ? (size_t)(H - 1) * guide_pitch + (size_t)W
-                          : lim / 4;
-    const void* outs[3] = {out, out_sub, support};
-    const size_t out_bytes[3] = {b16, b32, b16};
-    bool bad = false;
-    for (int o = 0; o < 3; o++) {
-        bad = bad || ranges_overlap(outs[o], out_bytes[o], disps, b16) ||
-              ranges_overlap(outs[o], out_bytes[o], subpix, b32) ||
-              ranges_overlap(outs[o], out_bytes[o], select, b8);
-        for (int i = 0; guides && i < n; i++)
-            bad = bad || ranges_overlap(outs[o], out_bytes[o], guides[i], bg);
-        for (int q = o + 1; q < 3; q++)
-            bad = bad || ranges_overlap(outs[o], out_bytes[o], outs[q], out_bytes[q]);
-    }
-    if (bad)
-        return fail(c, SVA_ERR_INVALID_ARG,
-                    "an output overlaps an input or another output (in place is not offered)");
-    return SVA_OK;
-}
-}  // namespace
 
 int sva_weighted_median_d(void* ctx, const uint16_t* disps, const float* subpix,
                           const uint8_t* const* guides, size_t guide_pitch,
                           const uint16_t* weights, const uint8_t* select, int n, int W, int H,
                           uint16_t invalid, int radius, int min_support, int fill, uint16_t* out,
                           float* out_sub, uint16_t* support) {
-    Ctx* c = as_ctx(ctx);
-    SVA_CHECK_CTX(c);
-    if (int s = check_wmed(c, disps, subpix, guides, guide_pitch, weights, select, n, W, H, radius,
-                           min_support, fill, out, out_sub, support))
-        return s;
-    SVA_HIP(c, launch_wmedian(*c, disps, subpix, guides, guide_pitch, weights, select, n, W, H,
-                              invalid, radius, min_support, fill, out, out_sub, support),
-            "wmed launch");
-    return SVA_OK;
+    return filter_entry<WmedArgs>(ctx, {{disps, subpix, n, W, H, invalid, out, out_sub}, guides,
+                                        guide_pitch, weights, select, radius, min_support, fill,
+                                        support},
+                                  check_wmed, run_wmed, nullptr);
 }
 
-// The guides are packed on the device, one W x H image per map.
 int sva_weighted_median(void* ctx, const uint16_t* disps, const float* subpix,
                         const uint8_t* const* guides, size_t guide_pitch, const uint16_t* weights,
                         const uint8_t* select, int n, int W, int H, uint16_t invalid, int radius,
                         int min_support, int fill, uint16_t* out, float* out_sub,
                         uint16_t* support) {
-    Ctx* c = as_ctx(ctx);
-    SVA_CHECK_CTX(c);
-    if (int s = check_wmed(c, disps, subpix, guides, guide_pitch, weights, select, n, W, H, radius,
-                           min_support, fill, out, out_sub, support))
-        return s;
-    const size_t np = (size_t)W * H, nnp = np * (size_t)n;
-    Staging g{c};
-    uint16_t* dd = g.up<uint16_t>(c->in_a, disps, nnp * 2);
-    float* ds = out_sub ? g.up<float>(c->in_mask, subpix, nnp * 4) : nullptr;
-    uint8_t* dsel = select ? g.up<uint8_t>(c->in_c, select, nnp) : nullptr;
-    std::vector<const uint8_t*> dguides;
-    if (guides) {
-        uint8_t* dg = g.out<uint8_t>(c->wmed_guides, nnp);
-        for (int i = 0; i < n && g.st == SVA_OK; i++) {
-            g.note(hipMemcpy2DAsync(dg + (size_t)i * np, W, guides[i], guide_pitch, W, H,
-                                    hipMemcpyHostToDevice, c->stream),
-                   "upload");
-            dguides.push_back(dg + (size_t)i * np);
-        }
-    }
-    uint16_t* dout = g.out<uint16_t>(c->out_a, nnp * 2);
-    float* dosub = out_sub ? g.out<float>(c->out_b, nnp * 4) : nullptr;
-    uint16_t* dsup = support ? g.out<uint16_t>(c->out_c, nnp * 2) : nullptr;
-    if (g.st) return g.st;
-    SVA_HIP(c, launch_wmedian(*c, dd, ds, guides ? dguides.data() : nullptr, (size_t)W, weights,
-                              dsel, n, W, H, invalid, radius, min_support, fill, dout, dosub, dsup),
-            "wmed launch");
-    g.down(out, dout, nnp * 2);
-    g.down(out_sub, dosub, nnp * 4);
-    g.down(support, dsup, nnp * 2);
-    return g.sync();
+    return filter_entry<WmedArgs>(ctx, {{disps, subpix, n, W, H, invalid, out, out_sub}, guides,
+                                        guide_pitch, weights, select, radius, min_support, fill,
+                                        support},
+                                  check_wmed, run_wmed, wmed_host);
 }
 
 // ------------------------------------------ refinement / 3-D --
