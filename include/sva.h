@@ -844,6 +844,87 @@ int sva_weighted_median(void* ctx, const uint16_t* disps, const float* subpix,
                         int height, uint16_t invalid, int radius, int min_support, int fill,
                         uint16_t* out, float* out_sub, uint16_t* support);
 
+/* Rectification: n >= 1 raw views src [n][src_h][src_pitch] u8
+ * warped onto the ideal grid, out [n][out_h][out_pitch] u8 (device / host); the
+ * output size may differ from the source size.  views: a HOST array of n
+ * sva_rectify_view in both forms, read before the call returns.  For the output
+ * pixel (x, y) of a view, all in f64, every operation rounded on its own (no
+ * contraction), the division IEEE, in exactly this order:
+ *   w  = (h6*x + h7*y) + h8
+ *   u  = ((h0*x + h1*y) + h2) / w          v  = ((h3*x + h4*y) + h5) / w
+ *   if k1 == k2 == p1 == p2 == k3 == 0:    sx = u, sy = v     (no distortion step)
+ *   else:
+ *     xn = (u - cx) / fx                   yn = (v - cy) / fy
+ *     xx = xn*xn   yy = yn*yn   xy = xn*yn   r2 = xx + yy
+ *     rad = 1 + r2*(k1 + r2*(k2 + r2*k3))
+ *     xd = (xn*rad + (2*p1)*xy) + p2*(r2 + 2*xx)
+ *     yd = (yn*rad + p1*(r2 + 2*yy)) + (2*p2)*xy
+ *     sx = xd*fx + cx                      sy = yd*fy + cy
+ *   inside = w > 0 and -2^20 < sx < 2^20 and -2^20 < sy < 2^20   (false on NaN)
+ *   qx = (int)rint(sx*32), qy = (int)rint(sy*32)                 (half to even; 1/32 px)
+ *   X = qx >> 5, a = qx & 31, Y = qy >> 5, b = qy & 31           (arithmetic shift)
+ *   taps (X,Y) (X+1,Y) (X,Y+1) (X+1,Y+1), weights (32-a)(32-b), a(32-b), (32-a)b, ab
+ *   value = (sum of weight * tap + 512) >> 10
+ * A tap of weight 0 is neither read nor judged; a tap of positive weight outside
+ * the source [0, src_w) x [0, src_h) contributes `border`.  valid (nullable): u8
+ * [n][out_h][out_pitch], 1 iff the pixel is inside and every tap of positive
+ * weight lies in the source.  map (nullable): i32 [n][out_h][out_w][2], (qx, qy).
+ * A pixel that is not inside: value = border, valid = 0, both map entries
+ * INT32_MIN.  The rule is the engine's own: it uses OpenCV's 1/32 px grid but not
+ * its coefficient tables, and parity with cv::remap is not claimed.
+ * Returned before anything is launched, in this order: SVA_ERR_INVALID_ARG for a
+ * null src, views or out, or n, a width or a height < 1; SVA_ERR_UNSUPPORTED for
+ * a width or height above SVA_RECTIFY_MAX_SIZE; SVA_ERR_INVALID_ARG for
+ * src_pitch < src_w or out_pitch < out_w; border outside 0..255; out, valid or
+ * map overlapping src or each other (not an in-place filter); the first rule a
+ * view breaks, view 0 first, the message naming the view: a non-finite entry of
+ * h; non-finite cx or cy; fx or fy not finite or <= 0; a non-finite coefficient.
+ * _d is asynchronous on the context stream and is timed as "rectify": one launch
+ * per 25 views. */
+typedef struct sva_rectify_view {
+    double h[9];            /* row-major 3x3: rectified pixel -> undistorted raw pixel */
+    double cx, cy, fx, fy;  /* raw camera: principal point and focal lengths, pixels   */
+    double k1, k2, p1, p2, k3; /* Brown-Conrady coefficients, OpenCV's order           */
+} sva_rectify_view;
+#define SVA_RECTIFY_MAX_SIZE 32767
+int sva_rectify_d(void* ctx, const uint8_t* src, int n, int src_w, int src_h, size_t src_pitch,
+                  const sva_rectify_view* views, int out_w, int out_h, size_t out_pitch,
+                  int border, uint8_t* out, uint8_t* valid, int32_t* map);
+int sva_rectify(void* ctx, const uint8_t* src, int n, int src_w, int src_h, size_t src_pitch,
+                const sva_rectify_view* views, int out_w, int out_h, size_t out_pitch, int border,
+                uint8_t* out, uint8_t* valid, int32_t* map);
+/* A view from a calibration, on the host alone (no context): h = K_raw . R .
+ * K_ideal^-1, where R takes ideal-camera rays to raw-camera rays; cx, cy, fx, fy
+ * from K_raw; dist = {k1, k2, p1, p2, k3} copied.  All matrices row-major 3x3.
+ * The order of operations (csrc/rectify_math.h): K_ideal^-1 by the adjugate, each
+ * cofactor a difference of two products, det = (k0*c0 + k1*c3) + k2*c6, every
+ * entry cofactor / det; then M = R . K_ideal^-1 and h = K_raw . M, every entry of
+ * a product ((a_i0*b_0j + a_i1*b_1j) + a_i2*b_2j); no contraction.
+ * SVA_ERR_INVALID_ARG for a null pointer, non-finite input, a K_raw with skew
+ * (K_raw[1] or K_raw[3] != 0) or a bottom row other than 0 0 1, or a singular
+ * K_ideal; *out is written on success only. */
+int sva_rectify_view_of(const double K_raw[9], const double dist[5], const double R[9],
+                        const double K_ideal[9], sva_rectify_view* out);
+
+/* Masking: n_maps >= 1 disparity maps disps [n_maps][H][W] u16
+ * (device / host) take `invalid` where valid [n_maps][H][W] u8 -- one plane per
+ * map, a rectified reference view's valid plane -- is 0, and stay as they are
+ * elsewhere.  subpix (nullable) f32; out_sub (nullable, needs subpix) gets NaN
+ * where valid is 0, as the cross-view check writes a rejected pixel, and the 32
+ * bits of subpix elsewhere.  In place is allowed: out == disps, out_sub == subpix.
+ * Returned before anything is launched, in this order: SVA_ERR_INVALID_ARG for a
+ * null disps, valid or out, n_maps < 1, a width or height < 1;
+ * SVA_ERR_UNSUPPORTED for width * height >= 2^31; SVA_ERR_INVALID_ARG for out_sub
+ * without subpix, or any overlap of an output with an input or the other output
+ * except exactly in place.  _d is asynchronous on the context stream and is
+ * timed as "mask_maps". */
+int sva_mask_maps_d(void* ctx, const uint16_t* disps, const float* subpix, int n_maps, int width,
+                    int height, const uint8_t* valid, uint16_t invalid, uint16_t* out,
+                    float* out_sub);
+int sva_mask_maps(void* ctx, const uint16_t* disps, const float* subpix, int n_maps, int width,
+                  int height, const uint8_t* valid, uint16_t invalid, uint16_t* out,
+                  float* out_sub);
+
 /* Disparity -> depth, CameraStereoVision.cpp:47,98-100 (f64; 0 where disp 0). */
 int sva_disparity_to_depth_d(void* ctx, const uint8_t* disp, int n, double cam_distance,
                              double f, double pixel_size, double* depth);
@@ -1143,6 +1224,42 @@ int sva_array_depth_smoothed(void* multi, const uint8_t* const* images, int n_im
                              int fill_min_found, int fill_mode, uint8_t* n_found, int wmed_radius,
                              const uint16_t* wmed_weights, int wmed_min_support, int wmed_select,
                              uint16_t* support);
+/* An array frame from RAW views: sva_array_depth_smoothed's
+ * arguments, then rect (a host array of n_images sva_rectify_view), border, mask
+ * (0 / 1), views_out and valid_out (nullable host [n_images][H][W] u8).  images
+ * are the raw views, of the frame's size.  Every device rectifies the views it
+ * needs with one sva_rectify_d launch on its copy stream, behind their uploads,
+ * and the jobs wait for that launch; everything after it sees rectified views.
+ * With mask = 1 every job's map -- and its f32 plane with sub = 1 -- goes through
+ * sva_mask_maps_d with the valid plane of its reference view, after the gather
+ * and before the cross-view check, on every route (on SVA_ARRAY_PAIRS per pair).
+ * views_out / valid_out receive the rectified views and their valid planes; a
+ * view that no pair names is left untouched.  Every stage of the chain can be
+ * switched off here: wmed_radius = 0 turns the weighted median off for this
+ * entry only (the outputs are then sva_array_depth_filled's bit for bit, support
+ * is left untouched), the other stages have their own off value.
+ * Bit for bit the stand-alone composition: sva_rectify; the same route's plain
+ * job maps on the rectified views; sva_mask_maps, sva_cross_check,
+ * sva_filter_speckles, sva_fill_holes, sva_weighted_median; the matching
+ * sva_fuse_depth*.
+ * After all of sva_array_depth_smoothed's rules (wmed_radius 0 allowed), in this
+ * order, SVA_ERR_INVALID_ARG for: a null rect; the first rule a view of rect
+ * breaks (sva_rectify's, view 0 first); border outside 0..255; mask outside
+ * 0..1.  Before anything is launched. */
+int sva_array_depth_rectified(void* multi, const uint8_t* const* images, int n_images, int width,
+                              int height, size_t pitch, const sva_array_pair* pairs, int n_pairs,
+                              const int32_t* group_start, int n_groups, int route,
+                              const double* unit_baseline, double f, double pixel_size,
+                              int uniqueness, int mode, double* depth, uint8_t* n_valid,
+                              uint8_t* winner, float* subpix, uint16_t* maps, uint16_t* cost_min,
+                              uint16_t* cost_second, const int32_t* view_step, int sub,
+                              int max_diff, int min_agree, int max_conflict, uint8_t* agree,
+                              uint8_t* conflict, int check, int speckle_max_size,
+                              int speckle_max_diff, uint32_t* comp_size, int fill_max_dist,
+                              int fill_min_found, int fill_mode, uint8_t* n_found, int wmed_radius,
+                              const uint16_t* wmed_weights, int wmed_min_support, int wmed_select,
+                              uint16_t* support, const sva_rectify_view* rect, int border,
+                              int mask, uint8_t* views_out, uint8_t* valid_out);
 
 #ifdef __cplusplus
 }

@@ -1174,6 +1174,120 @@ inline std::vector<std::vector<double>> computeArrayDepthSmoothed(
     return depth;
 }
 
+// ---- rectification ----------------------------------
+
+// The view of a calibration (sva_rectify_view_of; host only): h = K_raw . R .
+// K_ideal^-1 with R taking ideal-camera rays to raw-camera rays, all row-major
+// 3x3; dist = {k1, k2, p1, p2, k3}.  Throws on a K_raw with skew or a bottom row
+// other than 0 0 1, a singular K_ideal or non-finite input.
+inline sva_rectify_view rectifyViewOf(const std::array<double, 9>& K_raw,
+                                      const std::array<double, 5>& dist,
+                                      const std::array<double, 9>& R,
+                                      const std::array<double, 9>& K_ideal) {
+    sva_rectify_view v;
+    if (int st = sva_rectify_view_of(K_raw.data(), dist.data(), R.data(), K_ideal.data(), &v))
+        throw Error(st, "rectifyViewOf: bad calibration");
+    return v;
+}
+
+// What rectifyViews makes of each raw view: the rectified view (out_w * out_h u8),
+// its valid plane and, if asked for, the source position of every pixel in 1/32
+// px as (qx, qy) pairs (INT32_MIN where the pixel looks outside the limits).
+struct Rectified {
+    std::vector<std::vector<uint8_t>> views, valid;
+    std::vector<std::vector<int32_t>> map;        // empty unless asked for
+};
+
+// Warps raw views of one size onto the ideal grid (sva_rectify), view i by
+// rect[i].  out_w, out_h 0: the source's size.  A pixel whose taps leave the
+// source takes `border` there and is not valid.
+inline Rectified rectifyViews(Engine& eng, const std::vector<ImageView>& raw,
+                              const std::vector<sva_rectify_view>& rect, int out_w = 0,
+                              int out_h = 0, int border = 0, bool want_map = false) {
+    const size_t n = raw.size();
+    if (n == 0 || rect.size() != n)
+        throw Error(SVA_ERR_INVALID_ARG, "rectifyViews: need one sva_rectify_view per view");
+    const int sw = raw[0].width, sh = raw[0].height;
+    const int W = out_w ? out_w : sw, H = out_h ? out_h : sh;
+    std::vector<uint8_t> src((size_t)sw * sh * n);
+    for (size_t i = 0; i < n; i++) {
+        if (raw[i].width != sw || raw[i].height != sh)
+            throw Error(SVA_ERR_INVALID_ARG, "rectifyViews: view size");
+        for (int y = 0; y < sh; y++)
+            std::copy(raw[i].data + (size_t)y * raw[i].pitch, raw[i].data + (size_t)y * raw[i].pitch + sw,
+                      src.begin() + (i * sh + y) * sw);
+    }
+    const size_t np = (size_t)W * H;
+    std::vector<uint8_t> out(np * n), valid(np * n);
+    std::vector<int32_t> map(want_map ? np * n * 2 : 0);
+    eng.check(sva_rectify(eng.handle(), src.data(), (int)n, sw, sh, (size_t)sw, rect.data(), W, H,
+                          (size_t)W, border, out.data(), valid.data(),
+                          want_map ? map.data() : nullptr));
+    return {detail::unpackPlanes(out, np, n), detail::unpackPlanes(valid, np, n),
+            detail::unpackPlanes(map, np * 2, n)};
+}
+
+// What maskMaps keeps of each map.
+struct MaskedMaps {
+    std::vector<std::vector<uint16_t>> maps;
+    std::vector<std::vector<float>> subpix;       // empty unless sub-pixel maps went in
+};
+
+// maps[i] takes `invalid`, and subpix[i] NaN, where valid[i] is 0 (sva_mask_maps):
+// what a rectified reference view's valid plane says about its disparity map.
+inline MaskedMaps maskMaps(Engine& eng, const std::vector<std::vector<uint16_t>>& maps,
+                           const std::vector<std::vector<float>>& subpix,
+                           const std::vector<std::vector<uint8_t>>& valid, int W, int H,
+                           uint16_t invalid = 0xFFFF) {
+    const char* need = "need one valid plane, and none or one sub-pixel map, per map";
+    detail::PackedMaps io = detail::packFilterMaps("maskMaps", need, maps, subpix, W, H);
+    if (valid.size() != io.n) throw Error(SVA_ERR_INVALID_ARG, std::string("maskMaps: ") + need);
+    std::vector<uint8_t> v;
+    for (const auto& plane : valid) {
+        if (plane.size() != io.np) throw Error(SVA_ERR_INVALID_ARG, "maskMaps: map size");
+        v.insert(v.end(), plane.begin(), plane.end());
+    }
+    eng.check(sva_mask_maps(eng.handle(), io.d.data(), io.sub(), (int)io.n, W, H, v.data(), invalid,
+                            io.d.data(), io.sub()));
+    return {detail::unpackPlanes(io.d, io.np, io.n), detail::unpackPlanes(io.s, io.np, io.n)};
+}
+
+// computeArrayDepthSmoothed's frame from RAW views (sva_array_depth_rectified):
+// every device rectifies the views it needs by rect (one per image) before its
+// jobs, and with mask every job's map is masked by its reference view's valid
+// plane before the cross-view check.  wmed_radius 0 switches the weighted median
+// off.  views, valid (nullable): the rectified views and their valid planes, one
+// per image (zeros for an image no pair names).
+inline std::vector<std::vector<double>> computeArrayDepthRectified(
+    MultiEngine& m, const std::vector<ImageView>& raw, const std::vector<sva_rectify_view>& rect,
+    const std::vector<Camera>& cameras, const std::vector<std::array<int, 2>>& pairs,
+    const sva_sgm_params& p, int wmed_radius = 0, const std::array<uint16_t, 256>* weights = nullptr,
+    int wmed_min_support = 1, bool wmed_select = false, int fill_max_dist = 0,
+    int fill_min_found = 1, int fill_mode = SVA_FILL_SECOND, int speckle_max_size = 0,
+    int speckle_max_diff = 0, int route = SVA_ARRAY_GROUPS, bool check = false, bool sub = false,
+    int max_diff = 1, int min_agree = 1, int max_conflict = 0, int uniqueness = 0,
+    int mode = SVA_FUSE_MEDIAN, double pitch = 0.05, int border = 0, bool mask = true,
+    std::vector<std::vector<uint16_t>>* maps = nullptr,
+    std::vector<std::vector<uint8_t>>* views = nullptr,
+    std::vector<std::vector<uint8_t>>* valid = nullptr) {
+    if (rect.size() != raw.size())
+        throw Error(SVA_ERR_INVALID_ARG,
+                    "computeArrayDepthRectified: need one sva_rectify_view per image");
+    const detail::ChainFrame cf(raw, cameras, pairs, p, route, pitch, "computeArrayDepthRectified");
+    const size_t np = (size_t)cf.fr.W * cf.fr.H, n = raw.size();
+    std::vector<uint8_t> vw(views ? np * n : 0), vd(valid ? np * n : 0);
+    auto depth = cf.depth(m, cameras, sva_array_depth_rectified, route, uniqueness, mode, maps, sub,
+                          max_diff, min_agree, max_conflict, (uint8_t*)nullptr, (uint8_t*)nullptr,
+                          check ? 1 : 0, speckle_max_size, speckle_max_diff, (uint32_t*)nullptr,
+                          fill_max_dist, fill_min_found, fill_mode, (uint8_t*)nullptr, wmed_radius,
+                          weights ? weights->data() : (const uint16_t*)nullptr, wmed_min_support,
+                          wmed_select ? 1 : 0, (uint16_t*)nullptr, rect.data(), border,
+                          mask ? 1 : 0, cf.ptr(vw), cf.ptr(vd));
+    if (views) *views = detail::unpackPlanes(vw, np, n);
+    if (valid) *valid = detail::unpackPlanes(vd, np, n);
+    return depth;
+}
+
 // ---- refinement and 3-D output ----
 // The reference's names and argument meaning; cv::Mat becomes ImageView (u8)
 // or a dense W*H std::vector<double>.  Pixels a routine does not write keep

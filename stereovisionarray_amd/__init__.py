@@ -78,7 +78,10 @@ EXPORTED = [
     "sva_array_depth_checked", "sva_filter_speckles", "sva_filter_speckles_d",
     "sva_array_depth_filtered", "sva_fill_holes", "sva_fill_holes_d", "sva_array_depth_filled",
     "sva_weighted_median", "sva_weighted_median_d", "sva_array_depth_smoothed",
+    "sva_rectify", "sva_rectify_d", "sva_rectify_view_of", "sva_mask_maps", "sva_mask_maps_d",
+    "sva_array_depth_rectified",
 ]
+SVA_RECTIFY_MAX_SIZE = 32767
 SVA_WMED_MAX_RADIUS = 15
 SVA_FILL_MIN = 0
 SVA_FILL_SECOND = 1
@@ -103,6 +106,21 @@ class SgmParams(ct.Structure):
         ("lr_check", ct.c_int32), ("lr_max_diff", ct.c_int32),
         ("invalid", ct.c_uint16), ("_pad", ct.c_uint16), ("dir_y", ct.c_int32),
     ]
+
+
+class RectifyView(ct.Structure):
+    """Mirror of ``sva_rectify_view`` (include/sva.h): h, the row-major 3x3 from a
+    rectified pixel to the undistorted raw pixel; the raw camera's cx, cy, fx, fy;
+    the Brown-Conrady coefficients k1, k2, p1, p2, k3."""
+    _fields_ = [("h", ct.c_double * 9), ("cx", ct.c_double), ("cy", ct.c_double),
+                ("fx", ct.c_double), ("fy", ct.c_double), ("k1", ct.c_double),
+                ("k2", ct.c_double), ("p1", ct.c_double), ("p2", ct.c_double),
+                ("k3", ct.c_double)]
+
+    @classmethod
+    def make(cls, h=(1, 0, 0, 0, 1, 0, 0, 0, 1), cx=0.0, cy=0.0, fx=1.0, fy=1.0, dist=(0,) * 5):
+        return cls((ct.c_double * 9)(*[float(v) for v in np.asarray(h).ravel()]), cx, cy, fx, fy,
+                   *[float(v) for v in dist])
 
 
 class Camera(ct.Structure):
@@ -197,6 +215,9 @@ def _load() -> ct.CDLL:
     speckle_tail = [i32, i32, i32, vp]
     fill_tail = [i32, i32, i32, vp]
     wmed_tail = [i32, vp, i32, i32, vp]
+    rect_tail = [P(RectifyView), i32, i32, vp, vp]
+    rectify = [vp, vp, i32, i32, i32, sz, P(RectifyView), i32, i32, sz, i32, vp, vp, vp]
+    mask = [vp, vp, vp, i32, i32, i32, vp, ct.c_uint16, vp, vp]
     sig = {
         "sva_sgm_params_default": (None, [P(SgmParams)]),
         "sva_abi_version": (i32, []),
@@ -319,6 +340,13 @@ def _load() -> ct.CDLL:
         "sva_array_depth_filled": (i32, routed + check_tail + speckle_tail + fill_tail),
         "sva_array_depth_smoothed": (i32, routed + check_tail + speckle_tail + fill_tail +
                                      wmed_tail),
+        "sva_array_depth_rectified": (i32, routed + check_tail + speckle_tail + fill_tail +
+                                      wmed_tail + rect_tail),
+        "sva_rectify_d": (i32, rectify),
+        "sva_rectify": (i32, rectify),
+        "sva_rectify_view_of": (i32, [P(dbl), P(dbl), P(dbl), P(dbl), P(RectifyView)]),
+        "sva_mask_maps_d": (i32, mask),
+        "sva_mask_maps": (i32, mask),
         "sva_weighted_median_d": (i32, [vp, vp, vp, vp, sz, vp, vp, i32, i32, i32, ct.c_uint16, i32,
                                         i32, i32, vp, vp, vp]),
         "sva_weighted_median": (i32, [vp, vp, vp, vp, sz, vp, vp, i32, i32, i32, ct.c_uint16, i32,
@@ -352,6 +380,31 @@ def wmed_weights(sigma) -> np.ndarray:
     if not sigma > 0:
         raise ValueError("sigma must be positive")
     return np.floor(1024.0 * np.exp(-np.arange(256) / float(sigma)) + 0.5).astype(np.uint16)
+
+
+def rectify_view(K_raw, dist, R, K_ideal) -> RectifyView:
+    """sva_rectify_view_of: the view of a calibration, h = K_raw .
+    R . K_ideal^-1 with R taking ideal-camera rays to raw-camera rays; dist = (k1,
+    k2, p1, p2, k3).  Host only."""
+    def arr(a, n):
+        a = np.ascontiguousarray(a, dtype=np.float64).ravel()
+        if a.size != n:
+            raise ValueError(f"expected {n} values")
+        return (ct.c_double * n)(*a)
+    out = RectifyView()
+    st = lib.sva_rectify_view_of(arr(K_raw, 9), arr(dist, 5), arr(R, 9), arr(K_ideal, 9),
+                                 ct.byref(out))
+    if st != SVA_OK:
+        raise SvaError(st, "sva_rectify_view_of")
+    return out
+
+
+def _view_table(rect):
+    """A sequence of RectifyView as a C array (one is passed through); None stays
+    a null pointer."""
+    if rect is None or isinstance(rect, ct.Array):
+        return rect
+    return (RectifyView * max(1, len(rect)))(*rect)
 
 
 def default_params(**kw) -> SgmParams:
@@ -1054,6 +1107,46 @@ class Context:
                                             invalid, int(radius), int(min_support), int(fill),
                                             _ptr(out), _ptr(out_sub), _ptr(support)))
 
+    def rectify(self, views: np.ndarray, rect, size=None, border=0, want_valid=False,
+                want_map=False):
+        """(out, valid or None, map or None): sva_rectify of n raw
+        views [n][src_h][src_w] u8 by rect, n RectifyView, onto size = (out_w, out_h)
+        (None: the source's).  valid [n][out_h][out_w] u8; map [n][out_h][out_w][2]
+        i32, the source position in 1/32 px (INT32_MIN where outside)."""
+        src = np.ascontiguousarray(views, dtype=np.uint8)
+        n, sh, sw = src.shape
+        assert len(rect) == n
+        W, H = (sw, sh) if size is None else (int(size[0]), int(size[1]))
+        out = np.zeros((n, H, W), np.uint8)
+        valid = np.zeros((n, H, W), np.uint8) if want_valid else None
+        qmap = np.zeros((n, H, W, 2), np.int32) if want_map else None
+        self._chk(lib.sva_rectify(self.h, _ptr(src), n, sw, sh, sw, _view_table(rect), W, H, W,
+                                  int(border), _ptr(out), _ptr(valid), _ptr(qmap)))
+        return out, valid, qmap
+
+    def rectify_d(self, src, n, src_w, src_h, src_pitch, rect, out_w, out_h, out_pitch, border,
+                  out, valid=None, map=None):
+        """sva_rectify_d on device pointers; rect: a sequence of n RectifyView (host)."""
+        self._chk(lib.sva_rectify_d(self.h, _ptr(src), n, src_w, src_h, int(src_pitch),
+                                    _view_table(rect), out_w, out_h, int(out_pitch), int(border),
+                                    _ptr(out), _ptr(valid), _ptr(map)))
+
+    def mask_maps(self, disps: np.ndarray, valid, invalid=0xFFFF, subpix=None):
+        """(out, out_sub or None): sva_mask_maps: n maps [n][H][W]
+        u16 take `invalid` -- and out_sub (with subpix) NaN -- where their valid
+        plane [n][H][W] u8 is 0."""
+        d, s, N, H, W, out, osub = self._filter_maps(disps, subpix)
+        v = np.ascontiguousarray(valid, dtype=np.uint8)
+        assert v.shape == d.shape
+        self._chk(lib.sva_mask_maps(self.h, _ptr(d), _ptr(s), N, W, H, _ptr(v), invalid, _ptr(out),
+                                    _ptr(osub)))
+        return out, osub
+
+    def mask_maps_d(self, disps, subpix, n_maps, W, H, valid, invalid, out, out_sub=None):
+        """sva_mask_maps_d on device pointers; out may be disps and out_sub subpix."""
+        self._chk(lib.sva_mask_maps_d(self.h, _ptr(disps), _ptr(subpix), n_maps, W, H, _ptr(valid),
+                                      invalid, _ptr(out), _ptr(out_sub)))
+
     def disparity_to_depth(self, disp: np.ndarray, cam_distance, f, pixel_size):
         d = np.ascontiguousarray(disp, dtype=np.uint8)
         out = np.zeros(d.shape, np.float64)
@@ -1246,13 +1339,14 @@ class Multi:
                      ("n_found", True, np.uint8), ("support", True, np.uint16))
 
     def _array_depth_chain(self, fn, images, pairs, group_start, f, pixel_size, route,
-                           unit_baseline, uniqueness, mode, view_step, sub, cross, want, stages=()):
+                           unit_baseline, uniqueness, mode, view_step, sub, cross, want, stages=(),
+                           extra=()):
         """One call of sva_array_depth_checked, _filtered, _filled or _smoothed.
         cross: (max_diff, min_agree, max_conflict); want: plane name -> asked for,
         for the planes the entry can return besides depth; stages: for each stage
         after the check, its argument group as (the scalars in C order, the name
-        of the plane that ends it).  Returns the planes as a dict, None where not
-        asked for."""
+        of the plane that ends it); extra: the arguments after the last stage.
+        Returns the planes as a dict, None where not asked for."""
         fr = _ArrayFrame(images, pairs, group_start)
         # jobs: pairs on the pair route, which only the entries after the check take
         nj = len(pairs) if stages and int(route) == SVA_ARRAY_PAIRS else fr.G
@@ -1268,7 +1362,7 @@ class Multi:
         for scalars, plane in stages:
             tail += [*scalars, _ptr(r[plane])]
         self._chk(fn(self.h, *fr.head, int(route), ub, f, pixel_size, int(uniqueness), int(mode),
-                     *tail))
+                     *tail, *extra))
         return r
 
     def array_depth_checked(self, images, pairs, group_start, f, pixel_size, view_step,
@@ -1360,6 +1454,43 @@ class Multi:
             [((int(check), int(speckle_max_size), int(speckle_max_diff)), "comp_size"),
              ((int(fill_max_dist), int(fill_min_found), int(fill_mode)), "n_found"),
              ((int(wmed_radius), _ptr(w), int(wmed_min_support), int(wmed_select)), "support")])
+
+    def array_depth_rectified(self, raw_views, rect, pairs, group_start, f, pixel_size,
+                              wmed_radius=0, wmed_weights=None, wmed_min_support=1, wmed_select=0,
+                              fill_max_dist=0, fill_min_found=1, fill_mode=SVA_FILL_SECOND,
+                              speckle_max_size=0, speckle_max_diff=0, check=0, view_step=None,
+                              route=SVA_ARRAY_GROUPS, unit_baseline=None, uniqueness=0,
+                              mode=SVA_FUSE_MEDIAN, sub=0, max_diff=1, min_agree=1,
+                              max_conflict=0, border=0, mask=1, want_sub=False, want_maps=False,
+                              want_costs=False, want_counts=False, want_size=False,
+                              want_n_valid=False, want_winner=False, want_found=False,
+                              want_support=False, want_views=False, want_valid=False):
+        """sva_array_depth_rectified: array_depth_smoothed's frame from RAW views
+        (DESIGN.md §2.5f, §7): every device rectifies the views it needs by rect
+        (one RectifyView per view) before its jobs; with mask = 1 every job's map
+        is masked by its reference view's valid plane before the cross-view check.
+        wmed_radius = 0 switches the weighted median off.  Returns
+        array_depth_smoothed's dict with views and valid [n_images,H,W] u8 added
+        (None unless asked for; a view no pair names stays zero)."""
+        w = None if wmed_weights is None else np.ascontiguousarray(wmed_weights, dtype=np.uint16)
+        assert w is None or w.shape == (256,)
+        n = len(raw_views)
+        H, W = np.asarray(raw_views[0]).shape
+        views = np.zeros((n, H, W), np.uint8) if want_views else None
+        valid = np.zeros((n, H, W), np.uint8) if want_valid else None
+        r = self._array_depth_chain(
+            lib.sva_array_depth_rectified, raw_views, pairs, group_start, f, pixel_size, route,
+            unit_baseline, uniqueness, mode, view_step, sub, (max_diff, min_agree, max_conflict),
+            dict(n_valid=want_n_valid, winner=want_winner, subpix=want_sub, maps=want_maps,
+                 cost_min=want_costs, cost_second=want_costs, agree=want_counts,
+                 conflict=want_counts, comp_size=want_size,
+                 n_found=want_found, support=want_support),
+            [((int(check), int(speckle_max_size), int(speckle_max_diff)), "comp_size"),
+             ((int(fill_max_dist), int(fill_min_found), int(fill_mode)), "n_found"),
+             ((int(wmed_radius), _ptr(w), int(wmed_min_support), int(wmed_select)), "support")],
+            extra=(_view_table(rect), int(border), int(mask), _ptr(views), _ptr(valid)))
+        r["views"], r["valid"] = views, valid
+        return r
 
     def array_depth(self, images, pairs, group_start, f, pixel_size, want_maps=False):
         """images: list of HxW u8 numpy views; pairs: list of (ref, other,

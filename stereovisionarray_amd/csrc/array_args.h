@@ -2,13 +2,15 @@
 // entries) and their validation, shared by multi.cpp and the host
 // test programs (tests/test_array_args_cpu.py, test_array_sub_args_cpu.py,
 // test_cross_check_cpu.py, test_speckle_cpu.py, test_fill_cpu.py and
-// test_wmed_cpu.py compile this header with a C++ compiler under the
-// sanitizers).  Plain C++: no HIP header.
+// test_wmed_cpu.py and test_rectify_cpu.py compile this header with a C++
+// compiler under the sanitizers).  Plain C++: no HIP header.
 //
 // The post-filter chain (DESIGN.md §7 has its table): between its jobs and its
 // depth step a frame passes the jobs' maps through the cross-view check, the
 // speckle filter, hole filling and the weighted median, in this order, each
 // enabled by its flag below (cross, speckle, fill, wmed) with its argument group.
+// With rect the frame starts from raw views: they are rectified on the devices
+// before the jobs, and with rect_mask the jobs' maps are masked before the chain.
 #pragma once
 
 #include <algorithm>
@@ -21,6 +23,7 @@
 #include "cost_mixed_math.h"
 #include "cross_check_math.h"
 #include "fill_math.h"
+#include "rectify_math.h"
 #include "speckle_math.h"
 #include "sva.h"
 #include "sva_native_d.h"
@@ -92,6 +95,15 @@ struct ArrayArgs {
     int wmed_radius = 1, wmed_min_support = 1, wmed_select = 0;
     const uint16_t* wmed_weights = nullptr;   // host, 256 entries, nullable
     uint16_t* support = nullptr;              // host, per job, nullable
+    // rect (sva_array_depth_rectified; speckle and fill are set
+    // too, wmed iff wmed_radius != 0): images are RAW views; every device runs
+    // sva_rectify_d over the views it needs, by rect_views[v], and with rect_mask
+    // every job's map goes through sva_mask_maps_d with its reference view's valid
+    // plane before the cross-view check
+    bool rect = false;
+    const sva_rectify_view* rect_views = nullptr;   // host, n_images
+    int rect_border = 0, rect_mask = 0;
+    uint8_t *views_out = nullptr, *valid_out = nullptr;   // host [n_images][H][W], nullable
 };
 
 inline int check_params(const sva_sgm_params& p) {
@@ -273,7 +285,10 @@ inline int check_frame_args(const ArrayArgs& a, std::string& msg, std::vector<in
 // plane without sub; speckle_max_size < 0; speckle_max_diff < 0.  With a.fill
 // after those: fill_max_dist, fill_min_found, fill_mode out of range.  With
 // a.wmed after those: wmed_radius, wmed_min_support out of range, wmed_select
-// outside 0 / 1.
+// outside 0 / 1.  With a.rect those three are checked whether a.wmed or not, a
+// wmed_radius of 0 allowed (the median off), and after them: a null rect_views;
+// the first rule a view breaks (rc::view_error, view 0 first); rect_border
+// outside 0..255; rect_mask outside 0 / 1.
 inline int check_array_args(const ArrayArgs& a, std::string& msg, std::vector<int32_t>& ratio) {
     if (int st = check_frame_args(a, msg, ratio)) return st;
     if (!a.speckle) return SVA_OK;
@@ -290,18 +305,30 @@ inline int check_array_args(const ArrayArgs& a, std::string& msg, std::vector<in
     if (a.fill)
         if (const char* m = fl::thresholds_error(a.fill_max_dist, a.fill_min_found, a.fill_mode))
             return fail(m);
-    if (a.wmed) {
-        if (const char* m = wm::thresholds_error(a.wmed_radius, a.wmed_min_support, 1))
-            return fail(m);
+    if (a.wmed || a.rect) {
+        const int radius = a.rect && a.wmed_radius == 0 ? 1 : a.wmed_radius;
+        if (const char* m = wm::thresholds_error(radius, a.wmed_min_support, 1)) return fail(m);
         if (a.wmed_select != 0 && a.wmed_select != 1) return fail("wmed select must be 0 or 1");
+    }
+    if (a.rect) {
+        if (!a.rect_views) return fail("null rect");
+        for (int v = 0; v < a.n_images; v++)
+            if (const char* m = rc::view_error(a.rect_views[v])) {
+                msg = std::string(m) + " (view " + std::to_string(v) + ")";
+                return (int)SVA_ERR_INVALID_ARG;
+            }
+        if (a.rect_border < 0 || a.rect_border > 255) return fail("border must be 0..255");
+        if (a.rect_mask != 0 && a.rect_mask != 1) return fail("mask must be 0 or 1");
     }
     return SVA_OK;
 }
 
 // Which views does each device need?  Pair j runs on device dev_of[j] and needs
 // its ref and its other there.  With refs_on_0 (the weighted median stage: the
-// guide of a job is its reference view, and the filter runs on device 0) the
-// reference view of every pair is needed on device 0 as well.  Out: slot_of[d][v],
+// guide of a job is its reference view, and the filter runs on device 0; the
+// rectified frame's mask: the valid plane of a job's reference view is made where
+// the view is rectified, and sva_mask_maps_d runs on device 0) the reference view
+// of every pair is needed on device 0 as well.  Out: slot_of[d][v],
 // the slot of view v in device d's image buffer (-1: not needed there), slots
 // numbered in the order the pairs name them, the extra references of device 0
 // last; n_need[d], the number of slots; used[v], whether any device needs v.

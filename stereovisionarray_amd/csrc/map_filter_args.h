@@ -1,6 +1,7 @@
 // map_filter_args.h -- the arguments of the four map filters of the post-filter
 // chain (sva_cross_check, sva_filter_speckles,
-// sva_fill_holes, sva_weighted_median and their _d twins) and their validation,
+// sva_fill_holes, sva_weighted_median and their _d twins), of sva_mask_maps
+// (§2.5g) and of sva_rectify (§2.5f), and their validation,
 // shared by sva_api.cpp and a host test program
 // (tests/test_map_filter_args_cpu.py compiles this header with a C++ compiler
 // under the sanitizers).  Plain C++: no HIP header.  The rule functions only
@@ -13,6 +14,7 @@
 
 #include "cross_check_math.h"
 #include "fill_math.h"
+#include "rectify_math.h"
 #include "speckle_math.h"
 #include "sva.h"
 #include "wmedian_math.h"
@@ -57,6 +59,26 @@ struct WmedArgs {
     const uint8_t* select;
     int radius, min_support, fill;
     uint16_t* support;
+};
+
+// sva_mask_maps: one valid plane [H][W] u8 per map.
+struct MaskArgs {
+    MapArgs m;
+    const uint8_t* valid;
+};
+
+// sva_rectify: n raw views in, n rectified views out, all on the host or all on
+// the device; views is always a host array.
+struct RectifyArgs {
+    const uint8_t* src;
+    int n, src_w, src_h;
+    size_t src_pitch;
+    const sva_rectify_view* views;
+    int out_w, out_h;
+    size_t out_pitch;
+    int border;
+    uint8_t *out, *valid;
+    int32_t* map;
 };
 
 namespace mf {
@@ -173,6 +195,49 @@ inline int check_wmed(const WmedArgs& a, std::string& msg) {
         if (a.guides && a.guide_pitch < (size_t)a.m.W) return "guide pitch < width";
         return nullptr;
     }, {a.select, 1}, {a.support, 2}, a.guides, a.guide_pitch, msg);
+}
+
+inline int check_mask(const MaskArgs& a, std::string& msg) {
+    const mf::Rules r = {"masking", 0, "n_maps must be >= 1", true, true, mf::kInPlace};
+    return mf::check_filter(a.m, r, !a.valid, [] { return (const char*)nullptr; }, {a.valid, 1},
+                            {}, nullptr, 0, msg);
+}
+
+// The rules of sva_rectify and sva_rectify_d, in sva.h's order.
+inline int check_rectify(const RectifyArgs& a, std::string& msg) {
+    auto fail = [&](int code, const std::string& text) {
+        msg = text;
+        return code;
+    };
+    if (!a.src || !a.views || !a.out) return fail(SVA_ERR_INVALID_ARG, "null pointer");
+    if (a.n < 1) return fail(SVA_ERR_INVALID_ARG, "n must be >= 1");
+    if (a.src_w <= 0 || a.src_h <= 0 || a.out_w <= 0 || a.out_h <= 0)
+        return fail(SVA_ERR_INVALID_ARG, "image size must be positive");
+    if (a.src_w > rc::kMaxSize || a.src_h > rc::kMaxSize || a.out_w > rc::kMaxSize ||
+        a.out_h > rc::kMaxSize)
+        return fail(SVA_ERR_UNSUPPORTED, "rectification takes widths and heights up to 32767");
+    if (a.src_pitch < (size_t)a.src_w || a.out_pitch < (size_t)a.out_w)
+        return fail(SVA_ERR_INVALID_ARG, "pitch < width");
+    if (a.border < 0 || a.border > 255) return fail(SVA_ERR_INVALID_ARG, "border must be 0..255");
+    // n * h rows of w bytes, pitch apart
+    const size_t rows_out = mf::sat_bytes((unsigned long long)a.n, (size_t)a.out_h);
+    const mf::Plane src = {a.src, mf::sat_bytes(mf::sat_bytes((unsigned long long)a.n,
+                                                              (size_t)a.src_h) - 1,
+                                                a.src_pitch, (size_t)a.src_w)};
+    const size_t out_bytes = mf::sat_bytes(rows_out - 1, a.out_pitch, (size_t)a.out_w);
+    const mf::Plane out[3] = {{a.out, out_bytes}, {a.valid, out_bytes},
+                              {a.map, mf::sat_bytes(rows_out, (size_t)a.out_w * 8)}};
+    for (int o = 0; o < 3; o++) {
+        bool bad = mf::ranges_overlap(out[o], src);
+        for (int q = o + 1; q < 3; q++) bad = bad || mf::ranges_overlap(out[o], out[q]);
+        if (bad)
+            return fail(SVA_ERR_INVALID_ARG,
+                        "an output overlaps the source or another output (in place is not offered)");
+    }
+    for (int i = 0; i < a.n; i++)
+        if (const char* t = rc::view_error(a.views[i]))
+            return fail(SVA_ERR_INVALID_ARG, std::string(t) + " (view " + std::to_string(i) + ")");
+    return SVA_OK;
 }
 
 }  // namespace sva

@@ -123,7 +123,9 @@ struct Multi {
     DevBuf speckle0;                   // device 0: comp_size planes (sva_array_depth_filtered)
     DevBuf fill0;                      // device 0: n_found planes (sva_array_depth_filled)
     DevBuf wmed0;                      // device 0: the smoothed planes (sva_array_depth_smoothed)
-    PinnedBuf stage_in, stage_out;
+    std::vector<DevBuf> raw, rvalid;   // per device: raw views and the rectified views' valid
+                                       // planes, in images' slots (sva_array_depth_rectified)
+    PinnedBuf stage_in, stage_out, stage_rect;
     Rccl rccl;
     std::vector<ncclComm_t> comms;
     std::string last_error;
@@ -584,6 +586,8 @@ int sva_multi_create(const int* devices, int n_devices, int spd, int flags, void
     m->ctx.assign((size_t)n_devices * spd, nullptr);
     m->slots.resize((size_t)n_devices * spd);
     m->images.resize(n_devices);
+    m->raw.resize(n_devices);
+    m->rvalid.resize(n_devices);
     m->gathered.assign(n_devices, nullptr);
     m->ev_all.resize(n_devices);
     m->ev_used.assign(n_devices, 0);
@@ -635,6 +639,8 @@ int sva_multi_destroy(void* mp) {
         (void)hipSetDevice(m->devices[d]);
         for (int s = 0; s < m->spd; s++) m->slots[d * m->spd + s].release();
         m->images[d].release();
+        m->raw[d].release();
+        m->rvalid[d].release();
         if (d < m->copy.size() && m->copy[d]) (void)hipStreamDestroy(m->copy[d]);
         if (d < m->down.size() && m->down[d]) (void)hipStreamDestroy(m->down[d]);
     }
@@ -653,6 +659,7 @@ int sva_multi_destroy(void* mp) {
     }
     m->stage_in.release();
     m->stage_out.release();
+    m->stage_rect.release();
     for (size_t d = 0; d < m->devices.size(); d++) {
         (void)hipSetDevice(m->devices[d]);
         if (d < m->ev_all.size())
@@ -731,9 +738,15 @@ int batch_sgm_d(void* mp, const sva_pair_d* jobs, int n_jobs, int W, int H, size
 // slot of view v in m->images[d] (-1: not needed there), and up_ev[d][v], the
 // event of its upload on the device's copy stream.  plan_views (array_args.h)
 // decides who needs what; refs_on_0: every reference view on device 0 too.
+// rect (sva_array_depth_rectified; null for every other entry): the host views
+// are RAW.  They land in m->raw[d], one sva_rectify_d launch per device on its
+// copy stream writes the slots of m->images[d] -- and, where a mask or valid_out
+// needs them, of m->rvalid[d] -- and up_ev[d][v] is recorded after that launch.
+// views_out / valid_out are copied out here, from the first device that has the
+// view, before this returns.
 int upload_views(Multi* m, const uint8_t* const* images, int n_images, int W, int H, size_t pitch,
                  const sva_array_pair* pairs, int n_pairs, const std::vector<int32_t>& dev_of,
-                 bool refs_on_0, std::vector<std::vector<int>>& slot_of,
+                 bool refs_on_0, const ArrayArgs* rect, std::vector<std::vector<int>>& slot_of,
                  std::vector<std::vector<hipEvent_t>>& up_ev) {
     const size_t np = (size_t)W * H;
     if (m->copy.empty()) {
@@ -773,15 +786,70 @@ int upload_views(Multi* m, const uint8_t* const* images, int n_images, int W, in
             if (st) return st;
         }
         MHIP(m, m->images[d].ensure((size_t)n_need[d] * np), "view workspace");
+        if (rect) MHIP(m, m->raw[d].ensure((size_t)n_need[d] * np), "raw view workspace");
+        uint8_t* land = (uint8_t*)(rect ? m->raw[d].ptr : m->images[d].ptr);
         for (int v = 0; v < n_images; v++) {
             if (slot_of[d][v] < 0) continue;
-            MHIP(m, hipMemcpyAsync((uint8_t*)m->images[d].ptr + (size_t)slot_of[d][v] * np,
+            MHIP(m, hipMemcpyAsync(land + (size_t)slot_of[d][v] * np,
                                    (uint8_t*)m->stage_in.ptr + (size_t)pin_slot[v] * np, np,
                                    hipMemcpyHostToDevice, m->copy[d]),
                  "upload");
+            if (rect) continue;
             MHIP(m, ev_on(m, d, &up_ev[d][v]), "event");
             MHIP(m, hipEventRecord(up_ev[d][v], m->copy[d]), "event record");
         }
+    }
+    if (!rect) return SVA_OK;
+    // 3. one rectify launch per device behind its uploads, through the device's
+    // first context with the copy stream as its stream; one event for all its views
+    std::vector<int> home(n_images, -1);   // the first device that has the view
+    const bool want_out = rect->views_out || rect->valid_out;
+    if (want_out) MHIP(m, m->stage_rect.ensure((size_t)n_pin * np * 2), "pinned staging");
+    for (int d = 0; d < m->nd(); d++) {
+        if (!n_need[d]) continue;
+        MHIP(m, hipSetDevice(m->devices[d]), "hipSetDevice");
+        const bool want_valid = (d == 0 && rect->rect_mask) || rect->valid_out;
+        if (want_valid) MHIP(m, m->rvalid[d].ensure((size_t)n_need[d] * np), "valid workspace");
+        std::vector<sva_rectify_view> table(n_need[d]);
+        for (int v = 0; v < n_images; v++)
+            if (slot_of[d][v] >= 0) table[slot_of[d][v]] = rect->rect_views[v];
+        Ctx* c = m->c(d, 0);
+        const hipStream_t own = c->stream;
+        c->stream = m->copy[d];
+        const int st = sva_rectify_d(c, (const uint8_t*)m->raw[d].ptr, n_need[d], W, H, (size_t)W,
+                                     table.data(), W, H, (size_t)W, rect->rect_border,
+                                     (uint8_t*)m->images[d].ptr,
+                                     want_valid ? (uint8_t*)m->rvalid[d].ptr : nullptr, nullptr);
+        c->stream = own;
+        if (st) return m->ctx_fail(st, c, "rectify");
+        hipEvent_t done;
+        MHIP(m, ev_on(m, d, &done), "event");
+        MHIP(m, hipEventRecord(done, m->copy[d]), "event record");
+        for (int v = 0; v < n_images; v++) {
+            if (slot_of[d][v] < 0) continue;
+            up_ev[d][v] = done;
+            if (!want_out || home[v] >= 0) continue;
+            home[v] = d;
+            uint8_t* pin = (uint8_t*)m->stage_rect.ptr + (size_t)pin_slot[v] * np * 2;
+            const size_t at = (size_t)slot_of[d][v] * np;
+            if (rect->views_out)
+                MHIP(m, hipMemcpyAsync(pin, (uint8_t*)m->images[d].ptr + at, np,
+                                       hipMemcpyDeviceToHost, m->copy[d]), "download");
+            if (rect->valid_out)
+                MHIP(m, hipMemcpyAsync(pin + np, (uint8_t*)m->rvalid[d].ptr + at, np,
+                                       hipMemcpyDeviceToHost, m->copy[d]), "download");
+        }
+    }
+    for (int d = 0; want_out && d < m->nd(); d++) {
+        if (!n_need[d]) continue;
+        MHIP(m, hipSetDevice(m->devices[d]), "hipSetDevice");
+        MHIP(m, hipStreamSynchronize(m->copy[d]), "synchronize");
+    }
+    for (int v = 0; want_out && v < n_images; v++) {
+        if (home[v] < 0) continue;
+        const uint8_t* pin = (const uint8_t*)m->stage_rect.ptr + (size_t)pin_slot[v] * np * 2;
+        if (rect->views_out) std::memcpy(rect->views_out + (size_t)v * np, pin, np);
+        if (rect->valid_out) std::memcpy(rect->valid_out + (size_t)v * np, pin + np, np);
     }
     return SVA_OK;
 }
@@ -831,6 +899,8 @@ struct Download {
 // checked or not -- then passes through sva_filter_speckles_d in place, and
 // with a.fill (sva_array_depth_filled, §2.5d) through sva_fill_holes_d after it,
 // and with a.wmed (sva_array_depth_smoothed, §2.5e) through sva_weighted_median_d.
+// With a.rect (sva_array_depth_rectified, §2.5f) the views are raw: upload_views
+// rectifies them, and with a.rect_mask step 3a masks the gathered maps.
 int array_frame(void* mp, const ArrayArgs& a) {
     Multi* m = as_multi(mp);
     if (!m) return SVA_ERR_INVALID_ARG;
@@ -855,7 +925,8 @@ int array_frame(void* mp, const ArrayArgs& a) {
     std::vector<std::vector<int>> slot_of;
     std::vector<std::vector<hipEvent_t>> up_ev;
     if (int st = upload_views(m, a.images, a.n_images, W, H, a.pitch, pairs, n_pairs, dev_of,
-                              a.wmed, slot_of, up_ev))
+                              a.wmed || (a.rect && a.rect_mask), a.rect ? &a : nullptr, slot_of,
+                              up_ev))
         return st;
     // 3. jobs + gather into maps0 on device 0
     MHIP(m, hipSetDevice(m->devices[0]), "hipSetDevice");
@@ -922,6 +993,21 @@ int array_frame(void* mp, const ArrayArgs& a) {
         },
         group ? "group" : "pair");
     if (st) return st;
+    // 3a. the mask of a frame from raw views: every job's map (and f32 map), in
+    // place, by the valid plane of its reference view on device 0
+    if (a.rect && a.rect_mask) {
+        MHIP(m, hipSetDevice(m->devices[0]), "hipSetDevice");
+        for (int k = 0; k < n_jobs; k++) {
+            const int v = pairs[first[k]].ref;
+            const size_t o = (size_t)k * np;
+            MHIP(m, hipStreamWaitEvent(m->st(0, 0), up_ev[0][v], 0), "wait");
+            st = sva_mask_maps_d(m->ctx[0], maps0 + o, sub0 ? sub0 + o : nullptr, 1, W, H,
+                                 (const uint8_t*)m->rvalid[0].ptr + (size_t)slot_of[0][v] * np,
+                                 pairs[first[k]].params.invalid, maps0 + o,
+                                 sub0 ? sub0 + o : nullptr);
+            if (st) return m->ctx_fail(st, m->ctx[0], "mask");
+        }
+    }
     // 3b. the cross-view check: one pass on device 0 over the gathered maps into
     // planes of cross0 -- u16 maps, f32 maps (sub), agree, conflict -- which take
     // the place of maps0 / sub0 from here on
@@ -1338,6 +1424,39 @@ int sva_array_depth_smoothed(void* mp, const uint8_t* const* images, int n_image
     set_speckle(a, check, speckle_max_size, speckle_max_diff, comp_size);
     set_fill(a, fill_max_dist, fill_min_found, fill_mode, n_found);
     set_wmed(a, wmed_radius, wmed_weights, wmed_min_support, wmed_select, support);
+    return sub_frame(mp, a, sub);
+}
+
+// wmed_radius = 0: the weighted median is off (this entry only).
+int sva_array_depth_rectified(void* mp, const uint8_t* const* images, int n_images, int W, int H,
+                              size_t pitch, const sva_array_pair* pairs, int n_pairs,
+                              const int32_t* group_start, int n_groups, int route,
+                              const double* unit_baseline, double f, double pixel_size,
+                              int uniqueness, int mode, double* depth, uint8_t* n_valid,
+                              uint8_t* winner, float* subpix, uint16_t* maps, uint16_t* cost_min,
+                              uint16_t* cost_second, const int32_t* view_step, int sub,
+                              int max_diff, int min_agree, int max_conflict, uint8_t* agree,
+                              uint8_t* conflict, int check, int speckle_max_size,
+                              int speckle_max_diff, uint32_t* comp_size, int fill_max_dist,
+                              int fill_min_found, int fill_mode, uint8_t* n_found, int wmed_radius,
+                              const uint16_t* wmed_weights, int wmed_min_support, int wmed_select,
+                              uint16_t* support, const sva_rectify_view* rect, int border,
+                              int mask, uint8_t* views_out, uint8_t* valid_out) {
+    ArrayArgs a = routed_args(images, n_images, W, H, pitch, pairs, n_pairs, group_start, n_groups,
+                              route, unit_baseline, f, pixel_size, uniqueness, mode, depth, n_valid,
+                              winner, subpix, maps, cost_min, cost_second);
+    set_cross(a, check == 1, view_step, max_diff, min_agree, max_conflict, agree, conflict);
+    set_speckle(a, check, speckle_max_size, speckle_max_diff, comp_size);
+    set_fill(a, fill_max_dist, fill_min_found, fill_mode, n_found);
+    set_wmed(a, wmed_radius, wmed_weights, wmed_min_support, wmed_select, support);
+    a.wmed = wmed_radius != 0;
+    if (!a.wmed) a.support = nullptr;   // no stage writes it: left untouched
+    a.rect = true;
+    a.rect_views = rect;
+    a.rect_border = border;
+    a.rect_mask = mask;
+    a.views_out = views_out;
+    a.valid_out = valid_out;
     return sub_frame(mp, a, sub);
 }
 

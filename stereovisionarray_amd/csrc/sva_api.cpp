@@ -608,6 +608,12 @@ struct Staging {
         if (st == SVA_OK && dst)
             note(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream), "download");
     }
+    // rows of W bytes packed on the device, `pitch` apart at the caller's
+    void down2d(void* dst, size_t pitch, const void* src, size_t W, size_t rows) {
+        if (st == SVA_OK && dst)
+            note(hipMemcpy2DAsync(dst, pitch, src, W, W, rows, hipMemcpyDeviceToHost, c->stream),
+                 "download");
+    }
     int sync() {
         if (st == SVA_OK) note(hipStreamSynchronize(c->stream), "sync");
         return st;
@@ -775,6 +781,58 @@ int wmed_host(Ctx* c, const WmedArgs& a) {
     if (int st = run_wmed(c, d)) return st;
     s.g.down(a.support, d.support, s.nnp * 2);
     return s.done();
+}
+
+int run_mask(Ctx* c, const MaskArgs& a) {
+    const MapArgs& m = a.m;
+    SVA_HIP(c, launch_mask_maps(*c, m.disps, m.subpix, a.valid, m.n, m.W, m.H, m.invalid, m.out,
+                                m.out_sub),
+            "mask launch");
+    return SVA_OK;
+}
+
+// valid stages through in_c.
+int mask_host(Ctx* c, const MaskArgs& a) {
+    StagedMaps s(c, a.m, true, a.m.out_sub != nullptr);
+    MaskArgs d = a;
+    d.m = s.d;
+    d.valid = s.g.up<uint8_t>(c->in_c, a.valid, s.nnp);
+    if (s.g.st) return s.g.st;
+    if (int st = run_mask(c, d)) return st;
+    return s.done();
+}
+
+int run_rectify(Ctx* c, const RectifyArgs& a) {
+    SVA_HIP(c, launch_rectify(*c, a.src, a.n, a.src_w, a.src_h, a.src_pitch, a.views, a.out_w,
+                              a.out_h, a.out_pitch, a.border, a.out, a.valid, a.map),
+            "rectify launch");
+    return SVA_OK;
+}
+
+// The views are packed on the device: src through in_a, out through out_a, valid
+// through out_c and map through out_b; the caller's pitches hold on the host only.
+int rectify_host(Ctx* c, const RectifyArgs& a) {
+    Staging g{c};
+    const size_t rows_in = (size_t)a.n * a.src_h, rows_out = (size_t)a.n * a.out_h;
+    const size_t nout = rows_out * a.out_w;
+    RectifyArgs d = a;
+    uint8_t* ds = g.out<uint8_t>(c->in_a, rows_in * a.src_w);
+    if (g.st == SVA_OK)
+        g.note(hipMemcpy2DAsync(ds, a.src_w, a.src, a.src_pitch, a.src_w, rows_in,
+                                hipMemcpyHostToDevice, c->stream),
+               "upload");
+    d.src = ds;
+    d.src_pitch = (size_t)a.src_w;
+    d.out_pitch = (size_t)a.out_w;
+    d.out = g.out<uint8_t>(c->out_a, nout);
+    d.valid = a.valid ? g.out<uint8_t>(c->out_c, nout) : nullptr;
+    d.map = a.map ? g.out<int32_t>(c->out_b, nout * 8) : nullptr;
+    if (g.st) return g.st;
+    if (int st = run_rectify(c, d)) return st;
+    g.down2d(a.out, a.out_pitch, d.out, (size_t)a.out_w, rows_out);
+    g.down2d(a.valid, a.out_pitch, d.valid, (size_t)a.out_w, rows_out);
+    g.down(a.map, d.map, nout * 8);
+    return g.sync();
 }
 
 // One entry: the context, the rules, then the call on device planes (host null)
@@ -2058,6 +2116,40 @@ int sva_weighted_median(void* ctx, const uint16_t* disps, const float* subpix,
                                         guide_pitch, weights, select, radius, min_support, fill,
                                         support},
                                   check_wmed, run_wmed, wmed_host);
+}
+
+// ------------------------- rectification and masking --
+int sva_rectify_d(void* ctx, const uint8_t* src, int n, int src_w, int src_h, size_t src_pitch,
+                  const sva_rectify_view* views, int out_w, int out_h, size_t out_pitch,
+                  int border, uint8_t* out, uint8_t* valid, int32_t* map) {
+    return filter_entry<RectifyArgs>(ctx, {src, n, src_w, src_h, src_pitch, views, out_w, out_h,
+                                           out_pitch, border, out, valid, map},
+                                     check_rectify, run_rectify, nullptr);
+}
+
+int sva_rectify(void* ctx, const uint8_t* src, int n, int src_w, int src_h, size_t src_pitch,
+                const sva_rectify_view* views, int out_w, int out_h, size_t out_pitch, int border,
+                uint8_t* out, uint8_t* valid, int32_t* map) {
+    return filter_entry<RectifyArgs>(ctx, {src, n, src_w, src_h, src_pitch, views, out_w, out_h,
+                                           out_pitch, border, out, valid, map},
+                                     check_rectify, run_rectify, rectify_host);
+}
+
+int sva_rectify_view_of(const double K_raw[9], const double dist[5], const double R[9],
+                        const double K_ideal[9], sva_rectify_view* out) {
+    return rc::view_of(K_raw, dist, R, K_ideal, out) ? SVA_ERR_INVALID_ARG : SVA_OK;
+}
+
+int sva_mask_maps_d(void* ctx, const uint16_t* disps, const float* subpix, int n, int W, int H,
+                    const uint8_t* valid, uint16_t invalid, uint16_t* out, float* out_sub) {
+    return filter_entry<MaskArgs>(ctx, {{disps, subpix, n, W, H, invalid, out, out_sub}, valid},
+                                  check_mask, run_mask, nullptr);
+}
+
+int sva_mask_maps(void* ctx, const uint16_t* disps, const float* subpix, int n, int W, int H,
+                  const uint8_t* valid, uint16_t invalid, uint16_t* out, float* out_sub) {
+    return filter_entry<MaskArgs>(ctx, {{disps, subpix, n, W, H, invalid, out, out_sub}, valid},
+                                  check_mask, run_mask, mask_host);
 }
 
 // ------------------------------------------ refinement / 3-D --

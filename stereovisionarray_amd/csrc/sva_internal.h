@@ -280,6 +280,16 @@ hipError_t launch_wmedian(Ctx& c, const uint16_t* disps, const float* subpix,
                           const uint8_t* select, int n, int W, int H, uint16_t invalid, int radius,
                           int min_support, int fill, uint16_t* out, float* out_sub,
                           uint16_t* support);
+// rectify.hip -- rectification: n views [n][sh][src_pitch] onto
+// [n][H][out_pitch]; views a HOST array of n, read before the call returns; valid
+// (u8, out's layout) and map (i32 [n][H][W][2]) nullable.  Sizes 1..32767.
+hipError_t launch_rectify(Ctx& c, const uint8_t* src, int n, int sw, int sh, size_t src_pitch,
+                          const sva_rectify_view* views, int W, int H, size_t out_pitch,
+                          int border, uint8_t* out, uint8_t* valid, int32_t* map);
+// sva_mask_maps (§2.5g): out = valid ? disps : invalid, out_sub = valid ? subpix : NaN.
+hipError_t launch_mask_maps(Ctx& c, const uint16_t* disps, const float* subpix,
+                            const uint8_t* valid, int n, int W, int H, uint16_t invalid,
+                            uint16_t* out, float* out_sub);
 // refpath.hip
 hipError_t launch_ref_endpoints(Ctx& c, int W, int H, const sva_camera& cref,
                                 const sva_camera& coth, int k, double t_near, double t_far,

@@ -332,5 +332,16 @@ constexpr int kWmedTileW = 32, kWmedTileH = 8;
 // the 512-byte table): n_maps beyond this take a further launch.
 constexpr int kWmedLaunchMaps = 64;
 
+// ---- rectify.hip ------------------------------------------
+// A thread owns kRectPixels adjacent output pixels and stores them as one dword
+// (the store width is the reason for 4; not swept).  A workgroup is kRectBlockX x
+// kRectBlockY threads: 256 x 4 pixels, one wave per output row segment.
+constexpr int kRectPixels = 4;
+constexpr int kRectBlockX = 64, kRectBlockY = 4;
+// The views of one launch travel in the kernel's arguments, 144 bytes each
+// beside 64 bytes of planes and sizes, in a 4 KiB segment: a 25-camera frame is
+// one launch, n beyond this take a further one.
+constexpr int kRectLaunchViews = 25;
+
 }  // namespace tune
 }  // namespace sva
